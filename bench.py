@@ -11,8 +11,11 @@ torch.distributed; `--dist-backend gloo` (rehearsal with more ranks than GPUs) k
 The collective is inside the timed region. Total work is fixed: strong scaling.
 
 Inputs are resident in HBM before the timed region (scene upload + pool allocation happen in setup/warm-up).
-The JSON line carries `roofline` for the dominant kernel (closest-hit BVH traversal + triangle tests) and
-`cpu_baseline` (the f64 oracle on the host cores, bounded sample, rank 0 at N=1 only).
+A plain run sets up, renders one counting frame (the exact query counts `value` is made of), warms up, times
+--steps frames and prints the JSON line. `--dump-outputs DIR` writes the film of the last timed frame to DIR.
+`--full` adds what takes runs of its own after the timed region: `roofline` for the dominant kernel (closest-hit
+BVH traversal + triangle tests, from frames one at a time), `kernel_ms_per_frame_one_at_a_time` and `cpu_baseline`
+(the f64 oracle on the host cores, bounded sample, rank 0 at N=1 only).
 """
 import argparse
 import ctypes as C
@@ -95,6 +98,27 @@ def cpu_baseline(scene, target_seconds):
             "camera_mrays_per_s": round(rays / secs / 1e6, 4), "est_full_frame_s": round(secs * H / rows, 1)}
 
 
+DUMP_BYTES = 64 * 10**6   # cap on what --dump-outputs writes
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: the film a caller of the timed path receives (device, H x W x 4 float32: XYZ sums + filter weight sum) as
+    out_dir/film.npy. A film above DUMP_BYTES (2048^2 and larger) is written as a fixed sample instead: DUMP_SAMPLE_PIXELS pixels drawn
+    without replacement by numpy's default_rng(0), in index order, as film_sample.npy (n x 4 float32) and their row-major pixel
+    indices as film_sample_pixels.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = film.detach().float().cpu().numpy()
+    if a.nbytes + 4096 <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=min(DUMP_SAMPLE_PIXELS, px.shape[0]), replace=False))
+    np.save(os.path.join(out_dir, "film_sample.npy"), np.ascontiguousarray(px[idx]))
+    np.save(os.path.join(out_dir, "film_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,8 +132,14 @@ def main():
     ap.add_argument("--depth", type=int, default=0, help="default: the configuration's own (8 / 16)")
     ap.add_argument("--grid", type=int, default=224, help="heightfield cells per side (224 -> 100 352 triangles)")
     ap.add_argument("--compat-bvh", action="store_true", help="reference-exact builder incl. Q26/Q27 (default: fixed-bvh)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own after the timed region: frames one at a time and with the shadow launches on the main stream "
+                         "(kernel_ms_per_frame_one_at_a_time, roofline) and the f64 CPU baseline (cpu_baseline, unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed step to DIR (rank 0): film.npy, float32 H x W x 4 (XYZ sums + filter weight sum); "
+                         "a fixed sample of its pixels when it exceeds 64 MB (dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the cpu_baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline")
     ap.add_argument("--max-paths", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="handle option key=value (rrt_set_option), e.g. pt_split_any=1e9")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
@@ -119,6 +149,8 @@ def main():
                          "launches leave more of the chip to fill: tools/band_pipeline.py); n >= 2: alternate n handles (rrt_render_bands_begin / _end): a frame's latency-bound last bounces drain "
                          "while the next frame's camera rays fill the chip; 1: one synchronous frame at a time")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     full_size = {"cfg4": (1024, 256, 8), "cfg5": (2048, 1024, 16)}[args.config]
     args.res, args.spp, args.depth = args.res or full_size[0], args.spp or full_size[1], args.depth or full_size[2]
     at_full_size = (args.res, args.spp, args.depth) == full_size and args.grid == 224
@@ -268,29 +300,37 @@ def main():
     # per-kernel durations: HIP events on the handles' own streams around every launch of every frame of the timed region, averaged per frame
     assert len(frame_log) == args.steps
     timed = {k: sum(f[k] for f in frame_log) / len(frame_log) for k in frame_log[0]}
-    # Kernel durations for the roofline (after the timed region, not part of `value`): the same frames ONE AT A TIME on the first handle. With
-    # several frames in flight an event pair around a launch also holds the time the stream waits for compute units behind the other frame's
-    # kernels, and rocprofv3's per-dispatch duration of a persistent launch holds the time it runs on the few CUs it got first - neither is the
-    # kernel's duration. One frame at a time both views coincide (profiles/: kernel_stats_1flight.csv of `bench.py --frames-in-flight 1`).
-    step()
-    single = [step(collect=True) for _ in range(max(2, args.steps // 2))]
-    single = {k: sum(f[k] for f in single) / len(single) for k in single[0]}
-    # ... and with the shadow launches back on the main stream: the closest-hit kernel alone on the chip
-    r.set_option("overlap_shadow", 0)
-    step()
-    isolated = step(collect=True)
-    r.set_option("overlap_shadow", 1)
-    sync()
+    if args.dump_outputs and rank == 0:
+        # the film of the last timed step (frame steps - 1 rendered on handle (steps - 1) % nfl), before any later frame reuses it
+        dump_outputs(args.dump_outputs, films[(args.steps - 1) % nfl])
+
+    single = isolated = None
+    if args.full:
+        # Kernel durations for the roofline (after the timed region, not part of `value`): the same frames ONE AT A TIME on the first handle. With
+        # several frames in flight an event pair around a launch also holds the time the stream waits for compute units behind the other frame's
+        # kernels, and rocprofv3's per-dispatch duration of a persistent launch holds the time it runs on the few CUs it got first - neither is the
+        # kernel's duration. One frame at a time both views coincide (profiles/: kernel_stats_1flight.csv of `bench.py --full --frames-in-flight 1`).
+        step()
+        single = [step(collect=True) for _ in range(max(2, args.steps // 2))]
+        single = {k: sum(f[k] for f in single) / len(single) for k in single[0]}
+        # ... and with the shadow launches back on the main stream: the closest-hit kernel alone on the chip
+        r.set_option("overlap_shadow", 0)
+        step()
+        isolated = step(collect=True)
+        r.set_option("overlap_shadow", 1)
+        sync()
 
     stat_dev = "cpu" if args.dist_backend == "gloo" else f"cuda:{local_rank}"
     tt = torch.tensor([elapsed], dtype=torch.float64, device=stat_dev)
     keys = ["camera_samples", "camera_rays", "closest_queries", "any_queries", "closest_nodes", "closest_prims", "any_nodes", "any_prims", "closest_launches", "root_culled", "sky_culled"]
     counted["closest_launches"] = timed["closest_launches"]
     counted["root_culled"] = timed["root_culled"]   # (the counting frame keeps every camera ray in the queue; the horizon cull - geometry, not a kernel's test - applies to it too)
-    cnt = torch.tensor([float(counted[k]) for k in keys] + [timed["ms_closest"], timed["ms_any"], timed["ms_shade"], timed["ms_raygen"], timed["ms_film"], timed["ms_total"], isolated["ms_closest"],
-                                                            single["ms_closest"], single["ms_any"], single["ms_shade"], single["ms_raygen"], single["ms_film"], single["ms_total"],
-                                                            timed["ms_gather"]],
-                       dtype=torch.float64, device=stat_dev)
+    names = keys + ["ms_closest", "ms_any", "ms_shade", "ms_raygen", "ms_film", "ms_total", "ms_gather"]
+    vals = [float(counted[k]) for k in keys] + [timed["ms_closest"], timed["ms_any"], timed["ms_shade"], timed["ms_raygen"], timed["ms_film"], timed["ms_total"], timed["ms_gather"]]
+    if args.full:
+        names += ["ms_closest_isolated", "ms1_closest", "ms1_any", "ms1_shade", "ms1_raygen", "ms1_film", "ms1_total"]
+        vals += [isolated["ms_closest"], single["ms_closest"], single["ms_any"], single["ms_shade"], single["ms_raygen"], single["ms_film"], single["ms_total"]]
+    cnt = torch.tensor(vals, dtype=torch.float64, device=stat_dev)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         mx, mn = cnt.clone(), cnt.clone()
@@ -300,8 +340,6 @@ def main():
     else:
         mx = mn = cnt
     elapsed = float(tt.item())
-    names = keys + ["ms_closest", "ms_any", "ms_shade", "ms_raygen", "ms_film", "ms_total", "ms_closest_isolated",
-                    "ms1_closest", "ms1_any", "ms1_shade", "ms1_raygen", "ms1_film", "ms1_total", "ms_gather"]
     tot = dict(zip(names, cnt.tolist()))
     mx_tot = dict(zip(names, mx.tolist()))
     mn_tot = dict(zip(names, mn.tolist()))
@@ -310,6 +348,8 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         queries = tot["closest_queries"] + tot["any_queries"]
         value = queries / (ms_per_step * 1e-3) / 1e6
+    roofline = cpu = None
+    if rank == 0 and args.full:
         # Roofline of the dominant kernel: closest-hit BVH traversal. ALGORITHMIC bytes per closest query: 28 B ray in +
         # 16 B hit out + 32 B per BVH node visited + 48 B per triangle tested; node / triangle counts are exact device counters of a
         # counting frame of this very workload; duration = the kernel's launches, HIP events on the stream they were launched on, in the
@@ -411,9 +451,9 @@ def main():
                     "l1_gather": None if tcp_acc is None else l1_gather_bound(tcp_acc / n_launch, None if tcp_insts is None else tcp_insts / n_launch, launch_s, alone_s),
                     "nodes_per_query": round(tot["closest_nodes"] / max(1.0, tot["closest_queries"]), 2),
                     "tris_per_query": round(tot["closest_prims"] / max(1.0, tot["closest_queries"]), 2)}
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(scene, args.cpu_seconds)
+    if rank == 0:
         out = {
             "metric": "Mrays/s (BVH ray queries, closest+any) @ 100k-tri heightfield %d^2 %dspp depth %d%s" % (args.res, args.spp, args.depth, "" if args.config == "cfg4" else " + microfacet BSDFs + area lights (BASELINE cfg5)"),
             "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -423,13 +463,14 @@ def main():
                 args.config, scene.desc.n_prims, "" if args.config == "cfg4" else " (Plastic + Metal, Trowbridge-Reitz), 4 diffuse sphere area lights", W, H, args.spp, args.depth, "reference-exact (Q26/Q27)" if args.compat_bvh else "fixed-bvh", nfl),
                 "collective": collective, "comm_world": (comm.world if comm is not None else world),
                 "triangles": int(scene.desc.n_prims), "bvh_nodes": int(scene.desc.n_bvh_nodes), "bvh_depth": int(scene.desc.bvh_depth)},
-            "roofline": roofline, "cpu_baseline": cpu,
+            **({"roofline": roofline, "cpu_baseline": cpu} if args.full else {}),
             "camera_mrays_per_s": round(tot["camera_rays"] / (ms_per_step * 1e-3) / 1e6, 3),
             "camera_samples": int(tot["camera_samples"]), "camera_rays": int(tot["camera_rays"]),
             "closest_queries": int(tot["closest_queries"]), "root_culled": int(tot["root_culled"]), "sky_culled": int(tot["sky_culled"]), "any_queries": int(tot["any_queries"]),
             "any_nodes_per_query": round(tot["any_nodes"] / max(1.0, tot["any_queries"]), 2), "any_tris_per_query": round(tot["any_prims"] / max(1.0, tot["any_queries"]), 2),
             "kernel_ms_per_frame": {k: round(mx_tot[k], 3) for k in ("ms_raygen", "ms_closest", "ms_any", "ms_shade", "ms_film", "ms_total")},
-            "kernel_ms_per_frame_one_at_a_time": {k.replace("ms1_", "ms_"): round(mx_tot[k], 3) for k in ("ms1_raygen", "ms1_closest", "ms1_any", "ms1_shade", "ms1_film", "ms1_total")},
+            **({"kernel_ms_per_frame_one_at_a_time": {k.replace("ms1_", "ms_"): round(mx_tot[k], 3) for k in ("ms1_raygen", "ms1_closest", "ms1_any", "ms1_shade", "ms1_film", "ms1_total")}}
+               if args.full else {}),
             # per rank, per frame of the timed region (HIP events on each rank's own stream): the render (ms_total: camera kernel to film kernel) and the frame's
             # collective (ms_gather: around the grouped ncclSend / ncclRecv or the ncclReduce of rrt_film_gather) - max and min over the ranks, so that a scaling
             # run can tell render imbalance between the ranks (max - min of ms_total) from the time the collective takes (0 with one rank / the gloo rehearsal)

@@ -2,10 +2,11 @@
 # per-bounce kernel durations of one bench frame (rocprofv3 kernel trace)
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/fp_$tag -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "$@" > gpurun_out/fp_$tag.log 2>&1
-grep '^{' gpurun_out/fp_$tag.log | tail -1 | python3 -c "
+res=${RRT_RESULTS_DIR:-results}; mkdir -p $res
+rocprofv3 --kernel-trace --stats --output-format csv -d $res/fp_$tag -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "$@" > $res/fp_$tag.log 2>&1
+grep '^{' $res/fp_$tag.log | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('value',d['value'],'ms',d['ms_per_step'],'roof',d['roofline']['achieved'],d['roofline']['frac'],d['kernel_ms_per_frame'])"
-t=$(find gpurun_out/fp_$tag -name "*kernel_trace.csv" | head -1)
+t=$(find $res/fp_$tag -name "*kernel_trace.csv" | head -1)
 python3 - "$t" <<'PY'
 import csv,sys,collections
 rows=list(csv.DictReader(open(sys.argv[1])))

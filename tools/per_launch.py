@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-dispatch durations of one frame from a rocprofv3 --kernel-trace CSV (bench.py --frames-in-flight 1): the launches of the LAST whole frame, in start order.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/pl -- python3 bench.py --no-cpu-baseline --frames-in-flight 1 --steps 3 --warmup 1
-    python tools/per_launch.py gpurun_out/pl
+    rocprofv3 --kernel-trace --output-format csv -d results/pl -- python3 bench.py --full --no-cpu-baseline --frames-in-flight 1 --steps 3 --warmup 1
+    python tools/per_launch.py results/pl
 """
 import csv
 import glob

@@ -8,7 +8,7 @@ for set in "SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_SALU SQ_BUSY_CU_CYCLES SQ_IFETCH SQ_LDS_CMD_FIFO_FULL" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD SQ_LDS_DATA_FIFO_FULL SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $out/pass$i -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 --frames-in-flight 1 $BENCH_OPTS > $out.pass$i.log 2>&1 || { tail -5 $out.pass$i.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $out/pass$i -- python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --frames-in-flight 1 $BENCH_OPTS > $out.pass$i.log 2>&1 || { tail -5 $out.pass$i.log; exit 1; }
 done
 python3 - $out <<'PY' > gpurun_out/pu_$1.txt
 import collections, csv, glob, re, sys

@@ -13,7 +13,7 @@ for spec in "$@"; do   # <variant|default>[:opt=value,...]
              "SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_BRANCH" \
              "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum"; do
     i=$((i+1))
-    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $out/pass$i -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 --frames-in-flight 1 $BENCH_OPTS $opts > $out.pass$i.log 2>&1 || { tail -5 $out.pass$i.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $out/pass$i -- python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --frames-in-flight 1 $BENCH_OPTS $opts > $out.pass$i.log 2>&1 || { tail -5 $out.pass$i.log; exit 1; }
   done
   python3 tools/pmc_kernels.py $out > gpurun_out/pv_$v.txt
   python3 - $out <<'PY' >> gpurun_out/pv_$v.txt
