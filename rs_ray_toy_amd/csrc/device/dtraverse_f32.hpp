@@ -25,6 +25,7 @@
 // are persistent, so the treelet is loaded once per workgroup.
 #pragma once
 #include "dkernels.hpp"
+#include "lens_cull.hpp"   // kLcR / kLcX / kLcY / kLcWords: the cull table's layout, shared with the host builder
 
 // refill thresholds of the persistent-thread kernels: idle lanes of a wave before it fetches new work
 #ifndef RRT_VOTE_A
@@ -1303,8 +1304,10 @@ RRT_DEV bool camera_ray_meets_root(const SceneDev<float>& s, const V3<float>& wo
 
 // staging records live in the next-queue arrays, which are free until the first shading launch:
 //   nray_o[i] = {o.xyz (world), slot}, nray_d[i] = {d.xyz (world), weight}, npath[i] = {p_film.xy, p_lens.xy}, hindex[i] = Halton index
+// lens_cull (optional): the lens cull table of host/lens_cull.cpp, [box][r cell][y cell][x word] bits, set = no sample of the cell gets through
 static __global__ void __launch_bounds__(kRgDense) k_raygen_main_f32(SceneDev<float> s, Pools<float> p, PassDesc pd, int write_samp, double* dims_out,
-                                                                     const float2* safe_lim, float aux_delta, float aux_pupil, int enqueue, uint32_t spb, uint2* chunks) {
+                                                                     const float2* safe_lim, float aux_delta, float aux_pupil, int enqueue, uint32_t spb, uint2* chunks,
+                                                                     const uint32_t* lens_cull, float lc_inv_dr) {
   __shared__ RgLensLds lens;
   __shared__ float2 safe_s[32];
   __shared__ uint32_t push_lds[kRgDense / 64 + 2];
@@ -1345,10 +1348,22 @@ static __global__ void __launch_bounds__(kRgDense) k_raygen_main_f32(SceneDev<fl
   const float r_film = __builtin_amdgcn_sqrtf(L.o.x * L.o.x + L.o.y * L.o.y);
   float m_scale = aux_delta * (1.0f + aux_pupil * __builtin_amdgcn_rcpf(r_film));
   bool safe = safe_lim != nullptr && r_film > 0.0f;
+  // Lens cull table: whether a sample gets through depends on (r_film, p_lens) only, and the cells of the table where no sample does were
+  // found on the host (lens_cull.cpp, with a margin of one cell for the fp32 arithmetic and the cell index). One 32-bit load per sample; a
+  // culled sample is dead as if its lens trace had stopped it (weight 0, nothing else written). A sample outside the table's domain is kept.
+  if (lens_cull && alive) {
+    const float cr = r_film * lc_inv_dr, cx = (lx - 0.5f) * (float)kLcX, cy = (ly - 0.5f) * (float)kLcY;
+    if (cr < (float)kLcR && cx >= 0.0f && cx < (float)kLcX && cy >= 0.0f && cy < (float)kLcY) {
+      const uint32_t box = (r_film / (s.diagonal / 2.0f) >= 1.0f) ? 1u : 0u;   // rg_begin_lean's choice of the exit-pupil box (Q6)
+      const uint32_t ix = (uint32_t)cx, row = (box * (uint32_t)kLcR + (uint32_t)cr) * (uint32_t)kLcY + (uint32_t)cy;
+      alive = ((lens_cull[row * (uint32_t)kLcWords + (ix >> 5)] >> (ix & 31u)) & 1u) == 0u;
+    }
+  }
   // The first interfaces stop most of the doomed samples (29 % at the second, 16 % at the third on the scene.json lens): after
   // kRgRepack of them the block's survivors are packed into its first threads through LDS, so that the remaining interfaces run in
-  // full waves and the emptied waves skip them.
-  const int k_pack = (kRgRepack > 0 && s.n_lens - 1 - kRgRepack >= 0) ? s.n_lens - 1 - kRgRepack : -1;   // first interface after the re-pack; block-uniform
+  // full waves and the emptied waves skip them. With the cull table the doomed samples are mostly gone already: the survivors are
+  // packed before the first interface, and all thirteen run on about a third of the waves.
+  const int k_pack = lens_cull ? s.n_lens - 1 : (kRgRepack > 0 && s.n_lens - 1 - kRgRepack >= 0) ? s.n_lens - 1 - kRgRepack : -1;   // first interface after the re-pack; block-uniform
   for (int k = s.n_lens - 1; k > k_pack; k--) {   // (no lane-divergent branch inside: dead lanes ride along)
     if (__ballot(alive) == 0ull) break;
     alive &= rg_step_lean(lens.a[k], lens.b[k], &L, safe_s[k], m_scale, &safe);

@@ -606,6 +606,7 @@ class Handle : public HandleBase {
     else if (key == "pt_split_any") pt_split_any_ = (uint32_t)v;
     else if (key == "overlap_shadow") overlap_shadow_ = v != 0;
     else if (key == "aux_margin") aux_margin_ = v != 0;
+    else if (key == "lens_cull") lens_cull_on_ = v != 0;   // 1 (default): the fp32 camera kernel drops the samples of dead lens cells before any lens arithmetic (host/lens_cull.cpp)
     else if (key == "shade_spec") shade_kinds_ = v != 0 ? shade_kinds_scene_ : kAllKinds;
     else if (key == "frame_stats") frame_stats_ = v != 0;
     else if (key == "halton_tables") scene_.n_hblk = (v != 0 && hblk_.n) ? (uint32_t)kHaltonTabDims : 0u;
@@ -1078,6 +1079,9 @@ class Handle : public HandleBase {
   DevBuf<float> lens_safe_;   // calibrate_aux_margins(): per interface, the squared radius inside which an auxiliary ray cannot be blocked (fp32 camera kernels)
   bool aux_margin_ = true;
   float aux_delta_ = 0.0f, aux_pupil_ = 0.0f;
+  DevBuf<uint32_t> lens_cull_;   // build_lens_cull(): the lens cull table of the fp32 camera kernel (empty: no table)
+  float lc_inv_dr_ = 0.0f;
+  bool lens_cull_on_ = true;    // option "lens_cull"
   DevBuf<R> filter_table_;
   DevBuf<HaltonDim> hdims_;
   static constexpr int kHaltonTabDims = 64;
@@ -1433,6 +1437,10 @@ class Handle : public HandleBase {
     materials_.upload(mats, st_); textures_.upload(texs, st_); images_.upload(imgs, st_); image_texels_.upload(texels, st_);
     { const AuxMargins am = calibrate_aux_margins(d); lens_safe_.upload(am.lim, st_); aux_delta_ = am.delta; aux_pupil_ = am.pupil; }
     if constexpr (std::is_same<R, float>::value) {
+      const LensCull lc = build_lens_cull(d);
+      if (!lc.bits.empty()) { lens_cull_.upload(lc.bits, st_); lc_inv_dr_ = lc.inv_dr; }
+    }
+    if constexpr (std::is_same<R, float>::value) {
       // shadow candidate lists (dtraverse_f32.hpp): scenes whose lights are all point / distant lights, triangles in world space only
       shadow_lists_ok_ = false;
       if (pairs_ok_ && !mixed_ && d->n_lights > 0 && d->bvh_depth + 1 <= 64) {
@@ -1708,6 +1716,8 @@ class Handle : public HandleBase {
         // (dead samples: weight 0, Q2 - written by k_raygen_main_f32 itself, one coalesced store per sample)
         {   // dense two-stage version with the lean lens arithmetic
           const float2* safe_r2 = (aux_margin_ && tex_depth_ == 0) ? reinterpret_cast<const float2*>(lens_safe_.p) : nullptr;   // textured scenes keep the auxiliary rays themselves (ray differentials)
+          // lens cull table (option lens_cull): tiled passes of untextured scenes
+          const uint32_t* cull = (lens_cull_on_ && lens_cull_.n != 0 && tex_depth_ == 0 && pd.tiled) ? lens_cull_.p : nullptr;
           // pixel blocks over grid y and z (a grid dimension holds at most 65 535 blocks; a pass has up to 2^28 / 512 of them)
           // samples / pixels per workgroup: 8 samples of one 8 x 8-pixel tile (PassDesc::tiled) where the pass has that many, else one sample of 512 pixels
           const uint32_t spb = (pd.tiled && pd.ns >= (uint32_t)rg_spb_) ? (uint32_t)std::max(1, std::min(rg_spb_, kRgDense / 64)) : 1u, ppb = kRgDense / spb;
@@ -1721,7 +1731,7 @@ class Handle : public HandleBase {
             tt_pass_ok_ = true;
           }
           hipLaunchKernelGGL(k_raygen_main_f32, dim3((pd.ns + spb - 1) / spb, gy, gz), dim3(kRgDense), 0, st_, scene_, pool_, pd, write_samp, dims_out, safe_r2, aux_delta_, aux_pupil_, enqueue, spb,
-                             tt_pass_ok_ ? tt_chunks_.p : nullptr);
+                             tt_pass_ok_ ? tt_chunks_.p : nullptr, cull, lc_inv_dr_);
           if (tt_pass_ok_) hipLaunchKernelGGL(k_tt_snapshot, dim3(1), dim3(1), 0, st_, counters_.p);
           hipLaunchKernelGGL(k_raygen_aux2_f32, dim3((total + kRgDense - 1) / kRgDense), dim3(kRgDense), 0, st_, scene_, pool_, enqueue);
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 4);   // q_next was only a staging queue
