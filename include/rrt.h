@@ -450,6 +450,9 @@ int rrt_film_gather_all(rrt_handle* const* handles, void* const* films_device, i
  *                                 before shading them (a miss is shaded with nothing)
  * shade_spec            1  fp32   path shading kernel instantiated for the lobe kinds the scene's materials      same arithmetic per lobe: frames equal to fp32 rounding,
  *                                 can produce; 0: always the general kernel                                      weights and counts identical (test_shading_kernel_specialisation)
+ * film_records          1  fp32   path integrator, tile-tree passes, box filter of radius 0.5, untextured:       invariant (tests/test_film_records.py);
+ *                                 radiance in per-workgroup record runs read by a run-walking box film;          other passes keep the per-slot layout
+ *                                 0: the per-slot layout and k_film_box
  */
 int rrt_set_option(rrt_handle*, const char* key, double value);
 

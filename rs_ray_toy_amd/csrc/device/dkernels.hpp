@@ -17,7 +17,9 @@ enum { C_ACTIVE = 0, C_NEXT = 32, C_SHADOW = 64, C_CAMERA_RAYS = 96, C_ERROR = 1
        // camera rays answered by the camera kernels (SceneDev::root_cull): closest-hit queries that never entered a queue
        C_CULLED = 832,
        // bounce rays the path shading kernel proves to leave the scene (SceneDev::horizon): closest-hit queries that never entered a queue
-       C_SKY = 864, C_COUNT = 896 };
+       C_SKY = 864,
+       // film records of the pass (k_raygen_main_f32 with film runs: one run per camera workgroup, allocated from this counter)
+       C_RECORDS = 896, C_COUNT = 928 };
 // shading kernels push to their queues once per block (measured: 256 <= 512 <= 1024 threads by 5 %: smaller blocks retire
 // and refill a CU sooner, and one atomic per 256 paths no longer serialises)
 template <typename R> struct ShadeBlock { static constexpr int n = 256; };
@@ -1440,7 +1442,7 @@ static __global__ void k_rotate(uint32_t* c, int what) {
   else if (what == 5) { c[C_ACTIVE] = c[C_NEXT]; c[C_NEXT] = 0; c[C_WORK_CLOSEST] = 0; c[C_WORK_AUX] = 0; for (int k = 0; k < 8; k++) c[C_WORK8_CLOSEST + 32 * k] = 0; return; }
   else if (what == 6) { c[C_SHADOW] = 0; c[C_WORK_SHADOW] = 0; for (int k = 0; k < 8; k++) c[C_WORK8_SHADOW + 32 * k] = 0; return; }
   else if (what == 7) { c[C_SHADOW2] = 0; c[C_WORK_SHADOW] = 0; for (int k = 0; k < 8; k++) c[C_WORK8_SHADOW + 32 * k] = 0; return; }
-  else { c[C_ACTIVE] = 0; c[C_NEXT] = 0; c[C_SHADOW] = 0; }
+  else { c[C_ACTIVE] = 0; c[C_NEXT] = 0; c[C_SHADOW] = 0; c[C_RECORDS] = 0; }
   c[C_WORK_CLOSEST] = 0; c[C_WORK_SHADOW] = 0; c[C_WORK_AUX] = 0;
   for (int k = 0; k < 8; k++) { c[C_WORK8_CLOSEST + 32 * k] = 0; c[C_WORK8_SHADOW + 32 * k] = 0; }
 }
@@ -1461,6 +1463,21 @@ static __global__ void k_accumulate_camera(uint32_t* c, unsigned long long* tota
 // <= 0.5: every sample lands in its own pixel, so one thread owns a pixel and sums the pass's samples in sample
 // order (deterministic, no atomics). film = per pixel {X, Y, Z sums, filter_weight_sum}.
 // ------------------------------------------------------------------------------------------------------------
+// One sample of the box filter: `w` = its weight, `l` = its radiance record (only read for w > 0). k_film_box and k_film_box_runs
+// both add through this function, so their sums are the same expressions, contracted the same way.
+template <typename R>
+RRT_DEV void film_box_add(const SceneDev<R>& s, R& cr, R& cg, R& cb, R& wsum, R w, const typename Vec4T<R>::type& l) {
+  Rgb<R> L;
+  if (w > R(0)) L = Rgb<R>(l.x, l.y, l.z);   // dead samples: L = 0, w = 0 (Q2); their record is never initialised
+  // integrator/mod.rs:105-122
+  if (L.has_nan()) L = Rgb<R>();
+  else if (L.y() < R(-1e-5)) L = Rgb<R>();
+  else if (isinf(L.y())) L = Rgb<R>();
+  if (L.y() > s.max_sample_luminance) L = L * (s.max_sample_luminance / L.y());
+  cr += (L.r * w) * R(1); cg += (L.g * w) * R(1); cb += (L.b * w) * R(1);  // box filter table weight 1
+  wsum += R(1);
+}
+
 template <typename R>
 __global__ void __launch_bounds__(kBlock) k_film_box(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film) {
   const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1475,17 +1492,7 @@ __global__ void __launch_bounds__(kBlock) k_film_box(SceneDev<R> s, Pools<R> p, 
   R* px = film + 4 * (size_t)pix;
   R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];
   constexpr uint32_t kBatch = 8;   // independent loads in flight per thread: a band of a frame has too few pixels to hide the latency otherwise
-  auto add = [&](R w, const typename Vec4T<R>::type& l) {
-    Rgb<R> L;
-    if (w > R(0)) L = Rgb<R>(l.x, l.y, l.z);   // dead samples: L = 0, w = 0 (Q2); their record is never initialised
-    // integrator/mod.rs:105-122
-    if (L.has_nan()) L = Rgb<R>();
-    else if (L.y() < R(-1e-5)) L = Rgb<R>();
-    else if (isinf(L.y())) L = Rgb<R>();
-    if (L.y() > s.max_sample_luminance) L = L * (s.max_sample_luminance / L.y());
-    cr += (L.r * w) * R(1); cg += (L.g * w) * R(1); cb += (L.b * w) * R(1);  // box filter table weight 1
-    wsum += R(1);
-  };
+  auto add = [&](R w, const typename Vec4T<R>::type& l) { film_box_add(s, cr, cg, cb, wsum, w, l); };
   uint32_t sl = 0;
   // few pixels (a band of a frame): latency-bound, batch the loads; many pixels: bandwidth-bound, and seven samples in ten are
   // dead on the 100k-triangle config, so their L records are better left unread

@@ -161,6 +161,42 @@ RRT_DEV uint32_t block_push_range(uint32_t* counter, bool pred, uint32_t* lds, u
   return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// block_push_range() onto several queues at once: two barriers and one atomic per queue (lanes 0 .. kN-1 of wave 0, side by side) in place of
+// three barriers and an atomic per queue in turn. Queue i is counters[kOff[i]]; bit i of `pred` is this thread's predicate for it, bit i of `on`
+// whether the queue is in use (block-uniform; a queue not in use, or with no thread's bit set, gets no atomic).
+// `lds` = kN x (waves per block + 2) words. Must be reached by every thread of the block.
+template <uint32_t... kOff>
+RRT_DEV void block_push_multi(uint32_t* counters, uint32_t on, uint32_t pred, uint32_t* lds, uint32_t* at, uint32_t* first, uint32_t* total) {
+  constexpr uint32_t kN = sizeof...(kOff);
+  constexpr uint32_t off[kN] = {kOff...};
+  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6, nw = (blockDim.x + 63u) >> 6, stride = nw + 2u;
+  uint64_t mask[kN];
+#pragma unroll
+  for (uint32_t i = 0; i < kN; i++) {
+    mask[i] = __ballot((pred >> i) & 1u);
+    if (lane == 0) lds[i * stride + w] = (uint32_t)__popcll(mask[i]);
+  }
+  __syncthreads();
+  if (threadIdx.x < kN) {
+    uint32_t o = off[0];
+#pragma unroll
+    for (uint32_t i = 1; i < kN; i++) if (threadIdx.x == i) o = off[i];
+    uint32_t* l = lds + threadIdx.x * stride;
+    uint32_t tot = 0;
+    for (uint32_t k = 0; k < nw; k++) { const uint32_t n = l[k]; l[k] = tot; tot += n; }
+    l[nw] = (tot && ((on >> threadIdx.x) & 1u)) ? atomicAdd(counters + o, tot) : 0u;
+    l[nw + 1] = tot;
+  }
+  __syncthreads();
+  const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (uint32_t i = 0; i < kN; i++) {
+    first[i] = lds[i * stride + nw]; total[i] = lds[i * stride + nw + 1];
+    at[i] = first[i] + lds[i * stride + w] + (uint32_t)__popcll(mask[i] & below);
+  }
+  __syncthreads();   // lds is reused by the next push
+}
+
 // Rank of this thread among the block's threads with `pred` (block order) and their number: block_push() without the queue.
 // `lds` = (waves per block + 1) words. Must be reached by every thread of the block.
 RRT_DEV uint32_t block_rank(bool pred, uint32_t* lds, uint32_t* total) {

@@ -1305,12 +1305,16 @@ RRT_DEV bool camera_ray_meets_root(const SceneDev<float>& s, const V3<float>& wo
 // staging records live in the next-queue arrays, which are free until the first shading launch:
 //   nray_o[i] = {o.xyz (world), slot}, nray_d[i] = {d.xyz (world), weight}, npath[i] = {p_film.xy, p_lens.xy}, hindex[i] = Halton index
 // lens_cull (optional): the lens cull table of host/lens_cull.cpp, [box][r cell][y cell][x word] bits, set = no sample of the cell gets through
+// runs (optional, with `chunks`): film records instead of the per-slot state (option film_records, see k_film_box_runs). A sample that survives
+//   the lens and is queued or staged gets a record in its workgroup's run, in thread order: L[r] = {L.rgb = 0, weight} and weight[r] = its code
+//   (sample in group x 64 + pixel in tile, as bits); runs[chunk] = {first record, records}. The queues carry r where they carry the slot
+//   otherwise, so the shadow kernels add to the record. Nothing is written per slot.
 static __global__ void __launch_bounds__(kRgDense) k_raygen_main_f32(SceneDev<float> s, Pools<float> p, PassDesc pd, int write_samp, double* dims_out,
                                                                      const float2* safe_lim, float aux_delta, float aux_pupil, int enqueue, uint32_t spb, uint2* chunks,
-                                                                     const uint32_t* lens_cull, float lc_inv_dr) {
+                                                                     const uint32_t* lens_cull, float lc_inv_dr, uint2* runs) {
   __shared__ RgLensLds lens;
   __shared__ float2 safe_s[32];
-  __shared__ uint32_t push_lds[kRgDense / 64 + 2];
+  __shared__ uint32_t push_lds[5 * (kRgDense / 64 + 2)];
   const uint32_t tid = threadIdx.x;
   rg_lens_to_lds(s, &lens, tid);
   if (tid < (uint32_t)s.n_lens) safe_s[tid] = safe_lim ? safe_lim[tid] : make_float2(0.0f, 0.0f);   // 16 c_i = 0: never safe
@@ -1330,8 +1334,8 @@ static __global__ void __launch_bounds__(kRgDense) k_raygen_main_f32(SceneDev<fl
     slot = sl * pd.npix + pl;
     // dead samples: weight 0 (Q2), nothing else is written for them. Every sample's first owner writes it here (coalesced, one store instead of a 1 GB
     // memset per frame in front of the kernel); a survivor's weight is stored at the end of this kernel - behind the block's barriers, by whichever thread of
-    // the block holds the sample after the re-pack - or by stage B.
-    p.weight[slot] = 0.0f;
+    // the block holds the sample after the re-pack - or by stage B. (Film runs: a dead sample has no record, and nothing is stored.)
+    if (!runs) p.weight[slot] = 0.0f;
     const uint2 po = reinterpret_cast<const uint2*>(p.pix_off)[pl];
     const uint32_t px = po.y & 0xffffu, py = po.y >> 16;
     index = po.x + (pd.s_begin + sl) * s.stride;
@@ -1344,6 +1348,8 @@ static __global__ void __launch_bounds__(kRgDense) k_raygen_main_f32(SceneDev<fl
     w = rg_begin_lean(s, pfx, pfy, lx, ly, &L);
     alive = w != 0.0f;
   }
+  // film runs: from here on a sample is known by its thread of the workgroup (its record's code), which the re-pack carries in place of the slot
+  if (runs) slot = tid;
   // the sample's displacement scale m = delta (1 + P / r_film) (calibrate_aux_margins()); the film point is the lens-space origin
   const float r_film = __builtin_amdgcn_sqrtf(L.o.x * L.o.x + L.o.y * L.o.y);
   float m_scale = aux_delta * (1.0f + aux_pupil * __builtin_amdgcn_rcpf(r_film));
@@ -1406,28 +1412,39 @@ static __global__ void __launch_bounds__(kRgDense) k_raygen_main_f32(SceneDev<fl
     wd = wdu * __builtin_amdgcn_rsqf(len2(wdu));
     if (s.root_cull && done) meets = camera_ray_meets_root(s, wo, wd);
   }
-  uint32_t qa_first, qa_total;
-  const uint32_t qa = block_push_range(&p.counters[C_ACTIVE], done && enqueue && meets, push_lds, &qa_first, &qa_total);
-  if (s.root_cull) (void)block_push(&p.counters[C_CULLED], done && enqueue && !meets, push_lds);   // block-uniform condition
+  // Film runs: a root-culled sample gets no record - the film adds it as (0, 0), i.e. +0, where the per-slot film adds (0 x w) = +0 for its
+  // L = 0; only a weight that is not finite makes that product a NaN, and such a sample keeps a record.
+  const bool rec = staged || (done && (meets || !(fabsf(w) < Const<float>::inf)));
+  // the block's pushes in one go: first queue, root-culled rays, staging queue, camera rays, film records
+  const uint32_t on = 0xdu | (s.root_cull ? 0x2u : 0u) | (runs ? 0x10u : 0u);   // queues in use (bit i = queue i below)
+  const uint32_t pred = (done && enqueue && meets ? 1u : 0u) | (done && enqueue && !meets ? 2u : 0u) | (staged ? 4u : 0u) | (done ? 8u : 0u) | (rec ? 16u : 0u);
+  uint32_t at[5], first[5], total[5];
+  block_push_multi<C_ACTIVE, C_CULLED, C_NEXT, C_CAMERA_RAYS, C_RECORDS>(p.counters, on, pred, push_lds, at, first, total);
+  const uint32_t qa = at[0], qs = at[2];
+  const size_t chunk = (size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
   // chunk record of this workgroup (k_trace_tiles_f32): its entries of the first queue are one contiguous run, all from one tile of the image
-  if (chunks && tid == 0) chunks[(size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = make_uint2(qa_first, qa_total);
-  const uint32_t qs = block_push(&p.counters[C_NEXT], staged, push_lds);
-  (void)block_push(&p.counters[C_CAMERA_RAYS], done, push_lds);
+  if (chunks && tid == 0) chunks[chunk] = make_uint2(first[0], total[0]);
+  uint32_t ref = slot;   // what the queues carry: the slot, or the record
+  if (runs) {   // (block-uniform)
+    ref = at[4];
+    if (tid == 0) runs[chunk] = make_uint2(first[4], total[4]);
+    if (rec) reinterpret_cast<uint32_t*>(p.weight)[ref] = slot;   // the record's code
+  }
   if (alive) {
     if (staged) {
-      p.nray_o[qs] = make_float4(wo.x, wo.y, wo.z, __uint_as_float(slot));
+      p.nray_o[qs] = make_float4(wo.x, wo.y, wo.z, __uint_as_float(ref));
       p.nray_d[qs] = make_float4(wd.x, wd.y, wd.z, w);
       p.npath[qs] = make_float4(pfx, pfy, lx, ly);
       p.hindex[qs] = index;
     } else {
       if (enqueue && meets) {
-        p.q_active[qa] = QEnt{slot, 5u, index, 0u};          // five camera dimensions consumed, bounce 0
+        p.q_active[qa] = QEnt{ref, 5u, index, 0u};          // five camera dimensions consumed, bounce 0
         if (s.integrator != 0 /* RRT_INT_PATH */) p.path[qa] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);    // beta, eta_scale (k_shade_path knows a camera ray's without reading it)
         p.ray_o[qa] = make_float4(wo.x, wo.y, wo.z, Const<float>::inf);
         p.ray_d[qa] = make_float4(wd.x, wd.y, wd.z, __uint_as_float(0xffffffffu));
       }
-      p.L[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      p.weight[slot] = w;
+      if (!runs) { p.L[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); p.weight[slot] = w; }
+      else if (rec) p.L[ref] = make_float4(0.0f, 0.0f, 0.0f, w);
     }
   }
 }
@@ -1446,7 +1463,8 @@ RRT_DEV bool rg_trace_lean(const SceneDev<float>& s, const RgLensLds& lens, floa
   return ok;
 }
 
-static __global__ void __launch_bounds__(kRgDense) k_raygen_aux2_f32(SceneDev<float> s, Pools<float> p, int enqueue) {
+// records: the staging records carry film records (k_raygen_main_f32 with runs), which are written {0, 0, 0, weight} for a kept sample, zero for a dropped one
+static __global__ void __launch_bounds__(kRgDense) k_raygen_aux2_f32(SceneDev<float> s, Pools<float> p, int enqueue, int records) {
   __shared__ RgLensLds lens;
   __shared__ uint32_t push_lds[kRgDense / 64 + 1];
   const uint32_t tid = threadIdx.x;
@@ -1503,7 +1521,87 @@ static __global__ void __launch_bounds__(kRgDense) k_raygen_aux2_f32(SceneDev<fl
     p.ray_o[q] = make_float4(ro.x, ro.y, ro.z, Const<float>::inf);
     p.ray_d[q] = make_float4(rd.x, rd.y, rd.z, __uint_as_float(0xffffffffu));
   }
-  if (alive) { p.L[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); p.weight[slot] = rd.w; }
+  if (records) { if (i < n) p.L[slot] = make_float4(0.0f, 0.0f, 0.0f, alive ? rd.w : 0.0f); }
+  else if (alive) { p.L[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); p.weight[slot] = rd.w; }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Box film from the record runs (option film_records): the fp32 path integrator's tile-tree passes (8 x 8 tile x 8 samples per camera
+// workgroup) with the box filter of radius 0.5 on untextured scenes. k_film_box reads a 4-byte weight for every slot of the pass and the
+// 16-byte L of every survivor, scattered at a third of the slots' density; here one wave owns one 8 x 8 tile and walks its ns / 8 runs in
+// sample-group order, each run the dense 20-byte records of one camera workgroup. A run is scattered by its codes into an LDS table
+// [8 samples][64 pixels] whose entries are {0, 0, 0, 0} ("absent") otherwise, and each pixel's lane then adds its 8 entries in sample
+// order through film_box_add(), k_film_box's own function.
+// Bit identity with k_film_box, pixel by pixel, sample by sample:
+//   - a queued or staged sample that stage B keeps has the record {L, w} where the per-slot state holds weight w and L: add(w, L) both;
+//   - a sample without a record (dead in the lens, or root-culled) is added as add(0, 0), i.e. +0 to the colour sums. k_film_box adds a dead
+//     sample as add(0, .) = +0 and a root-culled one as add(w, L = 0) = (0 w) 1 = +0 (for a finite w; a root-culled sample whose weight is
+//     not finite keeps a record, see k_raygen_main_f32);
+//   - a sample that stage B drops has the record {0, 0, 0, 0}: add(0, 0), where k_film_box adds add(0, .) for its weight 0;
+//   - wsum gets one +1 per sample either way.
+// So every pixel makes the sequence of film_box_add() calls that k_film_box makes, and its sums are equal bit for bit.
+// ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kFrTiles = 4;   // tiles (waves) per workgroup of k_film_box_runs
+typedef float v4f __attribute__((ext_vector_type(4)));   // (arrays of float4 = HIP_vector_type end up in scratch here; of this, in registers)
+static __global__ void __launch_bounds__(64 * kFrTiles) k_film_box_runs(SceneDev<float> s, Pools<float> p, PassDesc pd, float* film, const uint2* runs, uint32_t n_groups) {
+  __shared__ v4f tab[kFrTiles][8][64];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t tile = blockIdx.x * kFrTiles + wv;
+  const bool live = tile < pd.npix / 64u;   // (every wave reaches the barriers)
+  const uint32_t* code = reinterpret_cast<const uint32_t*>(p.weight);
+  float cr = 0.0f, cg = 0.0f, cb = 0.0f, wsum = 0.0f;
+  float* px = film;
+  if (live) {
+    uint32_t x, y;
+    pass_pixel(pd, pd.pix_begin + tile * 64u + lane, &x, &y);
+    px = film + 4 * ((size_t)y * (uint32_t)s.xres + x);
+    cr = px[0]; cg = px[1]; cb = px[2]; wsum = px[3];
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++) tab[wv][k][lane] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+  // a run holds at most 512 records: up to 8 per lane, their loads issued together; the next run's are in flight while this one is added
+  // (two register sets, chosen at compile time: the run loop is unrolled by two)
+  v4f rec[2][8];
+  uint32_t cd[2][8];
+  auto load = [&](auto B, uint32_t first, uint32_t cnt) {
+    constexpr uint32_t b = decltype(B)::value;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) {
+      const uint32_t j = lane + 64u * k;
+      if (j < cnt) { rec[b][k] = reinterpret_cast<const v4f*>(p.L)[first + j]; cd[b][k] = code[first + j]; }
+    }
+  };
+  using B0 = std::integral_constant<uint32_t, 0>;
+  using B1 = std::integral_constant<uint32_t, 1>;
+  for (uint32_t g0 = 0; g0 < n_groups; g0 += 64u) {
+    // the {first, records} of up to 64 runs, one per lane, handed out by shuffles
+    const uint2 rl = (live && g0 + lane < n_groups) ? runs[(size_t)tile * n_groups + g0 + lane] : make_uint2(0u, 0u);
+    const uint32_t ng = min(64u, n_groups - g0);
+    auto step = [&](auto B, uint32_t g) {   // run g of the batch, in register set B; prefetches run g + 1 into the other one
+      constexpr uint32_t b = decltype(B)::value;
+      const uint32_t cnt = __shfl(rl.y, (int)g);
+      if (g + 1 < ng) load(std::integral_constant<uint32_t, b ^ 1u>{}, __shfl(rl.x, (int)g + 1), __shfl(rl.y, (int)g + 1));
+      __syncthreads();   // the table is all "absent" again
+#pragma unroll
+      for (uint32_t k = 0; k < 8; k++) {
+        const uint32_t j = lane + 64u * k;
+        if (j < cnt) tab[wv][cd[b][k] >> 6][cd[b][k] & 63u] = rec[b][k];
+      }
+      __syncthreads();
+#pragma unroll
+      for (uint32_t k = 0; k < 8; k++) {
+        const v4f e = tab[wv][k][lane];
+        tab[wv][k][lane] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+        film_box_add(s, cr, cg, cb, wsum, e.w, make_float4(e.x, e.y, e.z, e.w));
+      }
+    };
+    load(B0{}, __shfl(rl.x, 0), __shfl(rl.y, 0));
+    for (uint32_t g = 0; g < ng; g += 2) {
+      step(B0{}, g);
+      if (g + 1 < ng) step(B1{}, g + 1);
+    }
+  }
+  if (live) { px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum; }
 }
 
 }  // namespace rrtd

@@ -607,6 +607,7 @@ class Handle : public HandleBase {
     else if (key == "overlap_shadow") overlap_shadow_ = v != 0;
     else if (key == "aux_margin") aux_margin_ = v != 0;
     else if (key == "lens_cull") lens_cull_on_ = v != 0;   // 1 (default): the fp32 camera kernel drops the samples of dead lens cells before any lens arithmetic (host/lens_cull.cpp)
+    else if (key == "film_records") film_records_on_ = v != 0;   // 1 (default): the path integrator's tile-tree passes keep radiance in per-workgroup record runs, added up by k_film_box_runs
     else if (key == "shade_spec") shade_kinds_ = v != 0 ? shade_kinds_scene_ : kAllKinds;
     else if (key == "frame_stats") frame_stats_ = v != 0;
     else if (key == "halton_tables") scene_.n_hblk = (v != 0 && hblk_.n) ? (uint32_t)kHaltonTabDims : 0u;
@@ -927,7 +928,11 @@ class Handle : public HandleBase {
           }
         }
         e = tick(4);
-        if (!wide_filter) hipLaunchKernelGGL((k_film_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
+        if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen)
+          if constexpr (std::is_same<R, float>::value)
+            hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_.p, film_runs_.p, (uint32_t)(ns / 8));
+        }
+        else if (!wide_filter) hipLaunchKernelGGL((k_film_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
         else {
           // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
           const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
@@ -1082,6 +1087,9 @@ class Handle : public HandleBase {
   DevBuf<uint32_t> lens_cull_;   // build_lens_cull(): the lens cull table of the fp32 camera kernel (empty: no table)
   float lc_inv_dr_ = 0.0f;
   bool lens_cull_on_ = true;    // option "lens_cull"
+  DevBuf<uint2> film_runs_;      // per camera workgroup of a pass with film records: {first record, records} (k_raygen_main_f32, k_film_box_runs)
+  bool film_records_on_ = true;  // option "film_records"
+  bool film_runs_ok_ = false;    // the pass the camera kernels last ran for writes film records
   DevBuf<R> filter_table_;
   DevBuf<HaltonDim> hdims_;
   static constexpr int kHaltonTabDims = 64;
@@ -1693,6 +1701,7 @@ class Handle : public HandleBase {
   // for_render: the queue feeds the integrator (camera rays that miss the root box may be answered here); otherwise every survivor's ray is wanted (rrt_camera_samples)
   void launch_raygen(const PassDesc& pd, uint32_t grid, double* dims_out, int enqueue, bool for_render = false) {
     tt_pass_ok_ = false;
+    film_runs_ok_ = false;
     scene_.root_cull = 0u;
     if constexpr (std::is_same<R, float>::value) {
       // a miss is shaded with nothing by the path integrator only (DirectLighting / Debug panic on a miss without lights, Q20), and the root test that
@@ -1729,11 +1738,18 @@ class Handle : public HandleBase {
             if (tt_chunks_.n < n_chunks) { HIP_CHECK(hipStreamSynchronize(st_)); tt_chunks_.alloc(n_chunks); }
             tt_pass_ = TileTrees{reinterpret_cast<const float4*>(tt_trees_.p), tt_tris_.p, tt_chunks_.p, (uint32_t)pd.rw / kTileW, pd.npix / (uint32_t)pd.rw / kTileH, pd.ns / spb, tt_mt_x_, tt_n_trees_, pd};
             tt_pass_ok_ = true;
+            // film records (option film_records): the path integrator's radiance in record runs, one per camera workgroup (k_film_box_runs). Only where every
+            // reader of the per-slot state is known: the box filter of radius 0.5 (write_samp = 0), untextured (no ray differentials per slot), the frame's
+            // own passes (not rrt_camera_samples, which reads weight[slot])
+            if (film_records_on_ && for_render && !dims_out && write_samp == 0 && tex_depth_ == 0 && desc_.integrator.type == RRT_INT_PATH) {
+              if (film_runs_.n < n_chunks) { HIP_CHECK(hipStreamSynchronize(st_)); film_runs_.alloc(n_chunks); }
+              film_runs_ok_ = true;
+            }
           }
           hipLaunchKernelGGL(k_raygen_main_f32, dim3((pd.ns + spb - 1) / spb, gy, gz), dim3(kRgDense), 0, st_, scene_, pool_, pd, write_samp, dims_out, safe_r2, aux_delta_, aux_pupil_, enqueue, spb,
-                             tt_pass_ok_ ? tt_chunks_.p : nullptr, cull, lc_inv_dr_);
+                             tt_pass_ok_ ? tt_chunks_.p : nullptr, cull, lc_inv_dr_, film_runs_ok_ ? film_runs_.p : nullptr);
           if (tt_pass_ok_) hipLaunchKernelGGL(k_tt_snapshot, dim3(1), dim3(1), 0, st_, counters_.p);
-          hipLaunchKernelGGL(k_raygen_aux2_f32, dim3((total + kRgDense - 1) / kRgDense), dim3(kRgDense), 0, st_, scene_, pool_, enqueue);
+          hipLaunchKernelGGL(k_raygen_aux2_f32, dim3((total + kRgDense - 1) / kRgDense), dim3(kRgDense), 0, st_, scene_, pool_, enqueue, film_runs_ok_ ? 1 : 0);
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 4);   // q_next was only a staging queue
         }
         HIP_CHECK(hipGetLastError());
