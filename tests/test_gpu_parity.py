@@ -736,7 +736,7 @@ def test_quad_nodes_change_nothing(which, workdir):
         assert np.array_equal(hits[1][k], hits[0][k]), k
 
 
-@pytest.mark.parametrize("which", ["cfg4", "rough_1", "rough_2", "rough_z_up", "cfg2", "cfg3", "cfg5", "stacked", "cfg4_passes", "boxes_1", "boxes_2"])
+@pytest.mark.parametrize("which", ["cfg4", "rough_1", "rough_2", "rough_z_up", "cfg2", "cfg3", "cfg5", "stacked", "cfg4_passes", "boxes_1", "boxes_2", "cfg4_compat_bvh"])
 def test_horizon_cull_changes_nothing(which, workdir, monkeypatch):
     """The path shading kernel answers a bounce ray as the miss it is when its elevation exceeds everything the host found visible from ANY point of its start
     triangle in its azimuth sector (rrt_impl.hpp build_horizons(): per triangle 2 x 16 quantised horizons about the scene's flattest axis; touching neighbours bounded
@@ -744,10 +744,12 @@ def test_horizon_cull_changes_nothing(which, workdir, monkeypatch):
     its own leaf. Frames, weights and query counts (the culled rays stay closest-hit queries, rrt_render_stats::sky_culled) are identical bit for bit with and without:
     the gentle BASELINE terrain, steep noisy ones (valleys whose walls start on a triangle's own edge; also with z as the flat axis), the reference's tilted cubes and
     an enclosure whose light sits inside (nothing may be culled towards a wall), config 5's two meshes, a second terrain stacked above the first (overhangs), several
-    pool passes. RRT_HZ_CHECK makes the builder test 20 000 random rays it declares free against every triangle in double precision."""
+    pool passes, the reference-exact BVH (flags = 0: overlapping children, Q26 / Q27). RRT_HZ_CHECK makes the builder test 20 000 random rays it declares free against every triangle in double precision."""
     monkeypatch.setenv("RRT_HZ_CHECK", "20000")
     flags = RRT_FIXED_BVH
-    if which in ("cfg4", "cfg4_passes"): cfg, root = scenes.cfg4(workdir, xres=128, yres=96, nsamp=9, max_depth=6, n=64)
+    if which in ("cfg4", "cfg4_passes", "cfg4_compat_bvh"):
+        cfg, root = scenes.cfg4(workdir, xres=128, yres=96, nsamp=9, max_depth=6, n=64)
+        if which == "cfg4_compat_bvh": flags = 0
     elif which.startswith("rough"):
         cfg, root = rough_terrain(workdir, {"rough_1": 1, "rough_2": 2, "rough_z_up": 3}[which])
         if which == "rough_z_up":      # the same terrain stood on its side (a rigid instance, flattened to world space): z becomes the scene's flattest axis
@@ -774,6 +776,7 @@ def test_horizon_cull_changes_nothing(which, workdir, monkeypatch):
     assert out[0][1].sky_culled == 0
     print(f"horizon cull, {which}: {out[1][1].sky_culled} of {out[1][1].closest_queries} closest-hit queries answered by the tables")
     if which in ("cfg4", "cfg5", "cfg4_passes"): assert out[1][1].sky_culled > 0.05 * out[1][1].closest_queries     # (the steep terrains have high horizons: little to cull, and that little exactly)
+    if which == "cfg4_compat_bvh": assert out[1][1].sky_culled > 0      # the cull is active on the reference-exact tree too
     if which == "cfg3": assert out[1][1].sky_culled == 0      # an enclosure: something is visible in every direction
 
 
