@@ -381,6 +381,35 @@ int rrt_render_end(rrt_handle*);
  * flight when the option "frame_stats" is 1 */
 int rrt_render_end_stats(rrt_handle*, rrt_render_stats* stats);
 
+/* First-hit feature buffers (no counterpart in the reference): what a denoiser or compositor wants beside the film - albedo, normal and
+ * depth of the camera rays' first hits, filtered by the film's own pixel filter. The pass runs over exactly the camera samples
+ * rrt_render_rect takes for the rect's pixels (same sampler, sample_num 1..nsamp-1, same p_film); rank / world = 0 / 1 takes the whole
+ * rect, otherwise the rect's interleaved 16-row bands b % world == rank as rrt_render_bands partitions them; max_samples = 0 takes all
+ * samples, k takes sample_num 1..min(k, nsamp-1). Each plane is a full-frame W*H*4 buffer of the handle's precision, added to (+=) like
+ * the film, so rects and bands sum to the whole; a wide filter's splats across a rect / band border land in this call's planes.
+ *   live sample: camera weight > 0. Dead samples add nothing (unlike the film's filter_weight_sum, which counts them), and no weight
+ *                is tripled on the way out.
+ *   fw:          the film's filter weight of the sample at the pixel (box filter of radius 0.5: 1 in the sample's own pixel; every
+ *                other filter: FilmTile::add_sample's footprint test and 16 x 16 table, film.rs:77-130).
+ *   t:           what rrt_trace_closest reports for the camera ray.
+ *   n:           the interaction's geometric normal as the reference holds it after Triangle / Sphere::intersect and the instance
+ *                transform (primitives.rs:131-136), normalised (a non-rigid instance leaves it un-normalised); not turned towards the
+ *                camera, and taken before any bump_map.
+ *   rho:         first-hit reflectance from the material's own parameters, textured ones evaluated at the hit with ZERO differentials
+ *                (the pixel's samples do the anti-aliasing), clamped to >= 0 where the material clamps: Matte / Plastic / Translucent
+ *                Kd, Mirror Kr, Glass (1, 1, 1), Metal ((eta - 1)^2 + k^2) / ((eta + 1)^2 + k^2) per channel, Debug (0, 1, 1).
+ * A live sample that misses the scene adds only fw to albedo[3]. The handle is left as it was (a frame rendered before and after is
+ * the same frame). Errors: RRT_EINVAL for NULL arguments, all planes NULL, a rect outside the film, bad rank / world, a precision that
+ * is not the handle's, or a frame in flight; RRT_EUNSUP / RRT_EPANIC as rrt_render_rect gives for the scene. */
+typedef struct rrt_aov {
+  int32_t mem;        /* RRT_MEM_* of the planes                                  */
+  int32_t precision;  /* must equal the handle's                                  */
+  void* albedo;       /* W*H*4: sum fw*rho.r, .g, .b | sum fw   over live samples  */
+  void* normal;       /* W*H*4: sum fw*n.x, .y, .z   | sum fw   over hit samples   */
+  void* depth;        /* W*H*4: sum fw*t, sum fw*t*t, sum fw over hit samples, 0  */
+} rrt_aov;            /* any plane may be NULL (not produced); all NULL = RRT_EINVAL */
+int rrt_render_aov(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples, rrt_aov* out);
+
 /* ---- multi-GPU film reassembly: RCCL over xGMI, one collective per frame ----
  * The reference has one address space: its rayon tiles merge under a lock (Film::merge_film_tile film.rs:248-263, driven from
  * integrator/mod.rs:64-74,133). Across GPUs every rank renders its bands (rrt_render_bands / _begin) into its own device

@@ -153,6 +153,11 @@ class RenderStats(C.Structure):
                 ("any_prims", C.c_uint64), ("tile_launches", C.c_uint64), ("root_culled", C.c_uint64), ("sky_culled", C.c_uint64), ("list_launches", C.c_uint64), ("ms_gather", C.c_double), ("s_horizon_build", C.c_double)]
 
 
+class Aov(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p)]
+
+
 # every symbol include/rrt.h declares (tests/test_abi.py checks the library exports all of them)
 PROTOTYPES = {
     "rrt_scene_load": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -179,6 +184,7 @@ PROTOTYPES = {
     "rrt_render_bands_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rrt_render_end": (C.c_int, [C.c_void_p]),
     "rrt_render_end_stats": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
+    "rrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.POINTER(Aov)]),
     "rrt_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "rrt_comm_id": (C.c_int, [C.c_void_p]),
     "rrt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

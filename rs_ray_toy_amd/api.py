@@ -206,6 +206,17 @@ class Renderer:
         _check(A.lib().rrt_render_bands(self._h, rank, world, film.ctypes.data, A.RRT_MEM_HOST, C.byref(st) if stats else None))
         return (film, st) if stats else film
 
+    # first-hit feature buffers (rrt_render_aov): the raw filtered sums, (H, W, 4) each; resolve_aov() divides them out
+    def render_aov(self, rect=None, max_samples=0, rank=0, world=1, planes=("albedo", "normal", "depth")):
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        out = {k: np.zeros((H, W, 4), self.dtype) for k in planes}
+        ptr = {k: (out[k].ctypes.data if k in out else None) for k in ("albedo", "normal", "depth")}
+        aov = A.Aov(A.RRT_MEM_HOST, self.precision, ptr["albedo"], ptr["normal"], ptr["depth"])
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_aov(self._h, r, rank, world, max_samples, C.byref(aov)))
+        return out
+
     def render_device(self, rect, film_ptr, stats=True):
         st = A.RenderStats()
         r = (C.c_int32 * 4)(*rect)
@@ -267,6 +278,36 @@ def resolve_rgba8(film, scale=1.0):
     return rgba
 
 
+def resolve_aov(aov):
+    """The sums of Renderer.render_aov -> dict(albedo (H, W, 3) = rgb / w_live, normal (H, W, 3) unit length (0 where nothing
+    is hit), depth (H, W) mean first-hit distance (0 where nothing is hit), coverage (H, W) = w_hit / w_live)."""
+    alb, nrm, dep = (np.asarray(aov[k], np.float64) for k in ("albedo", "normal", "depth"))
+    w_live, w_hit = alb[..., 3], dep[..., 2]
+    live, hit = w_live != 0, w_hit != 0
+    albedo = np.where(live[..., None], alb[..., :3] / np.where(live, w_live, 1.0)[..., None], 0.0)
+    length = np.linalg.norm(nrm[..., :3], axis=-1)
+    normal = np.where((length > 0)[..., None], nrm[..., :3] / np.where(length > 0, length, 1.0)[..., None], 0.0)
+    depth = np.where(hit, dep[..., 0] / np.where(hit, w_hit, 1.0), 0.0)
+    coverage = np.where(live, w_hit / np.where(live, w_live, 1.0), 0.0)
+    return dict(albedo=albedo, normal=normal, depth=depth, coverage=coverage)
+
+
+def write_aov_pngs(prefix, aov):
+    """<prefix>_albedo.png, <prefix>_normal.png (n * 0.5 + 0.5), <prefix>_depth.png (mean depth scaled to its own min .. max
+    over the covered pixels) from the sums of Renderer.render_aov - what rrt_render writes under RRT_AOV=<prefix>."""
+    res = resolve_aov(aov)
+    hit = res["coverage"] > 0
+    d = res["depth"]
+    lo, hi = (float(d[hit].min()), float(d[hit].max())) if hit.any() else (0.0, 0.0)
+    grey = np.where(hit, (d - lo) / (hi - lo) if hi > lo else 0.0, 0.0)
+    images = {"albedo": res["albedo"], "normal": np.where(hit[..., None], res["normal"] * 0.5 + 0.5, 0.0), "depth": np.repeat(grey[..., None], 3, -1)}
+    for name, rgb in images.items():
+        rgba = np.empty(rgb.shape[:2] + (4,), np.uint8)
+        rgba[..., :3] = np.clip(np.nan_to_num(rgb) * 255.0 + 0.5, 0.0, 255.0).astype(np.uint8)
+        rgba[..., 3] = 255
+        write_png(f"{prefix}_{name}.png", rgba)
+
+
 def write_png(path, rgba):
     rgba = np.ascontiguousarray(rgba, np.uint8)
     H, W, _ = rgba.shape
@@ -293,5 +334,7 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     print(f"{st.camera_rays} rays generated")
     rgba = resolve_rgba8(film, scene.desc.film.scale)
     write_png(save_to, rgba)
+    if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
+        write_aov_pngs(os.environ["RRT_AOV"], r.render_aov())
     r.close()
     return film, st

@@ -7,9 +7,13 @@
 //                   film.write_image -> write_image     -> rrt_resolve_rgba8 + rrt_write_png
 // Diagnostics go to stderr like the reference's eprintln!; its "N rays generated" line (integrator/mod.rs:137) goes to stdout.
 // Environment: RRT_GPUS = number of GPUs to partition the film over (default 1), RRT_PRECISION = f32 (default) | f64,
-// RRT_FIXED_BVH = 1 builds pbrt's intended tree instead of the reference's (quirks Q26 / Q27).
+// RRT_FIXED_BVH = 1 builds pbrt's intended tree instead of the reference's (quirks Q26 / Q27),
+// RRT_AOV = <prefix> writes the first-hit feature buffers after the frame (rrt_render_aov, on device 0 alone): <prefix>_albedo.png,
+// <prefix>_normal.png (n * 0.5 + 0.5) and <prefix>_depth.png (mean depth scaled to its own min .. max).
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +26,36 @@ namespace {
 int fail(const char* what, int rc) {
   std::fprintf(stderr, "rrt_render: %s failed (%d): %s\n", what, rc, rrt_last_error());
   return rc == RRT_EPANIC ? 101 : 1;   // a Rust panic exits with 101
+}
+
+// the sums of rrt_render_aov (rrt_aov in rrt.h) -> three 8-bit images
+template <typename R>
+int write_aov(rrt_handle* h, int precision, int W, int H, const std::string& prefix) {
+  const size_t npx = (size_t)W * (size_t)H;
+  std::vector<R> alb(4 * npx, R(0)), nrm(4 * npx, R(0)), dep(4 * npx, R(0));
+  rrt_aov out{RRT_MEM_HOST, precision, alb.data(), nrm.data(), dep.data()};
+  const int32_t rect[4] = {0, 0, W, H};
+  int rc = rrt_render_aov(h, rect, 0, 1, 0, &out);
+  if (rc != RRT_OK) return rc;
+  double dmin = INFINITY, dmax = -INFINITY;
+  for (size_t i = 0; i < npx; i++)
+    if (dep[4 * i + 2] != R(0)) { const double d = (double)dep[4 * i] / (double)dep[4 * i + 2]; dmin = std::min(dmin, d); dmax = std::max(dmax, d); }
+  auto q = [](double v) { return (uint8_t)std::min(255.0, std::max(0.0, (v == v ? v : 0.0) * 255.0 + 0.5)); };
+  std::vector<uint8_t> img[3];
+  for (auto& im : img) im.assign(4 * npx, 255);
+  for (size_t i = 0; i < npx; i++) {
+    const double w_live = (double)alb[4 * i + 3], w_hit = (double)dep[4 * i + 2];
+    const double n[3] = {(double)nrm[4 * i], (double)nrm[4 * i + 1], (double)nrm[4 * i + 2]}, len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double grey = (w_hit != 0.0 && dmax > dmin) ? ((double)dep[4 * i] / w_hit - dmin) / (dmax - dmin) : 0.0;
+    for (int c = 0; c < 3; c++) {
+      img[0][4 * i + c] = q(w_live != 0.0 ? (double)alb[4 * i + c] / w_live : 0.0);
+      img[1][4 * i + c] = q((w_hit != 0.0 && len > 0.0) ? n[c] / len * 0.5 + 0.5 : 0.0);
+      img[2][4 * i + c] = q(grey);
+    }
+  }
+  const char* names[3] = {"_albedo.png", "_normal.png", "_depth.png"};
+  for (int k = 0; k < 3 && rc == RRT_OK; k++) rc = rrt_write_png((prefix + names[k]).c_str(), img[k].data(), W, H);
+  return rc;
 }
 }  // namespace
 
@@ -96,6 +130,11 @@ int main(int argc, char** argv) {
   rc = rrt_resolve_rgba8(host.data(), precision, W, H, film_scale, rgba.data());
   if (rc == RRT_OK) rc = rrt_write_png(argv[2], rgba.data(), W, H);
   if (rc != RRT_OK) { const int e = fail("write_image", rc); cleanup(); return e; }
+  if (const char* env_aov = std::getenv("RRT_AOV"); env_aov && *env_aov) {
+    if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_AOV runs on one GPU: the feature buffers are rendered on device 0 alone\n");
+    rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, env_aov) : write_aov<double>(handles[0], precision, W, H, env_aov);
+    if (rc != RRT_OK) { const int e = fail("rrt_render_aov", rc); cleanup(); return e; }
+  }
   cleanup();
   return 0;
 }

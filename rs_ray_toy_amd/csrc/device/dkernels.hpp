@@ -1530,6 +1530,20 @@ RRT_DEV bool pass_pixel_inverse(const PassDesc& pd, int x, int y, uint32_t* pl) 
   *pl = (uint32_t)(lin - pd.pix_begin);
   return true;
 }
+// One sample of a wide filter at film pixel (x, y): FilmTile::add_sample's footprint test and table look-up (film.rs:77-130). False = the pixel is
+// outside the sample's footprint. k_film_wide and k_aov_wide both weigh through this function, so their weights are the same expressions.
+template <typename R>
+RRT_DEV bool film_wide_weight(const SceneDev<R>& s, R pfx, R pfy, int x, int y, R* fw) {
+  const R dx = pfx - R(0.5), dy = pfy - R(0.5);
+  // p0 = ceil(d - r), p1 = trunc(d + r) + 1 (Point2i::from truncates), clipped to the film by the tile bounds
+  const R p0x = ceil(dx - s.filter_rx), p0y = ceil(dy - s.filter_ry);
+  const R p1x = trunc(dx + s.filter_rx) + R(1), p1y = trunc(dy + s.filter_ry) + R(1);
+  if ((R)x < p0x || (R)x >= p1x || (R)y < p0y || (R)y >= p1y) return false;
+  const R fy = rabs(((R)y - dy) * s.filter_inv_ry * R(16)), fx = rabs(((R)x - dx) * s.filter_inv_rx * R(16));
+  const int ify = (int)rmin(floor(fy), R(15)), ifx = (int)rmin(floor(fx), R(15));
+  *fw = s.filter_table[ify * 16 + ifx];
+  return true;
+}
 template <typename R>
 __global__ void __launch_bounds__(kBlock) k_film_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1537,7 +1551,6 @@ __global__ void __launch_bounds__(kBlock) k_film_wide(SceneDev<R> s, Pools<R> p,
   const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
   R* px = film + 4 * ((size_t)y * (size_t)s.xres + (size_t)x);
   R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];   // running RGB + weight sums (see k_film_box)
-  const R inv_rx = s.filter_inv_rx, inv_ry = s.filter_inv_ry;
   for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
     if (sy < 0 || sy >= ymax) continue;
     for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
@@ -1546,14 +1559,8 @@ __global__ void __launch_bounds__(kBlock) k_film_wide(SceneDev<R> s, Pools<R> p,
       for (uint32_t sl = 0; sl < pd.ns; sl++) {
         const uint32_t slot = sl * pd.npix + pl;
         const typename Vec4T<R>::type cs = p.samp[slot];
-        const R dx = cs.x - R(0.5), dy = cs.y - R(0.5);
-        // p0 = ceil(d - r), p1 = trunc(d + r) + 1 (Point2i::from truncates), clipped to the film by the tile bounds
-        const R p0x = ceil(dx - s.filter_rx), p0y = ceil(dy - s.filter_ry);
-        const R p1x = trunc(dx + s.filter_rx) + R(1), p1y = trunc(dy + s.filter_ry) + R(1);
-        if ((R)x < p0x || (R)x >= p1x || (R)y < p0y || (R)y >= p1y) continue;
-        const R fy = rabs(((R)y - dy) * inv_ry * R(16)), fx = rabs(((R)x - dx) * inv_rx * R(16));
-        const int ify = (int)rmin(floor(fy), R(15)), ifx = (int)rmin(floor(fx), R(15));
-        const R fw = s.filter_table[ify * 16 + ifx];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
         const R w = p.weight[slot];
         Rgb<R> L;
         if (w > R(0)) { const typename Vec4T<R>::type l = p.L[slot]; L = Rgb<R>(l.x, l.y, l.z); }
@@ -1581,6 +1588,143 @@ __global__ void k_film_add(const R* src, R* dst, size_t n) {
   px[1] += R(0.212671) * cr + R(0.715160) * cg + R(0.072169) * cb;
   px[2] += R(0.019334) * cr + R(0.119193) * cg + R(0.950227) * cb;
   px[3] += wsum; px[3] += wsum; px[3] += wsum;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// First-hit feature buffers (rrt_render_aov, include/rrt.h): albedo, normal and depth of the camera rays' first hits, filtered by the
+// film's pixel filter. A pass of their own - camera kernels, closest-hit launch, k_aov_shade, k_aov_box / k_aov_wide - not a branch of
+// k_shade_path: the frame's kernels and their register budgets stay what they are.
+// ------------------------------------------------------------------------------------------------------------
+// rho of the table in rrt.h from the material's own parameters; a textured one is evaluated through `c` (zero differentials)
+template <typename R, bool TEX>
+RRT_DEV Rgb<R> aov_rho(const SceneDev<R>& s, const Material<R>& m, TexCtx<R>& c) {
+  auto par = [&](int slot, const R* k) -> Rgb<R> {
+    if (TEX) { if (m.tex[slot] >= 0) return TexEval<R, kTexDepth>::eval(s, m.tex[slot], c); }
+    return Rgb<R>(k);
+  };
+  switch (m.type) {
+    case 0: case 1: case 6: return rgb_clamp0(par(0, m.kd));   // Matte, Plastic, Translucent: Kd
+    case 3: return rgb_clamp0(par(2, m.kr));                   // Mirror: Kr
+    case 5: return Rgb<R>(R(1));                               // Glass
+    case 2: {                                                  // Metal: the conductor's reflectance at normal incidence
+      const Rgb<R> eta = par(3, m.eta), k = par(4, m.k), one(R(1));
+      return ((eta - one) * (eta - one) + k * k) / ((eta + one) * (eta + one) + k * k);
+    }
+    default: return Rgb<R>(R(0), R(1), R(1));                  // Debug: the sum of its two lobes
+  }
+}
+
+// One thread per entry of the camera queue, in queue order (slot word, ray, hit record: 128-bit loads). Two 16-byte records per slot:
+// rec_a = {rho.rgb, hit flag}, rec_b = {n.xyz, t}. Every live sample of the pass is in the queue (the camera kernels ran without the root
+// cull), so rec_a - the flag - is written for every live slot, hit or miss; rec_b only for hits. Slots that never reach the queue (dead
+// samples) get no record: the film kernels read records of slots with weight > 0 only.
+template <typename R, bool TEX>
+__global__ void __launch_bounds__(kBlock) k_aov_shade(SceneDev<R> s, Pools<R> p, typename Vec4T<R>::type* rec_a, typename Vec4T<R>::type* rec_b) {
+  using V4 = typename Vec4T<R>::type;
+  const uint32_t n = p.counters[C_ACTIVE];
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t slot = p.q_active[i].slot;
+    const V4 h = p.hit[i];
+    const int prim = (int)real_to_bits(h.y);
+    if (prim < 0) { rec_a[slot] = mk4u<R>(R(0), R(0), R(0), 0u); continue; }
+    const V4 ro = p.ray_o[i], rd = p.ray_d[i];
+    SurfExt<R> ext;
+    const Surf<R> si = build_surface(s, prim, V3<R>(ro.x, ro.y, ro.z), V3<R>(rd.x, rd.y, rd.z), h.x, h.z, h.w, TEX ? &ext : nullptr);
+    if (!si.ok) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_SHADING_NORMAL);   // primitives.rs:66, as the frame reports it
+    TexCtx<R> tc;
+    if (TEX) {   // dpdx = dpdy = 0, dudx .. dvdy = 0 (TexCtx's defaults)
+      tc.p = si.p; tc.u = ext.u; tc.v = ext.v;
+      tc.pd = V3<double>((double)si.p.x + (double)si.p_lo.x, (double)si.p.y + (double)si.p_lo.y, (double)si.p.z + (double)si.p_lo.z);
+    }
+    const Rgb<R> rho = aov_rho<R, TEX>(s, s.materials[si.material], tc);
+    if (TEX) { if (tc.err) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_MIPMAP); }
+    const V3<R> nn = vnormalize(si.n);
+    rec_a[slot] = mk4u<R>(rho.r, rho.g, rho.b, 1u);
+    rec_b[slot] = mk4<R>(nn.x, nn.y, nn.z, h.x);
+  }
+}
+
+// One live sample with filter weight fw into the three running sums of a pixel (rrt_aov in rrt.h). k_aov_box and k_aov_wide both add
+// through this function.
+template <typename R>
+struct AovPixel { typename Vec4T<R>::type alb, nrm, dep; };
+template <typename R>
+RRT_DEV void aov_add(AovPixel<R>& px, R fw, const typename Vec4T<R>::type& a, const typename Vec4T<R>::type* rec_b, uint32_t slot) {
+  px.alb.w += fw;
+  if (real_to_bits(a.w) == 0u) return;   // a live sample that misses the scene
+  const typename Vec4T<R>::type b = rec_b[slot];
+  px.alb.x += fw * a.x; px.alb.y += fw * a.y; px.alb.z += fw * a.z;
+  px.nrm.x += fw * b.x; px.nrm.y += fw * b.y; px.nrm.z += fw * b.z; px.nrm.w += fw;
+  px.dep.x += fw * b.w; px.dep.y += (fw * b.w) * b.w; px.dep.z += fw;
+}
+template <typename R>
+RRT_DEV AovPixel<R> aov_load(const R* planes, size_t plane_n, size_t pix) {
+  using V4 = typename Vec4T<R>::type;
+  AovPixel<R> px;
+  px.alb = reinterpret_cast<const V4*>(planes)[pix];
+  px.nrm = reinterpret_cast<const V4*>(planes + plane_n)[pix];
+  px.dep = reinterpret_cast<const V4*>(planes + 2 * plane_n)[pix];
+  return px;
+}
+template <typename R>
+RRT_DEV void aov_store(R* planes, size_t plane_n, size_t pix, const AovPixel<R>& px) {
+  using V4 = typename Vec4T<R>::type;
+  reinterpret_cast<V4*>(planes)[pix] = px.alb;
+  reinterpret_cast<V4*>(planes + plane_n)[pix] = px.nrm;
+  reinterpret_cast<V4*>(planes + 2 * plane_n)[pix] = px.dep;
+}
+
+// Gather form of k_film_box: one thread per pixel of the pass, its samples in sample order, running sums in the handle's three internal
+// W x H x 4 planes (`planes`, one after the other) - so the sums do not depend on how the samples were cut into passes.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_aov_box(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  const size_t pix = (size_t)py_ * (size_t)s.xres + px_, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
+  AovPixel<R> px = aov_load(planes, plane_n, pix);
+  for (uint32_t sl = 0; sl < pd.ns; sl++) {
+    const uint32_t slot = sl * pd.npix + pl;
+    if (!(p.weight[slot] > R(0))) continue;   // dead sample
+    aov_add(px, R(1), rec_a[slot], rec_b, slot);   // box filter table weight 1
+  }
+  aov_store(planes, plane_n, pix, px);
+}
+
+// Gather form of k_film_wide: one thread per film pixel within reach of the pass, the samples of every pass pixel within reach in the
+// same order, the film's own footprint test and table look-up (film_wide_weight).
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_aov_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b,
+                                                      int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint32_t)ew * (uint32_t)eh) return;
+  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
+  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
+  AovPixel<R> px = aov_load(planes, plane_n, pix);
+  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
+    if (sy < 0 || sy >= ymax) continue;
+    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+      uint32_t pl;
+      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
+      for (uint32_t sl = 0; sl < pd.ns; sl++) {
+        const uint32_t slot = sl * pd.npix + pl;
+        if (!(p.weight[slot] > R(0))) continue;
+        const typename Vec4T<R>::type cs = p.samp[slot];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
+        aov_add(px, fw, rec_a[slot], rec_b, slot);
+      }
+    }
+  }
+  aov_store(planes, plane_n, pix, px);
+}
+
+// the caller's plane += the internal one (`n` = W x H x 4 values)
+template <typename R>
+__global__ void k_aov_merge(const R* src, R* dst, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] += src[i];
 }
 
 }  // namespace rrtd

@@ -107,6 +107,15 @@ int rrt_render_end_stats(rrt_handle* h, rrt_render_stats* stats) {
   return guarded([&]() { h->impl->render_end(stats); });
 }
 
+int rrt_render_aov(rrt_handle* h, const int32_t rect[4], int rank, int world, uint64_t max_samples, rrt_aov* out) {
+  // the output description is checked first: it is the caller's own struct, wrong whichever handle it comes with
+  if (!out) { rrt::set_last_error("rrt_render_aov: null output description (rrt_aov)"); return RRT_EINVAL; }
+  if (!out->albedo && !out->normal && !out->depth) { rrt::set_last_error("rrt_render_aov: no plane requested (albedo, normal and depth are all NULL)"); return RRT_EINVAL; }
+  if (out->mem != RRT_MEM_HOST && out->mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_aov: bad mem"); return RRT_EINVAL; }
+  if (!h || !rect) { rrt::set_last_error("rrt_render_aov: null handle or rect"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_aov(rect, rank, world, max_samples, out); });
+}
+
 int rrt_set_option(rrt_handle* h, const char* key, double value) {
   if (!h || !key) { rrt::set_last_error("rrt_set_option: null argument"); return RRT_EINVAL; }
   return guarded([&]() { h->impl->set_option(key, value); });

@@ -52,6 +52,7 @@ struct HandleBase {
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
   virtual void render_end(rrt_render_stats* stats) = 0;
+  virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
   virtual void set_option(const std::string& key, double v) = 0;
   // rrt_film_gather (rrt_comm.hip): events on the handle's stream around the frame's collective, so that the frame's statistics can tell
   // the collective (rrt_render_stats::ms_gather) from the render (ms_total) - what a multi-GPU scaling run needs to separate imbalance from xGMI time
@@ -968,6 +969,94 @@ class Handle : public HandleBase {
     check_device_errors();
     if (stats) frame_stats(*fr, stats);
   }
+  // ---- first-hit feature buffers (rrt_render_aov): the frame's camera samples, traced once, into albedo / normal / depth planes -------------
+  // The pass loop of render_impl (same pixel groups and sample chunks from cap_) with three launches per pass: camera kernels, closest hit,
+  // k_aov_shade, then the gather-form film kernel over the handle's internal planes. Nothing of the frame's state is kept changed: the
+  // internal film, the statistics' totals and the tile-tree state are not touched (tile trees are used where a frame has built them, never
+  // built here), and what launch_raygen sets per pass is put back.
+  void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) override {
+    if (pending_) throw std::invalid_argument("render_aov: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (out->precision != precision()) throw std::invalid_argument("render_aov: plane precision must match the handle");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_aov: bad rank/world");
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    const rrt_film& f = desc_.film;
+    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
+    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_aov: rect outside the film");
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30, n_ranks = (uint32_t)world;
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
+    const size_t W = (size_t)f.xres, H = (size_t)f.yres, plane_n = W * H * 4;
+    size_t rh = (size_t)(rect[3] - rect[1]);
+    if (n_ranks > 1) {   // rows of this rank's bands
+      size_t rows = 0;
+      for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == (uint32_t)rank) rows++;
+      rh = rows;
+    }
+    const size_t rw = (size_t)(rect[2] - rect[0]), rpix = rw * rh;
+    uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
+    if (max_samples != 0) s_total = std::min<uint64_t>(s_total, max_samples);
+    if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
+    using V4 = typename Vec4T<R>::type;
+    struct Restore {   // what launch_raygen sets for the pass it last ran for
+      Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6];
+      ~Restore() { h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k]; }
+    } restore{this, tt_pass_ok_, film_runs_ok_, scene_.root_cull, {scene_.root_box[0], scene_.root_box[1], scene_.root_box[2], scene_.root_box[3], scene_.root_box[4], scene_.root_box[5]}};
+
+    if (aov_planes_.n != 3 * plane_n) aov_planes_.alloc(3 * plane_n);
+    HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
+    ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+    if (aov_rec_a_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); aov_rec_a_.alloc(cap_); aov_rec_b_.alloc(cap_); }
+    const size_t group = std::min(rpix, cap_);                     // pixels per group
+    const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
+    for (size_t g0 = 0; g0 < rpix; g0 += group) {
+      const size_t npix = std::min(group, rpix - g0);
+      for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
+        const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
+        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
+        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, (uint32_t)rank, tiled};
+        const size_t nslots = npix * (size_t)ns;
+        const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+        launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
+        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
+        const dim3 sg(std::min(grid, 16384u));
+        if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
+        else hipLaunchKernelGGL((k_aov_shade<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
+        if (!wide_filter) hipLaunchKernelGGL((k_aov_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p);
+        else {
+          // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as render_impl)
+          const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+          const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+          const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+          const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
+          hipLaunchKernelGGL((k_aov_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p,
+                             ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+        }
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    // merge into the caller's planes (+=)
+    void* user[3] = {out->albedo, out->normal, out->depth};
+    if (out->mem == RRT_MEM_DEVICE) {
+      for (int k = 0; k < 3; k++)
+        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)(aov_planes_.p + k * plane_n), (R*)user[k], plane_n);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(st_));
+    } else {
+      std::vector<R> tmp(plane_n);
+      for (int k = 0; k < 3; k++) {
+        if (!user[k]) continue;
+        HIP_CHECK(hipMemcpyAsync(tmp.data(), aov_planes_.p + k * plane_n, plane_n * sizeof(R), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipStreamSynchronize(st_));
+        R* dst = (R*)user[k];
+        for (size_t i = 0; i < plane_n; i++) dst[i] += tmp[i];
+      }
+    }
+    check_device_errors();
+  }
   void frame_stats(const FrameRec& fr, rrt_render_stats* stats) {
     unsigned long long ht[12];
     HIP_CHECK(hipMemcpy(ht, totals_.p, sizeof(ht), hipMemcpyDeviceToHost));
@@ -1108,6 +1197,8 @@ class Handle : public HandleBase {
   DevBuf<unsigned long long> totals_;
   DevBuf<R> film_;       // per pixel: running RGB contribution sum + filter weight sum of the frame being rendered
   DevBuf<R> film_xyz_;   // the same merged to XYZ, staging for a host film
+  DevBuf<R> aov_planes_;   // render_aov: running sums of the albedo, normal and depth planes, W x H x 4 each (allocated by the first call)
+  DevBuf<typename Vec4T<R>::type> aov_rec_a_, aov_rec_b_;   // k_aov_shade's per-slot records {rho.rgb, hit flag}, {n.xyz, t}: sized like pool.L
 
   // which materials the aggregate really uses (declared-but-unused ones never reach a kernel)
   void scan_materials(const rrt_scene_desc* d) {
