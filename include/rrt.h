@@ -410,6 +410,34 @@ typedef struct rrt_aov {
 } rrt_aov;            /* any plane may be NULL (not produced); all NULL = RRT_EINVAL */
 int rrt_render_aov(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples, rrt_aov* out);
 
+/* Denoiser (no counterpart in the reference): an edge-avoiding a-trous wavelet filter over a film, guided by the three planes of rrt_render_aov, with
+ * albedo demodulation and a luminance edge-stop scaled by a spatially estimated variance that the iterations carry along (the spatial half of SVGF).
+ * film_xyzw and the planes are full-frame W*H*4 sums of the handle's precision, exactly as rrt_render_rect / rrt_render_aov leave them, all in
+ * aov->mem (host or device); film_out is a film in the film's own layout (rrt_resolve_rgba8, rrt_film_gather take it as they take a frame) and
+ * may be film_xyzw. Rects and bands are summed by the caller first: the filter takes the whole frame.
+ *   per pixel p:  w = film[3], data = w > 0, rgb = xyz_to_rgb(film[:3] / w) (spectrum.rs:2075-2090, the matrices of rrt_resolve_rgba8);
+ *                 a = albedo[:3] / albedo[3] (0 where albedo[3] == 0); w_hit = depth[2], hit = w_hit > 0, z = depth[0] / w_hit,
+ *                 sd = sqrt(max(0, depth[1] / w_hit - z z)); n = normal[:3] / |normal[:3]| (0 where the length is 0);
+ *                 d = max(a, 1e-3) per channel when `demodulate`, else 1; c = rgb / d; l = 0.212671 c.r + 0.715160 c.g + 0.072169 c.b.
+ *   g(p, q):      0 if hit_p != hit_q, 1 if neither is hit, else max(0, n_p . n_q)^sigma_normal. A tap q is usable inside the frame where data_q.
+ *   variance:     over the usable taps of the 7 x 7 window around p, centre included, weights g: v_p = max(0, sum g l_q^2 / sum g - (sum g l_q / sum g)^2)
+ *                 (0 where sum g == 0).
+ *   iteration i = 0 .. iterations - 1, step s = 2^i:
+ *                 gv_p = sum k g v_q / sum k g over the usable taps of the 3 x 3 window at step 1, k = [1,2,1] x [1,2,1] (v_p where the sum is 0);
+ *                 the 25 taps q = p + s (dx, dy), dy outer, dx inner, both -2 .. 2 ascending, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+ *                 W = h[dy] h[dx] g(p, q) w_z w_l for usable taps, g = w_z = w_l = 1 at the centre;
+ *                 w_z = exp(-|z_p - z_q| / (sigma_depth (max(|dx|, |dy|) s sd_p + 1e-3 z_p))) where both are hit, else 1;
+ *                 w_l = exp(-|l_p - l_q| / (sigma_color sqrt(gv_p) + 1e-3 |l_p| + 1e-30)), 1 for sigma_color <= 0;
+ *                 c'_p = sum W c_q / sum W, v'_p = sum W^2 v_q / (sum W)^2, l from c'. Pixels without data keep c, v and are never a tap.
+ *   finish:       film_out[:3] = rgb_to_xyz(c d) w, film_out[3] = w (copied); a pixel without data is copied through unchanged.
+ * No weight carries an absolute radiance scale. The per-pixel steps before and after the iterations run in double in both precision modes.
+ * The handle is left as it was; its work buffers are allocated by the first call. Errors: RRT_EINVAL for a NULL aov, a NULL plane, bad mem,
+ * iterations outside 1 .. 6, sigma_normal or sigma_depth not > 0, a NULL film, film_out or handle, a precision that is not the handle's, or a
+ * frame in flight - each with its own message, the first seven before any device work. */
+typedef struct rrt_denoise_params { int32_t iterations; int32_t demodulate; double sigma_color, sigma_normal, sigma_depth; } rrt_denoise_params;
+void rrt_denoise_defaults(rrt_denoise_params*);   /* iterations 5, demodulate 1, sigma_color 4, sigma_normal 32, sigma_depth 8 */
+int rrt_denoise(rrt_handle*, const void* film_xyzw, const rrt_aov* aov, const rrt_denoise_params* params /* NULL = defaults */, void* film_out);
+
 /* ---- multi-GPU film reassembly: RCCL over xGMI, one collective per frame ----
  * The reference has one address space: its rayon tiles merge under a lock (Film::merge_film_tile film.rs:248-263, driven from
  * integrator/mod.rs:64-74,133). Across GPUs every rank renders its bands (rrt_render_bands / _begin) into its own device
@@ -482,6 +510,8 @@ int rrt_film_gather_all(rrt_handle* const* handles, void* const* films_device, i
  * film_records          1  fp32   path integrator, tile-tree passes, box filter of radius 0.5, untextured:       invariant (tests/test_film_records.py);
  *                                 radiance in per-workgroup record runs read by a run-walking box film;          other passes keep the per-slot layout
  *                                 0: the per-slot layout and k_film_box
+ * dn_lds                1         rrt_denoise: 1: the a-trous steps 1 and 2 read their taps from an LDS tile with       invariant (tests/test_denoise.py::test_denoise_lds_changes_nothing)
+ *                                 halo (the steps at which that measured faster); 0: direct gathers at every step
  */
 int rrt_set_option(rrt_handle*, const char* key, double value);
 

@@ -158,6 +158,11 @@ class Aov(C.Structure):
                 ("depth", C.c_void_p)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double)]
+
+
 # every symbol include/rrt.h declares (tests/test_abi.py checks the library exports all of them)
 PROTOTYPES = {
     "rrt_scene_load": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -185,6 +190,8 @@ PROTOTYPES = {
     "rrt_render_end": (C.c_int, [C.c_void_p]),
     "rrt_render_end_stats": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     "rrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.POINTER(Aov)]),
+    "rrt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+    "rrt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "rrt_comm_id": (C.c_int, [C.c_void_p]),
     "rrt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

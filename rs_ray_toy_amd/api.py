@@ -217,6 +217,39 @@ class Renderer:
         _check(A.lib().rrt_render_aov(self._h, r, rank, world, max_samples, C.byref(aov)))
         return out
 
+    # rrt_denoise: the edge-avoiding wavelet filter over a film, guided by the planes of render_aov (the definition is on the prototype in rrt.h)
+    def _denoise_params(self, params):
+        p = A.DenoiseParams()
+        A.lib().rrt_denoise_defaults(C.byref(p))
+        for k, v in params.items():
+            if k not in ("iterations", "demodulate", "sigma_color", "sigma_normal", "sigma_depth"):
+                raise TypeError(f"denoise: unknown parameter {k}")
+            setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
+        return p
+
+    def denoise(self, film, aov, out=None, **params):
+        """film (H, W, 4) and aov = the dict of render_aov (all three planes), host arrays of the handle's precision -> the filtered film
+        (`out`, which may be `film`, or a new array). params: iterations, demodulate, sigma_color, sigma_normal, sigma_depth."""
+        W, H = self.scene.resolution
+        arrs = [film] + [aov[k] for k in ("albedo", "normal", "depth")]
+        for a in arrs:
+            if a.dtype != self.dtype or a.shape != (H, W, 4) or not a.flags.c_contiguous:
+                raise ValueError("denoise: film and planes are C-contiguous (H, W, 4) arrays of the handle's precision")
+        if out is None:
+            out = np.empty((H, W, 4), self.dtype)
+        if out.dtype != self.dtype or out.shape != (H, W, 4) or not out.flags.c_contiguous:
+            raise ValueError("denoise: out is a C-contiguous (H, W, 4) array of the handle's precision")
+        d = A.Aov(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in arrs[1:]])
+        p = self._denoise_params(params)
+        _check(A.lib().rrt_denoise(self._h, film.ctypes.data, C.byref(d), C.byref(p), out.ctypes.data))
+        return out
+
+    def denoise_device(self, film_ptr, aov_ptrs, out_ptr, **params):
+        """The same on device buffers: raw pointers of the film, the (albedo, normal, depth) planes and the output (which may be the film)."""
+        d = A.Aov(A.RRT_MEM_DEVICE, self.precision, *aov_ptrs)
+        p = self._denoise_params(params)
+        _check(A.lib().rrt_denoise(self._h, film_ptr, C.byref(d), C.byref(p), out_ptr))
+
     def render_device(self, rect, film_ptr, stats=True):
         st = A.RenderStats()
         r = (C.c_int32 * 4)(*rect)
@@ -336,5 +369,7 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     write_png(save_to, rgba)
     if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
         write_aov_pngs(os.environ["RRT_AOV"], r.render_aov())
+    if os.environ.get("RRT_DENOISE"):   # as rrt_render: the filtered frame, guided by the planes of at most 32 samples per pixel
+        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, r.render_aov(max_samples=32)), scene.desc.film.scale))
     r.close()
     return film, st

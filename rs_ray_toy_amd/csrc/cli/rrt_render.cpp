@@ -9,7 +9,9 @@
 // Environment: RRT_GPUS = number of GPUs to partition the film over (default 1), RRT_PRECISION = f32 (default) | f64,
 // RRT_FIXED_BVH = 1 builds pbrt's intended tree instead of the reference's (quirks Q26 / Q27),
 // RRT_AOV = <prefix> writes the first-hit feature buffers after the frame (rrt_render_aov, on device 0 alone): <prefix>_albedo.png,
-// <prefix>_normal.png (n * 0.5 + 0.5) and <prefix>_depth.png (mean depth scaled to its own min .. max).
+// <prefix>_normal.png (n * 0.5 + 0.5) and <prefix>_depth.png (mean depth scaled to its own min .. max),
+// RRT_DENOISE = <path.png> writes the denoised frame beside the ordinary one: rrt_render_aov with max_samples 32 on device 0, then rrt_denoise
+// (default parameters) over the gathered film.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -55,6 +57,21 @@ int write_aov(rrt_handle* h, int precision, int W, int H, const std::string& pre
   }
   const char* names[3] = {"_albedo.png", "_normal.png", "_depth.png"};
   for (int k = 0; k < 3 && rc == RRT_OK; k++) rc = rrt_write_png((prefix + names[k]).c_str(), img[k].data(), W, H);
+  return rc;
+}
+
+// the gathered film, filtered by rrt_denoise under the planes of at most 32 samples per pixel -> one 8-bit image
+template <typename R>
+int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, const void* film, const char* path) {
+  const size_t npx = (size_t)W * (size_t)H;
+  std::vector<R> alb(4 * npx, R(0)), nrm(4 * npx, R(0)), dep(4 * npx, R(0)), out(4 * npx, R(0));
+  rrt_aov aov{RRT_MEM_HOST, precision, alb.data(), nrm.data(), dep.data()};
+  const int32_t rect[4] = {0, 0, W, H};
+  int rc = rrt_render_aov(h, rect, 0, 1, 32, &aov);
+  if (rc == RRT_OK) rc = rrt_denoise(h, film, &aov, nullptr, out.data());
+  std::vector<uint8_t> rgba(4 * npx);
+  if (rc == RRT_OK) rc = rrt_resolve_rgba8(out.data(), precision, W, H, scale, rgba.data());
+  if (rc == RRT_OK) rc = rrt_write_png(path, rgba.data(), W, H);
   return rc;
 }
 }  // namespace
@@ -134,6 +151,11 @@ int main(int argc, char** argv) {
     if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_AOV runs on one GPU: the feature buffers are rendered on device 0 alone\n");
     rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, env_aov) : write_aov<double>(handles[0], precision, W, H, env_aov);
     if (rc != RRT_OK) { const int e = fail("rrt_render_aov", rc); cleanup(); return e; }
+  }
+  if (const char* env_dn = std::getenv("RRT_DENOISE"); env_dn && *env_dn) {
+    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), env_dn)
+                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), env_dn);
+    if (rc != RRT_OK) { const int e = fail("rrt_denoise", rc); cleanup(); return e; }
   }
   cleanup();
   return 0;

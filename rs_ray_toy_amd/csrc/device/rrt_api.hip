@@ -116,6 +116,28 @@ int rrt_render_aov(rrt_handle* h, const int32_t rect[4], int rank, int world, ui
   return guarded([&]() { h->impl->render_aov(rect, rank, world, max_samples, out); });
 }
 
+void rrt_denoise_defaults(rrt_denoise_params* p) {
+  if (!p) return;
+  p->iterations = 5; p->demodulate = 1;
+  p->sigma_color = 4.0; p->sigma_normal = 32.0; p->sigma_depth = 8.0;
+}
+
+int rrt_denoise(rrt_handle* h, const void* film_xyzw, const rrt_aov* aov, const rrt_denoise_params* params, void* film_out) {
+  // the caller's own structs first (wrong whichever handle they come with), every pointer before any device work
+  if (!aov) { rrt::set_last_error("rrt_denoise: null plane description (rrt_aov)"); return RRT_EINVAL; }
+  if (!aov->albedo || !aov->normal || !aov->depth) { rrt::set_last_error("rrt_denoise: the filter needs all three planes (albedo, normal or depth is NULL)"); return RRT_EINVAL; }
+  if (aov->mem != RRT_MEM_HOST && aov->mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_denoise: bad mem"); return RRT_EINVAL; }
+  rrt_denoise_params p;
+  rrt_denoise_defaults(&p);
+  if (params) p = *params;
+  if (p.iterations < 1 || p.iterations > 6) { rrt::set_last_error("rrt_denoise: iterations must be 1 .. 6"); return RRT_EINVAL; }
+  if (!(p.sigma_normal > 0.0)) { rrt::set_last_error("rrt_denoise: sigma_normal must be > 0"); return RRT_EINVAL; }
+  if (!(p.sigma_depth > 0.0)) { rrt::set_last_error("rrt_denoise: sigma_depth must be > 0"); return RRT_EINVAL; }
+  if (!film_xyzw || !film_out) { rrt::set_last_error("rrt_denoise: null film or film_out"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_denoise: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->denoise(film_xyzw, aov, &p, film_out); });
+}
+
 int rrt_set_option(rrt_handle* h, const char* key, double value) {
   if (!h || !key) { rrt::set_last_error("rrt_set_option: null argument"); return RRT_EINVAL; }
   return guarded([&]() { h->impl->set_option(key, value); });

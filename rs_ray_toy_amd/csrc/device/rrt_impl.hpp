@@ -20,6 +20,7 @@
 
 #include <type_traits>
 
+#include "dfilter.hpp"
 #include "dkernels.hpp"
 #include "dtraverse_f32.hpp"
 #include "rrt.h"
@@ -53,6 +54,7 @@ struct HandleBase {
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
   virtual void render_end(rrt_render_stats* stats) = 0;
   virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
+  virtual void denoise(const void* film, const rrt_aov* aov, const rrt_denoise_params* p, void* film_out) = 0;
   virtual void set_option(const std::string& key, double v) = 0;
   // rrt_film_gather (rrt_comm.hip): events on the handle's stream around the frame's collective, so that the frame's statistics can tell
   // the collective (rrt_render_stats::ms_gather) from the render (ms_total) - what a multi-GPU scaling run needs to separate imbalance from xGMI time
@@ -611,6 +613,7 @@ class Handle : public HandleBase {
     else if (key == "film_records") film_records_on_ = v != 0;   // 1 (default): the path integrator's tile-tree passes keep radiance in per-workgroup record runs, added up by k_film_box_runs
     else if (key == "shade_spec") shade_kinds_ = v != 0 ? shade_kinds_scene_ : kAllKinds;
     else if (key == "frame_stats") frame_stats_ = v != 0;
+    else if (key == "dn_lds") dn_lds_ = v != 0;   // rrt_denoise: 1 (default): the a-trous steps 1 and 2 read their taps from an LDS tile; 0: direct gathers at every step
     else if (key == "halton_tables") scene_.n_hblk = (v != 0 && hblk_.n) ? (uint32_t)kHaltonTabDims : 0u;
     else if (key == "cam_tables") { for (int w = 0; w < 3; w++) { scene_.cam_lo[w] = (v != 0 && cam_lo_.n) ? cam_lo_.p + cam_lo_off_[w] : nullptr; scene_.cam_hi[w] = (v != 0 && cam_hi_.n) ? cam_hi_.p + cam_hi_off_[w] : nullptr; } }
     else if (key == "any_entry") { any_entry_on_ = v != 0; trav_.any_list = (any_entry_on_ && any_list_.n) ? reinterpret_cast<const uint4*>(any_list_.p) : nullptr; }
@@ -1057,6 +1060,60 @@ class Handle : public HandleBase {
     }
     check_device_errors();
   }
+  // ---- rrt_denoise (device/dfilter.hpp): prepare, initial variance, one a-trous launch per iteration, finish ---------------------------------------------
+  // Only the handle's stream and its own work buffers are used: nothing of the frame's state is read or written.
+  template <int S>
+  void launch_atrous(bool lds, dim3 grid, const typename Vec4T<R>::type* cin, typename Vec4T<R>::type* cout, const DnParams<R>& k) {
+    const dim3 block(kDnBX, kDnBY);
+    if constexpr (S <= 2) {   // the steps at which the LDS tile measured faster than the gathers (40 against 67 us per launch at 1024^2, fp32)
+      if (lds) { hipLaunchKernelGGL((k_dn_atrous_lds<R, S>), grid, block, 0, st_, cin, cout, dn_g_.p, dn_p_.p, k); return; }
+    }
+    hipLaunchKernelGGL((k_dn_atrous<R, S>), grid, block, 0, st_, cin, cout, dn_g_.p, dn_p_.p, k);
+  }
+  void denoise(const void* film, const rrt_aov* aov, const rrt_denoise_params* p, void* film_out) override {
+    if (pending_) throw std::invalid_argument("denoise: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (aov->precision != precision()) throw std::invalid_argument("denoise: plane precision must match the handle");
+    HIP_CHECK(hipSetDevice(dev_));
+    using V4 = typename Vec4T<R>::type;
+    const size_t W = (size_t)desc_.film.xres, H = (size_t)desc_.film.yres, npix = W * H;
+    if (npix == 0) return;
+    if (!dn_p_.p || dn_p_.n != npix) { dn_c_[0].alloc(npix); dn_c_[1].alloc(npix); dn_g_.alloc(npix); dn_p_.alloc(npix); }   // dn_p_ last: set only when all four exist
+    const V4* in[4] = {(const V4*)film, (const V4*)aov->albedo, (const V4*)aov->normal, (const V4*)aov->depth};
+    V4* out = (V4*)film_out;
+    const bool host = aov->mem == RRT_MEM_HOST;
+    if (host) {   // staged: the four inputs, the output over the film's copy
+      if (!dn_stage_.p || dn_stage_.n != 4 * npix) dn_stage_.alloc(4 * npix);
+      const void* src[4] = {film, aov->albedo, aov->normal, aov->depth};
+      for (int j = 0; j < 4; j++) {
+        HIP_CHECK(hipMemcpyAsync(dn_stage_.p + j * npix, src[j], npix * sizeof(V4), hipMemcpyHostToDevice, st_));
+        in[j] = dn_stage_.p + j * npix;
+      }
+      out = dn_stage_.p;
+    }
+    const DnParams<R> k{(int)W, (int)H, (R)p->sigma_color, (R)p->sigma_normal, (R)p->sigma_depth};
+    const uint32_t lin = (uint32_t)((npix + 255) / 256);
+    const dim3 grid((uint32_t)((W + kDnBX - 1) / kDnBX), (uint32_t)((H + kDnBY - 1) / kDnBY)), block(kDnBX, kDnBY);
+    hipLaunchKernelGGL((k_dn_prepare<R>), dim3(lin), dim3(256), 0, st_, in[0], in[1], in[2], in[3], dn_c_[0].p, dn_g_.p, dn_p_.p, npix, p->demodulate != 0 ? 1 : 0);
+    hipLaunchKernelGGL((k_dn_moments<R>), grid, block, 0, st_, (const V4*)dn_c_[0].p, dn_c_[1].p, (const V4*)dn_g_.p, k);
+    int cur = 1;
+    const bool lds = dn_lds_;
+    for (int i = 0; i < p->iterations; i++, cur ^= 1) {
+      const V4* cin = dn_c_[cur].p;
+      V4* cout = dn_c_[cur ^ 1].p;
+      switch (i) {
+        case 0: launch_atrous<1>(lds, grid, cin, cout, k); break;
+        case 1: launch_atrous<2>(lds, grid, cin, cout, k); break;
+        case 2: launch_atrous<4>(lds, grid, cin, cout, k); break;
+        case 3: launch_atrous<8>(lds, grid, cin, cout, k); break;
+        case 4: launch_atrous<16>(lds, grid, cin, cout, k); break;
+        default: launch_atrous<32>(lds, grid, cin, cout, k); break;
+      }
+    }
+    hipLaunchKernelGGL((k_dn_finish<R>), dim3(lin), dim3(256), 0, st_, in[0], (const V4*)dn_c_[cur].p, (const V4*)dn_p_.p, out, npix);
+    HIP_CHECK(hipGetLastError());
+    if (host) HIP_CHECK(hipMemcpyAsync(film_out, dn_stage_.p, npix * sizeof(V4), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+  }
   void frame_stats(const FrameRec& fr, rrt_render_stats* stats) {
     unsigned long long ht[12];
     HIP_CHECK(hipMemcpy(ht, totals_.p, sizeof(ht), hipMemcpyDeviceToHost));
@@ -1198,6 +1255,8 @@ class Handle : public HandleBase {
   DevBuf<R> film_;       // per pixel: running RGB contribution sum + filter weight sum of the frame being rendered
   DevBuf<R> film_xyz_;   // the same merged to XYZ, staging for a host film
   DevBuf<R> aov_planes_;   // render_aov: running sums of the albedo, normal and depth planes, W x H x 4 each (allocated by the first call)
+  DevBuf<typename Vec4T<R>::type> dn_c_[2], dn_g_, dn_p_, dn_stage_;   // denoise: the record planes C (ping-pong), G, P of dfilter.hpp, and the staging of host-memory calls (allocated by the first call)
+  bool dn_lds_ = true;       // option "dn_lds"
   DevBuf<typename Vec4T<R>::type> aov_rec_a_, aov_rec_b_;   // k_aov_shade's per-slot records {rho.rgb, hit flag}, {n.xyz, t}: sized like pool.L
 
   // which materials the aggregate really uses (declared-but-unused ones never reach a kernel)
