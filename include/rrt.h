@@ -438,6 +438,40 @@ typedef struct rrt_denoise_params { int32_t iterations; int32_t demodulate; doub
 void rrt_denoise_defaults(rrt_denoise_params*);   /* iterations 5, demodulate 1, sigma_color 4, sigma_normal 32, sigma_depth 8 */
 int rrt_denoise(rrt_handle*, const void* film_xyzw, const rrt_aov* aov, const rrt_denoise_params* params /* NULL = defaults */, void* film_out);
 
+/* Sample-variance plane beside the film (no counterpart in the reference, whose FilmTile keeps only the sums): the frame of rrt_render_rect
+ * (rank / world = 0 / 1) or of the rect's interleaved 16-row bands b % world == rank, partitioned as rrt_render_aov partitions them, and per
+ * film pixel the weighted moments of its samples' luminance. film_xyzw is added to (+=) with the very bits, all four channels, that
+ * rrt_render_rect / rrt_render_bands would have added, and the statistics hold the same camera_rays, closest_queries, any_queries,
+ * root_culled and sky_culled. `moments` is a second full-frame W*H*4 plane of the handle's precision in the same `mem`, also added to (+=):
+ *     { S1 = sum fw y,  S2 = sum fw y^2,  S0 = sum fw,  S3 = sum fw^2 }
+ * over EVERY sample of the frame whose filter footprint covers the pixel - dead samples (camera weight 0) included with y = 0, because the
+ * film's filter_weight_sum counts them (Q2).
+ *   fw:  the film's filter weight of the sample at the pixel (box filter of radius 0.5: 1 in the sample's own pixel; every other filter:
+ *        FilmTile::add_sample's footprint test and 16 x 16 table, film.rs:77-130, as rrt_render_aov's fw).
+ *   y:   (0.212671 L.r + 0.715160 L.g + 0.072169 L.b) w = 0.212671 (L.r w) + 0.715160 (L.g w) + 0.072169 (L.b w) up to rounding, L the
+ *        sample's radiance after the film's own NaN / negative / infinity / max_sample_luminance handling (integrator/mod.rs:105-122), w the
+ *        camera weight.
+ * So S1 is the film's Y channel up to rounding and S0 the film's weight channel / 3 (Q3); for the box filter of radius 0.5 S0 = S3 = the
+ * sample count. The plane is a plain sum: rects, bands and ranks add up, a wide filter's splats across a border land in this call's plane as
+ * they do in its film, and a pixel's sums do not depend on how the frame was cut into pool passes (samples are added in sample order).
+ * A moments frame renders as with the option film_records 0 (per-slot radiance layout), which changes no bit of the film. The handle is left
+ * as it was. Errors: RRT_EINVAL, each with its own message, for a NULL handle, rect, film or moments and a bad mem (before any device
+ * work), bad rank / world, a rect outside the film, a frame in flight; otherwise what rrt_render_rect gives for the scene. There is no
+ * _begin / _end form. */
+int rrt_render_moments(rrt_handle*, const int32_t rect[4], int rank, int world, void* film_xyzw, void* moments, int mem,
+                       rrt_render_stats* stats /* may be NULL */);
+
+/* rrt_denoise with the variance of the pixels' means taken from the plane of rrt_render_moments (summed over rects / bands by the caller, in
+ * aov->mem) where a pixel has one: the same prepare, iterations, finish and argument checks, and RRT_EINVAL for a NULL moments. Only the
+ * `variance` step differs. Per pixel p with data, in double in both precision modes:
+ *   n_eff = S0^2 / S3 (0 where S3 <= 0);
+ *   where n_eff >= 2 and S1 > 0:  rel = max(0, (S2 / S1) (S0 / S1) - 1) (= S2 S0 / S1^2 - 1; no square of a tiny S1),  v_p = l_p^2 rel / (n_eff - 1), l_p the luminance of the stored c record
+ *                 (what the spatial estimate reads), the product rounded once to the record type: the variance of the pixel's mean, carried
+ *                 to demodulated units by its relative size - no weight carries an absolute radiance scale, and Q3's tripling cancels;
+ *   elsewhere:    rrt_denoise's 7 x 7 spatial estimate, unchanged (every sample black, fewer than two effective samples, an empty plane). */
+int rrt_denoise_moments(rrt_handle*, const void* film_xyzw, const rrt_aov* aov, const void* moments,
+                        const rrt_denoise_params* params /* NULL = defaults */, void* film_out);
+
 /* ---- multi-GPU film reassembly: RCCL over xGMI, one collective per frame ----
  * The reference has one address space: its rayon tiles merge under a lock (Film::merge_film_tile film.rs:248-263, driven from
  * integrator/mod.rs:64-74,133). Across GPUs every rank renders its bands (rrt_render_bands / _begin) into its own device

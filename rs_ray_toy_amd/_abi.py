@@ -192,6 +192,8 @@ PROTOTYPES = {
     "rrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.POINTER(Aov)]),
     "rrt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "rrt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.POINTER(DenoiseParams), C.c_void_p]),
+    "rrt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
+    "rrt_denoise_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "rrt_comm_id": (C.c_int, [C.c_void_p]),
     "rrt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -217,6 +217,29 @@ class Renderer:
         _check(A.lib().rrt_render_aov(self._h, r, rank, world, max_samples, C.byref(aov)))
         return out
 
+    # rrt_render_moments: the frame of render() / render_bands() and the sample-variance plane {S1, S2, S0, S3} beside it; resolve_moments() divides it out
+    def render_moments(self, rect=None, rank=0, world=1, film=None, moments=None, stats=False):
+        """-> (film, moments[, stats]): both (H, W, 4) host arrays of the handle's precision, added to (+=) where given."""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        if film is None:
+            film = np.zeros((H, W, 4), self.dtype)
+        if moments is None:
+            moments = np.zeros((H, W, 4), self.dtype)
+        for a in (film, moments):
+            if a.dtype != self.dtype or a.shape != (H, W, 4) or not a.flags.c_contiguous:
+                raise ValueError("render_moments: film and moments are C-contiguous (H, W, 4) arrays of the handle's precision")
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_moments(self._h, r, rank, world, film.ctypes.data, moments.ctypes.data, A.RRT_MEM_HOST, C.byref(st) if stats else None))
+        return (film, moments, st) if stats else (film, moments)
+
+    def render_moments_device(self, rect, film_ptr, moments_ptr, rank=0, world=1, stats=True):
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_moments(self._h, r, rank, world, film_ptr, moments_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
+        return st
+
     # rrt_denoise: the edge-avoiding wavelet filter over a film, guided by the planes of render_aov (the definition is on the prototype in rrt.h)
     def _denoise_params(self, params):
         p = A.DenoiseParams()
@@ -227,11 +250,12 @@ class Renderer:
             setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
         return p
 
-    def denoise(self, film, aov, out=None, **params):
+    def denoise(self, film, aov, out=None, moments=None, **params):
         """film (H, W, 4) and aov = the dict of render_aov (all three planes), host arrays of the handle's precision -> the filtered film
-        (`out`, which may be `film`, or a new array). params: iterations, demodulate, sigma_color, sigma_normal, sigma_depth."""
+        (`out`, which may be `film`, or a new array). params: iterations, demodulate, sigma_color, sigma_normal, sigma_depth.
+        moments: the plane of render_moments; the filter then starts from the pixels' sample variance (rrt_denoise_moments)."""
         W, H = self.scene.resolution
-        arrs = [film] + [aov[k] for k in ("albedo", "normal", "depth")]
+        arrs = [film] + [aov[k] for k in ("albedo", "normal", "depth")] + ([] if moments is None else [moments])
         for a in arrs:
             if a.dtype != self.dtype or a.shape != (H, W, 4) or not a.flags.c_contiguous:
                 raise ValueError("denoise: film and planes are C-contiguous (H, W, 4) arrays of the handle's precision")
@@ -239,16 +263,23 @@ class Renderer:
             out = np.empty((H, W, 4), self.dtype)
         if out.dtype != self.dtype or out.shape != (H, W, 4) or not out.flags.c_contiguous:
             raise ValueError("denoise: out is a C-contiguous (H, W, 4) array of the handle's precision")
-        d = A.Aov(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in arrs[1:]])
+        d = A.Aov(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in arrs[1:4]])
         p = self._denoise_params(params)
-        _check(A.lib().rrt_denoise(self._h, film.ctypes.data, C.byref(d), C.byref(p), out.ctypes.data))
+        if moments is None:
+            _check(A.lib().rrt_denoise(self._h, film.ctypes.data, C.byref(d), C.byref(p), out.ctypes.data))
+        else:
+            _check(A.lib().rrt_denoise_moments(self._h, film.ctypes.data, C.byref(d), moments.ctypes.data, C.byref(p), out.ctypes.data))
         return out
 
-    def denoise_device(self, film_ptr, aov_ptrs, out_ptr, **params):
-        """The same on device buffers: raw pointers of the film, the (albedo, normal, depth) planes and the output (which may be the film)."""
+    def denoise_device(self, film_ptr, aov_ptrs, out_ptr, moments_ptr=None, **params):
+        """The same on device buffers: raw pointers of the film, the (albedo, normal, depth) planes and the output (which may be the film);
+        moments_ptr: the plane of rrt_render_moments (rrt_denoise_moments)."""
         d = A.Aov(A.RRT_MEM_DEVICE, self.precision, *aov_ptrs)
         p = self._denoise_params(params)
-        _check(A.lib().rrt_denoise(self._h, film_ptr, C.byref(d), C.byref(p), out_ptr))
+        if moments_ptr is None:
+            _check(A.lib().rrt_denoise(self._h, film_ptr, C.byref(d), C.byref(p), out_ptr))
+        else:
+            _check(A.lib().rrt_denoise_moments(self._h, film_ptr, C.byref(d), moments_ptr, C.byref(p), out_ptr))
 
     def render_device(self, rect, film_ptr, stats=True):
         st = A.RenderStats()
@@ -325,6 +356,18 @@ def resolve_aov(aov):
     return dict(albedo=albedo, normal=normal, depth=depth, coverage=coverage)
 
 
+def resolve_moments(m):
+    """The sums of Renderer.render_moments -> dict(mean (H, W) = S1 / S0: the pixel's mean sample luminance, variance_of_mean (H, W) =
+    (S2 / S0 - mean^2) / (n_eff - 1) (0 where n_eff < 2), n_eff (H, W) = S0^2 / S3: Kish's effective sample count)."""
+    m = np.asarray(m, np.float64)
+    s1, s2, s0, s3 = m[..., 0], m[..., 1], m[..., 2], m[..., 3]
+    with np.errstate(all="ignore"):
+        n_eff = np.where(s3 > 0, s0 * s0 / s3, 0.0)
+        mean = np.where(s0 > 0, s1 / s0, 0.0)
+        var = np.where(n_eff >= 2, np.maximum(0.0, s2 / s0 - mean * mean) / (n_eff - 1.0), 0.0)
+    return dict(mean=mean, variance_of_mean=var, n_eff=n_eff)
+
+
 def write_aov_pngs(prefix, aov):
     """<prefix>_albedo.png, <prefix>_normal.png (n * 0.5 + 0.5), <prefix>_depth.png (mean depth scaled to its own min .. max
     over the covered pixels) from the sums of Renderer.render_aov - what rrt_render writes under RRT_AOV=<prefix>."""
@@ -363,13 +406,17 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     r = Renderer(scene, device, precision)
     for w in r.warnings:
         print(w, flush=True)
-    film, st = r.render(stats=True)
+    moments = None
+    if os.environ.get("RRT_DENOISE") and os.environ.get("RRT_DENOISE_MOMENTS", "0") not in ("", "0"):   # as rrt_render: the same frame, and its sample-variance plane
+        film, moments, st = r.render_moments(stats=True)
+    else:
+        film, st = r.render(stats=True)
     print(f"{st.camera_rays} rays generated")
     rgba = resolve_rgba8(film, scene.desc.film.scale)
     write_png(save_to, rgba)
     if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
         write_aov_pngs(os.environ["RRT_AOV"], r.render_aov())
     if os.environ.get("RRT_DENOISE"):   # as rrt_render: the filtered frame, guided by the planes of at most 32 samples per pixel
-        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, r.render_aov(max_samples=32)), scene.desc.film.scale))
+        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, r.render_aov(max_samples=32), moments=moments), scene.desc.film.scale))
     r.close()
     return film, st

@@ -11,7 +11,9 @@
 // RRT_AOV = <prefix> writes the first-hit feature buffers after the frame (rrt_render_aov, on device 0 alone): <prefix>_albedo.png,
 // <prefix>_normal.png (n * 0.5 + 0.5) and <prefix>_depth.png (mean depth scaled to its own min .. max),
 // RRT_DENOISE = <path.png> writes the denoised frame beside the ordinary one: rrt_render_aov with max_samples 32 on device 0, then rrt_denoise
-// (default parameters) over the gathered film.
+// (default parameters) over the gathered film,
+// RRT_DENOISE_MOMENTS = 1 (any value but "" and "0") beside RRT_DENOISE (one GPU): the frame is rendered by rrt_render_moments - the same film, bit for bit, so the ordinary
+// PNG is unchanged - and the denoised frame comes from rrt_denoise_moments under the frame's sample-variance plane.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -62,13 +64,13 @@ int write_aov(rrt_handle* h, int precision, int W, int H, const std::string& pre
 
 // the gathered film, filtered by rrt_denoise under the planes of at most 32 samples per pixel -> one 8-bit image
 template <typename R>
-int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, const void* film, const char* path) {
+int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, const void* film, const void* moments /* NULL: rrt_denoise */, const char* path) {
   const size_t npx = (size_t)W * (size_t)H;
   std::vector<R> alb(4 * npx, R(0)), nrm(4 * npx, R(0)), dep(4 * npx, R(0)), out(4 * npx, R(0));
   rrt_aov aov{RRT_MEM_HOST, precision, alb.data(), nrm.data(), dep.data()};
   const int32_t rect[4] = {0, 0, W, H};
   int rc = rrt_render_aov(h, rect, 0, 1, 32, &aov);
-  if (rc == RRT_OK) rc = rrt_denoise(h, film, &aov, nullptr, out.data());
+  if (rc == RRT_OK) rc = moments ? rrt_denoise_moments(h, film, &aov, moments, nullptr, out.data()) : rrt_denoise(h, film, &aov, nullptr, out.data());
   std::vector<uint8_t> rgba(4 * npx);
   if (rc == RRT_OK) rc = rrt_resolve_rgba8(out.data(), precision, W, H, scale, rgba.data());
   if (rc == RRT_OK) rc = rrt_write_png(path, rgba.data(), W, H);
@@ -100,13 +102,22 @@ int main(int argc, char** argv) {
   int32_t W = 0, H = 0;
   double film_scale = 1.0;
   (void)rrt_scene_film(scene, &W, &H, &film_scale);
+  const char* env_dn_path = std::getenv("RRT_DENOISE");
+  const char* env_dn_mom = std::getenv("RRT_DENOISE_MOMENTS");
+  bool with_moments = env_dn_path && *env_dn_path && env_dn_mom && *env_dn_mom && std::strcmp(env_dn_mom, "0") != 0;   // on for any value but "" and "0", as deploy_render reads it
+  if (with_moments && n_gpus > 1) {
+    std::fprintf(stderr, "rrt_render: RRT_DENOISE_MOMENTS runs on one GPU: the denoised frame keeps the spatial variance estimate\n");
+    with_moments = false;
+  }
   const size_t word = precision == RRT_F32 ? 4 : 8, film_bytes = (size_t)W * (size_t)H * 4 * word;
   // the tiles banner of integrator/mod.rs:59-62
   std::fprintf(stderr, "Rendering %d x %d, %d tile rows of 16 over %d GPU(s)\n", W, H, (H + 15) / 16, n_gpus);
 
   std::vector<rrt_handle*> handles(n_gpus, nullptr);
   std::vector<void*> films(n_gpus, nullptr);
+  void* moments_dev = nullptr;   // the sample-variance plane of device 0 (RRT_DENOISE_MOMENTS)
   auto cleanup = [&]() {
+    if (moments_dev) { (void)hipSetDevice(0); (void)hipFree(moments_dev); }
     for (int i = 0; i < n_gpus; i++) {
       if (handles[i]) rrt_destroy(handles[i]);
       if (films[i]) { (void)hipSetDevice(i); (void)hipFree(films[i]); }
@@ -123,19 +134,32 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  // every GPU renders its interleaved bands at the same time (the calls only enqueue), then one collective, then wait
-  for (int i = 0; i < n_gpus; i++) {
-    rc = rrt_render_bands_begin(handles[i], i, n_gpus, films[i]);
-    if (rc != RRT_OK) { const int e = fail("rrt_render_bands_begin", rc); cleanup(); return e; }
-  }
-  rc = rrt_film_gather_all(handles.data(), films.data(), n_gpus, 0);
-  if (rc != RRT_OK) { const int e = fail("rrt_film_gather_all", rc); cleanup(); return e; }
   unsigned long long rays_generated = 0;
-  for (int i = n_gpus - 1; i >= 0; i--) {   // rank 0 last: its stream carries the receiving half of the collective
+  if (with_moments) {   // one GPU: the whole frame and its moments plane in one call
+    if (hipSetDevice(0) != hipSuccess || hipMalloc(&moments_dev, film_bytes) != hipSuccess || hipMemset(moments_dev, 0, film_bytes) != hipSuccess) {
+      std::fprintf(stderr, "rrt_render: cannot allocate the %zu-byte moments plane on device 0\n", film_bytes);
+      cleanup();
+      return 1;
+    }
+    const int32_t rect[4] = {0, 0, W, H};
     rrt_render_stats st;
-    rc = rrt_render_end_stats(handles[i], &st);
-    if (rc != RRT_OK) { const int e = fail("rrt_render_end", rc); cleanup(); return e; }
-    rays_generated += st.camera_rays;
+    rc = rrt_render_moments(handles[0], rect, 0, 1, films[0], moments_dev, RRT_MEM_DEVICE, &st);
+    if (rc != RRT_OK) { const int e = fail("rrt_render_moments", rc); cleanup(); return e; }
+    rays_generated = st.camera_rays;
+  } else {
+    // every GPU renders its interleaved bands at the same time (the calls only enqueue), then one collective, then wait
+    for (int i = 0; i < n_gpus; i++) {
+      rc = rrt_render_bands_begin(handles[i], i, n_gpus, films[i]);
+      if (rc != RRT_OK) { const int e = fail("rrt_render_bands_begin", rc); cleanup(); return e; }
+    }
+    rc = rrt_film_gather_all(handles.data(), films.data(), n_gpus, 0);
+    if (rc != RRT_OK) { const int e = fail("rrt_film_gather_all", rc); cleanup(); return e; }
+    for (int i = n_gpus - 1; i >= 0; i--) {   // rank 0 last: its stream carries the receiving half of the collective
+      rrt_render_stats st;
+      rc = rrt_render_end_stats(handles[i], &st);
+      if (rc != RRT_OK) { const int e = fail("rrt_render_end", rc); cleanup(); return e; }
+      rays_generated += st.camera_rays;
+    }
   }
   std::printf("%llu rays generated\n", rays_generated);   // integrator/mod.rs:137 (camera samples with weight > 0, over all tiles)
   std::vector<unsigned char> host(film_bytes), rgba((size_t)W * (size_t)H * 4);
@@ -152,10 +176,20 @@ int main(int argc, char** argv) {
     rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, env_aov) : write_aov<double>(handles[0], precision, W, H, env_aov);
     if (rc != RRT_OK) { const int e = fail("rrt_render_aov", rc); cleanup(); return e; }
   }
-  if (const char* env_dn = std::getenv("RRT_DENOISE"); env_dn && *env_dn) {
-    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), env_dn)
-                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), env_dn);
-    if (rc != RRT_OK) { const int e = fail("rrt_denoise", rc); cleanup(); return e; }
+  if (const char* env_dn = env_dn_path; env_dn && *env_dn) {
+    std::vector<unsigned char> host_moments;
+    if (with_moments) {
+      host_moments.resize(film_bytes);
+      if (hipMemcpy(host_moments.data(), moments_dev, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "rrt_render: moments copy-out failed\n");
+        cleanup();
+        return 1;
+      }
+    }
+    const void* mom = with_moments ? host_moments.data() : nullptr;
+    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), mom, env_dn)
+                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), mom, env_dn);
+    if (rc != RRT_OK) { const int e = fail(with_moments ? "rrt_denoise_moments" : "rrt_denoise", rc); cleanup(); return e; }
   }
   cleanup();
   return 0;

@@ -160,6 +160,25 @@ __global__ void __launch_bounds__(kDnBX* kDnBY) k_dn_moments(const typename Vec4
   Cout[i] = cp;
 }
 
+// ---- rrt_denoise_moments: the variance of the pixel's mean from the plane of rrt_render_moments, where the pixel has one ----------------------------
+// Runs after k_dn_moments over the same C records: v is replaced where n_eff >= 2 and S1 > 0, the spatial estimate stays everywhere else. One
+// thread per pixel, double arithmetic in both modes, one rounding to the record type. `M` = {S1, S2, S0, S3} per pixel.
+template <typename R>
+__global__ void __launch_bounds__(256) k_dn_sample_variance(const typename Vec4T<R>::type* __restrict__ M, typename Vec4T<R>::type* __restrict__ C, size_t npix) {
+  using V4 = typename Vec4T<R>::type;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= npix) return;
+  const V4 c = C[i];
+  if (!(c.w >= R(0))) return;   // no data
+  const V4 m = M[i];
+  const double s1 = (double)m.x, s2 = (double)m.y, s0 = (double)m.z, s3 = (double)m.w;
+  const double n_eff = s3 > 0.0 ? s0 * s0 / s3 : 0.0;
+  if (!(n_eff >= 2.0) || !(s1 > 0.0)) return;
+  const double l = 0.212671 * (double)c.x + 0.715160 * (double)c.y + 0.072169 * (double)c.z;
+  const double rel = fmax(0.0, (s2 / s1) * (s0 / s1) - 1.0);   // = S2 S0 / S1^2 - 1, without the square of a tiny S1 underflowing
+  C[i].w = (R)(l * l * rel / (n_eff - 1.0));
+}
+
 // ---- one a-trous iteration ---------------------------------------------------------------------------------------------------------------------------
 // dn_prefilter_tap / dn_tap hold the arithmetic of a tap; the two fetch forms (direct gathers, LDS tile) call them with the same records in the
 // same order, so their results are the same bits.

@@ -1463,10 +1463,9 @@ static __global__ void k_accumulate_camera(uint32_t* c, unsigned long long* tota
 // <= 0.5: every sample lands in its own pixel, so one thread owns a pixel and sums the pass's samples in sample
 // order (deterministic, no atomics). film = per pixel {X, Y, Z sums, filter_weight_sum}.
 // ------------------------------------------------------------------------------------------------------------
-// One sample of the box filter: `w` = its weight, `l` = its radiance record (only read for w > 0). k_film_box and k_film_box_runs
-// both add through this function, so their sums are the same expressions, contracted the same way.
+// L of one sample as the film clamps it: `w` = its weight, `l` = its radiance record (only read for w > 0)
 template <typename R>
-RRT_DEV void film_box_add(const SceneDev<R>& s, R& cr, R& cg, R& cb, R& wsum, R w, const typename Vec4T<R>::type& l) {
+RRT_DEV Rgb<R> film_sample_radiance(const SceneDev<R>& s, R w, const typename Vec4T<R>::type& l) {
   Rgb<R> L;
   if (w > R(0)) L = Rgb<R>(l.x, l.y, l.z);   // dead samples: L = 0, w = 0 (Q2); their record is never initialised
   // integrator/mod.rs:105-122
@@ -1474,6 +1473,13 @@ RRT_DEV void film_box_add(const SceneDev<R>& s, R& cr, R& cg, R& cb, R& wsum, R 
   else if (L.y() < R(-1e-5)) L = Rgb<R>();
   else if (isinf(L.y())) L = Rgb<R>();
   if (L.y() > s.max_sample_luminance) L = L * (s.max_sample_luminance / L.y());
+  return L;
+}
+// One sample of the box filter: `w` = its weight, `l` = its radiance record (only read for w > 0). k_film_box and k_film_box_runs
+// both add through this function, so their sums are the same expressions, contracted the same way.
+template <typename R>
+RRT_DEV void film_box_add(const SceneDev<R>& s, R& cr, R& cg, R& cb, R& wsum, R w, const typename Vec4T<R>::type& l) {
+  const Rgb<R> L = film_sample_radiance(s, w, l);
   cr += (L.r * w) * R(1); cg += (L.g * w) * R(1); cb += (L.b * w) * R(1);  // box filter table weight 1
   wsum += R(1);
 }
@@ -1725,6 +1731,89 @@ template <typename R>
 __global__ void k_aov_merge(const R* src, R* dst, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] += src[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Sample-variance plane beside the film (rrt_render_moments, include/rrt.h): per film pixel {S1 = sum fw y, S2 = sum fw y^2, S0 = sum fw,
+// S3 = sum fw^2} over every sample whose footprint covers the pixel, y = the luminance of L w after the film's own clamps. Kernels of their
+// own, not a template flag on k_film_box / k_film_wide: the kernels a plain frame launches stay the code they are. The film sums go through
+// film_box_add and, for the wide filter, k_film_wide's three accumulation statements after film_sample_radiance. k_film_wide itself keeps its own
+// inline copy of those clamp statements on purpose: re-emitting it around the shared function is a risk to the code plain frames launch, and
+// tests/test_moments.py::test_film_is_the_plain_frames is what holds the two copies to the same film bits.
+// ------------------------------------------------------------------------------------------------------------
+
+// k_film_box with two more running sums per pixel: the same passes, the same sequential sample order in both of its paths, so neither the film
+// nor the moments depend on how the frame was cut into passes. S0 = S3 = the sample count, which the film's weight sum already is.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_film_box_moments(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, R* mom) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  const uint32_t pix = py_ * (uint32_t)s.xres + px_;
+  R* px = film + 4 * (size_t)pix;
+  R* pm = mom + 4 * (size_t)pix;
+  R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];
+  R s1 = pm[0], s2 = pm[1];
+  constexpr uint32_t kBatch = 8;
+  auto add = [&](R w, const typename Vec4T<R>::type& l) {
+    film_box_add(s, cr, cg, cb, wsum, w, l);
+    const R y = film_sample_radiance(s, w, l).y() * w;
+    s1 += y; s2 += y * y;
+  };
+  uint32_t sl = 0;
+  if (pd.npix < (1u << 18))
+  for (; sl + kBatch <= pd.ns; sl += kBatch) {
+    R wb[kBatch];
+    typename Vec4T<R>::type lb[kBatch];
+#pragma unroll
+    for (uint32_t k = 0; k < kBatch; k++) { wb[k] = p.weight[(sl + k) * pd.npix + pl]; lb[k] = p.L[(sl + k) * pd.npix + pl]; }
+#pragma unroll
+    for (uint32_t k = 0; k < kBatch; k++) add(wb[k], lb[k]);
+  }
+  for (; sl < pd.ns; sl++) {
+    const R w = p.weight[sl * pd.npix + pl];
+    typename Vec4T<R>::type l = mk4<R>(R(0), R(0), R(0), R(0));
+    if (w > R(0)) l = p.L[sl * pd.npix + pl];
+    add(w, l);
+  }
+  px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
+  pm[0] = s1; pm[1] = s2; pm[2] = wsum; pm[3] = wsum;
+}
+
+// k_film_wide with the four running sums of the pixel
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_film_wide_moments(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, R* mom, int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint32_t)ew * (uint32_t)eh) return;
+  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
+  R* px = film + 4 * ((size_t)y * (size_t)s.xres + (size_t)x);
+  R* pm = mom + 4 * ((size_t)y * (size_t)s.xres + (size_t)x);
+  R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];
+  R s1 = pm[0], s2 = pm[1], s0 = pm[2], s3 = pm[3];
+  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
+    if (sy < 0 || sy >= ymax) continue;
+    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+      uint32_t pl;
+      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
+      for (uint32_t sl = 0; sl < pd.ns; sl++) {
+        const uint32_t slot = sl * pd.npix + pl;
+        const typename Vec4T<R>::type cs = p.samp[slot];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
+        const R w = p.weight[slot];
+        typename Vec4T<R>::type l = mk4<R>(R(0), R(0), R(0), R(0));
+        if (w > R(0)) l = p.L[slot];
+        const Rgb<R> L = film_sample_radiance(s, w, l);
+        cr += (L.r * w) * fw; cg += (L.g * w) * fw; cb += (L.b * w) * fw;
+        wsum += fw;
+        const R ly = L.y() * w, fy = fw * ly;
+        s1 += fy; s2 += fy * ly; s0 += fw; s3 += fw * fw;
+      }
+    }
+  }
+  px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
+  pm[0] = s1; pm[1] = s2; pm[2] = s0; pm[3] = s3;
 }
 
 }  // namespace rrtd

@@ -122,20 +122,44 @@ void rrt_denoise_defaults(rrt_denoise_params* p) {
   p->sigma_color = 4.0; p->sigma_normal = 32.0; p->sigma_depth = 8.0;
 }
 
-int rrt_denoise(rrt_handle* h, const void* film_xyzw, const rrt_aov* aov, const rrt_denoise_params* params, void* film_out) {
+namespace {
+// rrt_denoise and rrt_denoise_moments: the same checks in the same order under either name; `moments` is looked at only where `with_moments`
+int denoise_entry(const char* fn, rrt_handle* h, const void* film_xyzw, const rrt_aov* aov, bool with_moments, const void* moments, const rrt_denoise_params* params, void* film_out) {
+  const std::string name(fn);
+  auto bad = [&](const char* what) { rrt::set_last_error(name + ": " + what); return (int)RRT_EINVAL; };
   // the caller's own structs first (wrong whichever handle they come with), every pointer before any device work
-  if (!aov) { rrt::set_last_error("rrt_denoise: null plane description (rrt_aov)"); return RRT_EINVAL; }
-  if (!aov->albedo || !aov->normal || !aov->depth) { rrt::set_last_error("rrt_denoise: the filter needs all three planes (albedo, normal or depth is NULL)"); return RRT_EINVAL; }
-  if (aov->mem != RRT_MEM_HOST && aov->mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_denoise: bad mem"); return RRT_EINVAL; }
+  if (!aov) return bad("null plane description (rrt_aov)");
+  if (!aov->albedo || !aov->normal || !aov->depth) return bad("the filter needs all three planes (albedo, normal or depth is NULL)");
+  if (aov->mem != RRT_MEM_HOST && aov->mem != RRT_MEM_DEVICE) return bad("bad mem");
   rrt_denoise_params p;
   rrt_denoise_defaults(&p);
   if (params) p = *params;
-  if (p.iterations < 1 || p.iterations > 6) { rrt::set_last_error("rrt_denoise: iterations must be 1 .. 6"); return RRT_EINVAL; }
-  if (!(p.sigma_normal > 0.0)) { rrt::set_last_error("rrt_denoise: sigma_normal must be > 0"); return RRT_EINVAL; }
-  if (!(p.sigma_depth > 0.0)) { rrt::set_last_error("rrt_denoise: sigma_depth must be > 0"); return RRT_EINVAL; }
-  if (!film_xyzw || !film_out) { rrt::set_last_error("rrt_denoise: null film or film_out"); return RRT_EINVAL; }
-  if (!h) { rrt::set_last_error("rrt_denoise: null handle"); return RRT_EINVAL; }
-  return guarded([&]() { h->impl->denoise(film_xyzw, aov, &p, film_out); });
+  if (p.iterations < 1 || p.iterations > 6) return bad("iterations must be 1 .. 6");
+  if (!(p.sigma_normal > 0.0)) return bad("sigma_normal must be > 0");
+  if (!(p.sigma_depth > 0.0)) return bad("sigma_depth must be > 0");
+  if (!film_xyzw || !film_out) return bad("null film or film_out");
+  if (with_moments && !moments) return bad("null moments plane");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->denoise(film_xyzw, aov, with_moments ? moments : nullptr, &p, film_out); });
+}
+}  // namespace
+
+int rrt_denoise(rrt_handle* h, const void* film_xyzw, const rrt_aov* aov, const rrt_denoise_params* params, void* film_out) {
+  return denoise_entry("rrt_denoise", h, film_xyzw, aov, false, nullptr, params, film_out);
+}
+
+int rrt_denoise_moments(rrt_handle* h, const void* film_xyzw, const rrt_aov* aov, const void* moments, const rrt_denoise_params* params, void* film_out) {
+  return denoise_entry("rrt_denoise_moments", h, film_xyzw, aov, true, moments, params, film_out);
+}
+
+int rrt_render_moments(rrt_handle* h, const int32_t rect[4], int rank, int world, void* film_xyzw, void* moments, int mem, rrt_render_stats* stats) {
+  // every pointer before any device work, each with its own message
+  if (!h) { rrt::set_last_error("rrt_render_moments: null handle"); return RRT_EINVAL; }
+  if (!rect) { rrt::set_last_error("rrt_render_moments: null rect"); return RRT_EINVAL; }
+  if (!film_xyzw) { rrt::set_last_error("rrt_render_moments: null film"); return RRT_EINVAL; }
+  if (!moments) { rrt::set_last_error("rrt_render_moments: null moments plane"); return RRT_EINVAL; }
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_moments: bad mem"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_moments(rect, rank, world, film_xyzw, moments, mem, stats); });
 }
 
 int rrt_set_option(rrt_handle* h, const char* key, double value) {

@@ -54,7 +54,8 @@ struct HandleBase {
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
   virtual void render_end(rrt_render_stats* stats) = 0;
   virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
-  virtual void denoise(const void* film, const rrt_aov* aov, const rrt_denoise_params* p, void* film_out) = 0;
+  virtual void render_moments(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, rrt_render_stats* stats) = 0;
+  virtual void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) = 0;   // moments may be NULL (rrt_denoise)
   virtual void set_option(const std::string& key, double v) = 0;
   // rrt_film_gather (rrt_comm.hip): events on the handle's stream around the frame's collective, so that the frame's statistics can tell
   // the collective (rrt_render_stats::ms_gather) from the render (ms_total) - what a multi-GPU scaling run needs to separate imbalance from xGMI time
@@ -749,7 +750,19 @@ class Handle : public HandleBase {
     const int32_t full[4] = {0, 0, desc_.film.xres, desc_.film.yres};
     render_impl(full, 16, (uint32_t)world, (uint32_t)rank, film_user, film_mem, stats);
   }
-  void render_impl(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, void* film_user, int film_mem, rrt_render_stats* stats) {
+  // ---- rrt_render_moments: the frame of render_rect / render_bands, and the sample-variance plane beside it ----------------------------------
+  // render_impl in its moments mode: the passes of a frame with film_records off (per-slot layout), k_film_box_moments / k_film_wide_moments in
+  // place of the film kernels, a second internal W x H x 4 running-sum buffer merged into the caller's plane by k_aov_merge (a plain +=).
+  void render_moments(const int32_t rect[4], int rank, int world, void* film_user, void* moments_user, int mem, rrt_render_stats* stats) override {
+    if (pending_) throw std::invalid_argument("render_moments: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_moments: bad rank/world");
+    const rrt_film& f = desc_.film;
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_moments: rect outside the film");
+    render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user);
+  }
+  // moments_user: the caller's sample-variance plane (same memory kind as the film) = the frame's moments mode; NULL = a plain frame
+  void render_impl(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, void* film_user, int film_mem, rrt_render_stats* stats, void* moments_user = nullptr) {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
     const rrt_film& f = desc_.film;
@@ -774,6 +787,11 @@ class Handle : public HandleBase {
     // internal full-frame film (zeroed), merged into the caller's buffer at the end
     if (film_.n != W * H * 4) film_.alloc(W * H * 4);
     HIP_CHECK(hipMemsetAsync(film_.p, 0, W * H * 4 * sizeof(R), st_));
+    const bool with_moments = moments_user != nullptr;
+    if (with_moments) {
+      if (moments_.n != W * H * 4) moments_.alloc(W * H * 4);
+      HIP_CHECK(hipMemsetAsync(moments_.p, 0, W * H * 4 * sizeof(R), st_));
+    }
     if (totals_.n == 0) totals_.alloc(12);
     HIP_CHECK(hipMemsetAsync(totals_.p, 0, 12 * sizeof(unsigned long long), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
@@ -825,7 +843,7 @@ class Handle : public HandleBase {
         const uint32_t sgrid = (uint32_t)((nslots + ShadeBlock<R>::n - 1) / ShadeBlock<R>::n);
         hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
         size_t e = tick(0);
-        launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true);
+        launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments);
         tock(e);
         hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
         if (integ == RRT_INT_PATH) {
@@ -932,19 +950,24 @@ class Handle : public HandleBase {
           }
         }
         e = tick(4);
-        if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen)
+        if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
           if constexpr (std::is_same<R, float>::value)
             hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_.p, film_runs_.p, (uint32_t)(ns / 8));
         }
-        else if (!wide_filter) hipLaunchKernelGGL((k_film_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
+        else if (!wide_filter) {
+          const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
+          if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p);
+          else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
+        }
         else {
           // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
           const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
           const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
           const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
           const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-          hipLaunchKernelGGL((k_film_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p,
-                             ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+          const dim3 fg((uint32_t)((en + kBlock - 1) / kBlock));
+          if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+          else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
         }
         tock(e);
         HIP_CHECK(hipGetLastError());
@@ -955,6 +978,7 @@ class Handle : public HandleBase {
     const size_t nfilm = W * H * 4, npx = W * H;
     if (film_mem == RRT_MEM_DEVICE) {
       hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)film_.p, (R*)film_user, npx);
+      if (with_moments) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((nfilm + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)moments_.p, (R*)moments_user, nfilm);
       HIP_CHECK(hipGetLastError());
       if (defer_) { frame_ = std::move(fr); return; }   // render_end() synchronises, checks the error flags and reads the statistics
       HIP_CHECK(hipStreamSynchronize(st_));
@@ -968,6 +992,12 @@ class Handle : public HandleBase {
       HIP_CHECK(hipStreamSynchronize(st_));
       R* dst = (R*)film_user;
       for (size_t i = 0; i < nfilm; i++) dst[i] += tmp[i];
+      if (with_moments) {
+        HIP_CHECK(hipMemcpyAsync(tmp.data(), moments_.p, nfilm * sizeof(R), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipStreamSynchronize(st_));
+        R* dm = (R*)moments_user;
+        for (size_t i = 0; i < nfilm; i++) dm[i] += tmp[i];
+      }
     }
     check_device_errors();
     if (stats) frame_stats(*fr, stats);
@@ -1070,7 +1100,7 @@ class Handle : public HandleBase {
     }
     hipLaunchKernelGGL((k_dn_atrous<R, S>), grid, block, 0, st_, cin, cout, dn_g_.p, dn_p_.p, k);
   }
-  void denoise(const void* film, const rrt_aov* aov, const rrt_denoise_params* p, void* film_out) override {
+  void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) override {
     if (pending_) throw std::invalid_argument("denoise: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
     if (aov->precision != precision()) throw std::invalid_argument("denoise: plane precision must match the handle");
     HIP_CHECK(hipSetDevice(dev_));
@@ -1090,11 +1120,18 @@ class Handle : public HandleBase {
       }
       out = dn_stage_.p;
     }
+    const V4* mom = (const V4*)moments;
+    if (moments && host) {
+      if (!dn_stage_m_.p || dn_stage_m_.n != npix) dn_stage_m_.alloc(npix);
+      HIP_CHECK(hipMemcpyAsync(dn_stage_m_.p, moments, npix * sizeof(V4), hipMemcpyHostToDevice, st_));
+      mom = dn_stage_m_.p;
+    }
     const DnParams<R> k{(int)W, (int)H, (R)p->sigma_color, (R)p->sigma_normal, (R)p->sigma_depth};
     const uint32_t lin = (uint32_t)((npix + 255) / 256);
     const dim3 grid((uint32_t)((W + kDnBX - 1) / kDnBX), (uint32_t)((H + kDnBY - 1) / kDnBY)), block(kDnBX, kDnBY);
     hipLaunchKernelGGL((k_dn_prepare<R>), dim3(lin), dim3(256), 0, st_, in[0], in[1], in[2], in[3], dn_c_[0].p, dn_g_.p, dn_p_.p, npix, p->demodulate != 0 ? 1 : 0);
     hipLaunchKernelGGL((k_dn_moments<R>), grid, block, 0, st_, (const V4*)dn_c_[0].p, dn_c_[1].p, (const V4*)dn_g_.p, k);
+    if (mom) hipLaunchKernelGGL((k_dn_sample_variance<R>), dim3(lin), dim3(256), 0, st_, mom, dn_c_[1].p, npix);   // rrt_denoise_moments
     int cur = 1;
     const bool lds = dn_lds_;
     for (int i = 0; i < p->iterations; i++, cur ^= 1) {
@@ -1254,8 +1291,10 @@ class Handle : public HandleBase {
   DevBuf<unsigned long long> totals_;
   DevBuf<R> film_;       // per pixel: running RGB contribution sum + filter weight sum of the frame being rendered
   DevBuf<R> film_xyz_;   // the same merged to XYZ, staging for a host film
+  DevBuf<R> moments_;    // render_moments: per pixel running {S1, S2, S0, S3} of the frame being rendered (allocated by the first call)
   DevBuf<R> aov_planes_;   // render_aov: running sums of the albedo, normal and depth planes, W x H x 4 each (allocated by the first call)
   DevBuf<typename Vec4T<R>::type> dn_c_[2], dn_g_, dn_p_, dn_stage_;   // denoise: the record planes C (ping-pong), G, P of dfilter.hpp, and the staging of host-memory calls (allocated by the first call)
+  DevBuf<typename Vec4T<R>::type> dn_stage_m_;   // denoise with a moments plane in host memory: its staging
   bool dn_lds_ = true;       // option "dn_lds"
   DevBuf<typename Vec4T<R>::type> aov_rec_a_, aov_rec_b_;   // k_aov_shade's per-slot records {rho.rgb, hit flag}, {n.xyz, t}: sized like pool.L
 
@@ -1849,7 +1888,7 @@ class Handle : public HandleBase {
   // camera ray generation: the dense lean-arithmetic kernels in fp32 (dtraverse_f32.hpp), the generic two-stage kernels (main trace, auxiliary traces; the
   // reference's operation order) in f64 and for what the dense ones do not cover
   // for_render: the queue feeds the integrator (camera rays that miss the root box may be answered here); otherwise every survivor's ray is wanted (rrt_camera_samples)
-  void launch_raygen(const PassDesc& pd, uint32_t grid, double* dims_out, int enqueue, bool for_render = false) {
+  void launch_raygen(const PassDesc& pd, uint32_t grid, double* dims_out, int enqueue, bool for_render = false, bool film_records = true) {
     tt_pass_ok_ = false;
     film_runs_ok_ = false;
     scene_.root_cull = 0u;
@@ -1891,7 +1930,7 @@ class Handle : public HandleBase {
             // film records (option film_records): the path integrator's radiance in record runs, one per camera workgroup (k_film_box_runs). Only where every
             // reader of the per-slot state is known: the box filter of radius 0.5 (write_samp = 0), untextured (no ray differentials per slot), the frame's
             // own passes (not rrt_camera_samples, which reads weight[slot])
-            if (film_records_on_ && for_render && !dims_out && write_samp == 0 && tex_depth_ == 0 && desc_.integrator.type == RRT_INT_PATH) {
+            if (film_records_on_ && film_records && for_render && !dims_out && write_samp == 0 && tex_depth_ == 0 && desc_.integrator.type == RRT_INT_PATH) {
               if (film_runs_.n < n_chunks) { HIP_CHECK(hipStreamSynchronize(st_)); film_runs_.alloc(n_chunks); }
               film_runs_ok_ = true;
             }
