@@ -472,6 +472,36 @@ int rrt_render_moments(rrt_handle*, const int32_t rect[4], int rank, int world, 
 int rrt_denoise_moments(rrt_handle*, const void* film_xyzw, const rrt_aov* aov, const void* moments,
                         const rrt_denoise_params* params /* NULL = defaults */, void* film_out);
 
+/* Error map of a sample-variance plane (no counterpart in the reference). `moments` is a full-frame W*H*4 plane of the handle's precision in `mem`,
+ * as rrt_render_moments leaves it; the rect is cut into 8 x 8-pixel tiles anchored at its origin (width and height multiples of 8), numbered
+ * row-major within the rect, t = ty * (rw / 8) + tx, and tile_error (in `mem`) receives (rh / 8) * (rw / 8) doubles. Per pixel, in double in both
+ * precision modes (resolve_moments of the Python layer):
+ *   n_eff = S0^2 / S3 (0 where S3 <= 0);   m = S1 / S0 (0 where S0 <= 0);   v = max(0, S2 / S0 - m^2) / (n_eff - 1) where n_eff >= 2, else 0.
+ * Per tile: M = sum m, V = sum v over its 64 pixels, E = sqrt(V / 64) / (M / 64) where M > 0, else 0: the RMS standard error of the pixels' means
+ * relative to the tile's mean luminance. No weight carries an absolute radiance scale. The handle is left as it was. Errors: RRT_EINVAL, each with
+ * its own message, for a NULL handle, moments, rect or output, a bad mem and a rect that is not whole tiles (all before any device work), a rect
+ * outside the film, a frame in flight. */
+int rrt_tile_error(rrt_handle*, const void* moments, int mem, const int32_t rect[4], double* tile_error /* in mem */);
+
+/* Adaptive sampling (no counterpart in the reference, which spends nsamp - 1 samples on every pixel): the frame of rrt_render_moments over the rect,
+ * except that an 8 x 8 tile (numbered as rrt_tile_error numbers them) stops taking samples once its error E falls below `threshold`.
+ *   K = min(max_samples ? max_samples : nsamp - 1, nsamp - 1).
+ *   round 0:      sample numbers 1 .. k0, k0 = min(min_samples, K), of every pixel of the rect;
+ *   after a round: every tile still active gets rrt_tile_error's E from this call's own running moments (not from what the caller's plane held). A
+ *                 tile with E < threshold (strict: threshold 0 stops nothing and gives the uniform frame) stops; an all-black tile has E = 0;
+ *   next round:   the next min(batch, K - k) sample numbers of the active tiles only; until no tile is active or k == K.
+ * Halton sample k of a pixel does not depend on nsamp and a pixel's sums are added in sample order, so a tile that stopped at k holds in film and
+ * moments, bit for bit, what a frame with nsamp = k + 1 holds there. film_xyzw and moments are added to (+=) as rrt_render_moments adds them;
+ * tile_samples (in `mem`, may be NULL) receives each tile's final sample count; the statistics hold the sums over the rounds, camera_samples =
+ * 64 * sum tile_samples. The handle is left as it was. Errors: as rrt_render_moments, and RRT_EINVAL before any device work for min_samples < 2,
+ * batch < 1, a negative or NaN threshold, a rect that is not whole tiles; RRT_EUNSUP, the reason named, for the StratifiedSampler (a prefix of a
+ * stratified pixel is not a smaller stratified pixel) and for every pixel filter but the box filter of radius 0.5 (splats across tiles with
+ * different counts). There is no rank / world form and no _begin / _end form. */
+typedef struct rrt_adaptive_params { uint32_t min_samples, batch, max_samples; double threshold; } rrt_adaptive_params;
+void rrt_adaptive_defaults(rrt_adaptive_params*);   /* min_samples 16, batch 16, max_samples 0 (= nsamp - 1), threshold 0.05 */
+int rrt_render_adaptive(rrt_handle*, const int32_t rect[4], const rrt_adaptive_params* params /* NULL = defaults */, void* film_xyzw, void* moments,
+                        uint32_t* tile_samples /* may be NULL */, int mem, rrt_render_stats* stats /* may be NULL */);
+
 /* ---- multi-GPU film reassembly: RCCL over xGMI, one collective per frame ----
  * The reference has one address space: its rayon tiles merge under a lock (Film::merge_film_tile film.rs:248-263, driven from
  * integrator/mod.rs:64-74,133). Across GPUs every rank renders its bands (rrt_render_bands / _begin) into its own device

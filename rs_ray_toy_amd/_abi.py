@@ -163,6 +163,10 @@ class DenoiseParams(C.Structure):
                 ("sigma_depth", C.c_double)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("batch", C.c_uint32), ("max_samples", C.c_uint32), ("threshold", C.c_double)]
+
+
 # every symbol include/rrt.h declares (tests/test_abi.py checks the library exports all of them)
 PROTOTYPES = {
     "rrt_scene_load": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -194,6 +198,9 @@ PROTOTYPES = {
     "rrt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_denoise_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]),
+    "rrt_tile_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
+    "rrt_adaptive_defaults": (None, [C.POINTER(AdaptiveParams)]),
+    "rrt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "rrt_comm_id": (C.c_int, [C.c_void_p]),
     "rrt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

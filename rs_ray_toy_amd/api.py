@@ -240,6 +240,59 @@ class Renderer:
         _check(A.lib().rrt_render_moments(self._h, r, rank, world, film_ptr, moments_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
         return st
 
+    # rrt_render_adaptive: the moments frame with 8 x 8 tiles that stop once their error estimate (rrt_tile_error) is below the threshold
+    def _adaptive_params(self, params):
+        p = A.AdaptiveParams()
+        A.lib().rrt_adaptive_defaults(C.byref(p))
+        for k, v in params.items():
+            if k not in ("min_samples", "batch", "max_samples", "threshold"):
+                raise TypeError(f"render_adaptive: unknown parameter {k}")
+            setattr(p, k, float(v) if k == "threshold" else int(v))
+        return p
+
+    def render_adaptive(self, rect=None, film=None, moments=None, stats=False, **params):
+        """-> (film, moments, tile_samples[, stats]): film and moments as render_moments gives them, tile_samples (rh / 8, rw / 8) uint32 = the
+        samples each 8 x 8 tile of the rect took. params: min_samples, batch, max_samples, threshold (rrt_adaptive_params)."""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        if film is None:
+            film = np.zeros((H, W, 4), self.dtype)
+        if moments is None:
+            moments = np.zeros((H, W, 4), self.dtype)
+        for a in (film, moments):
+            if a.dtype != self.dtype or a.shape != (H, W, 4) or not a.flags.c_contiguous:
+                raise ValueError("render_adaptive: film and moments are C-contiguous (H, W, 4) arrays of the handle's precision")
+        tiles = np.zeros((max(0, rect[3] - rect[1]) // 8, max(0, rect[2] - rect[0]) // 8), np.uint32)
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        p = self._adaptive_params(params)
+        _check(A.lib().rrt_render_adaptive(self._h, r, C.byref(p), film.ctypes.data, moments.ctypes.data, tiles.ctypes.data, A.RRT_MEM_HOST, C.byref(st) if stats else None))
+        return (film, moments, tiles, st) if stats else (film, moments, tiles)
+
+    def render_adaptive_device(self, rect, film_ptr, moments_ptr, tile_samples_ptr=None, stats=True, **params):
+        """The same on device buffers (raw pointers; tile_samples_ptr: (rh / 8) * (rw / 8) uint32, or None)."""
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        p = self._adaptive_params(params)
+        _check(A.lib().rrt_render_adaptive(self._h, r, C.byref(p), film_ptr, moments_ptr, tile_samples_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
+        return st
+
+    # rrt_tile_error: per 8 x 8 tile of the rect, the RMS standard error of the pixels' means relative to the tile's mean luminance
+    def tile_error(self, moments, rect=None):
+        """moments (H, W, 4): the plane of render_moments / render_adaptive -> (rh / 8, rw / 8) float64"""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        if moments.dtype != self.dtype or moments.shape != (H, W, 4) or not moments.flags.c_contiguous:
+            raise ValueError("tile_error: moments is a C-contiguous (H, W, 4) array of the handle's precision")
+        out = np.zeros((max(0, rect[3] - rect[1]) // 8, max(0, rect[2] - rect[0]) // 8), np.float64)
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_tile_error(self._h, moments.ctypes.data, A.RRT_MEM_HOST, r, out.ctypes.data))
+        return out
+
+    def tile_error_device(self, moments_ptr, rect, out_ptr):
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_tile_error(self._h, moments_ptr, A.RRT_MEM_DEVICE, r, out_ptr))
+
     # rrt_denoise: the edge-avoiding wavelet filter over a film, guided by the planes of render_aov (the definition is on the prototype in rrt.h)
     def _denoise_params(self, params):
         p = A.DenoiseParams()
@@ -407,7 +460,17 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     for w in r.warnings:
         print(w, flush=True)
     moments = None
-    if os.environ.get("RRT_DENOISE") and os.environ.get("RRT_DENOISE_MOMENTS", "0") not in ("", "0"):   # as rrt_render: the same frame, and its sample-variance plane
+    with_moments = bool(os.environ.get("RRT_DENOISE")) and os.environ.get("RRT_DENOISE_MOMENTS", "0") not in ("", "0")
+    if os.environ.get("RRT_ADAPTIVE"):   # as rrt_render: rrt_render_adaptive in the frame's place
+        params = {"threshold": float(os.environ["RRT_ADAPTIVE"])}
+        for key, var in (("min_samples", "RRT_ADAPTIVE_MIN"), ("batch", "RRT_ADAPTIVE_BATCH")):
+            if os.environ.get(var):
+                params[key] = int(os.environ[var])
+        film, plane, _, st = r.render_adaptive(stats=True, **params)
+        moments = plane if with_moments else None
+        W, H = scene.resolution
+        print(f"{st.camera_samples} of {W * H * max(0, scene.desc.sampler.samples_per_pixel - 1)} camera samples taken (adaptive)")
+    elif with_moments:   # as rrt_render: the same frame, and its sample-variance plane
         film, moments, st = r.render_moments(stats=True)
     else:
         film, st = r.render(stats=True)

@@ -98,10 +98,36 @@ int main(int argc, char** argv) {
   int rc = rrt_scene_load(argv[1], flags, 0x853C49E6748FEA9Bull, &scene);
   if (rc != RRT_OK) return fail("rrt_scene_load", rc);
   for (size_t i = 0; i < rrt_scene_warning_count(scene); i++) std::fprintf(stderr, "%s\n", rrt_scene_warning(scene, i));
-  const rrt_scene_desc* desc = rrt_scene_desc_of(scene);   // opaque here: handed to rrt_create as it is
+  const rrt_scene_desc* desc = rrt_scene_desc_of(scene);   // handed to rrt_create as it is (RRT_ADAPTIVE reads its sample count)
   int32_t W = 0, H = 0;
   double film_scale = 1.0;
   (void)rrt_scene_film(scene, &W, &H, &film_scale);
+  // RRT_ADAPTIVE=<threshold>: rrt_render_adaptive in the frame's place (RRT_ADAPTIVE_MIN, RRT_ADAPTIVE_BATCH: its min_samples and batch); film and
+  // moments are consistent per pixel, so RRT_DENOISE / RRT_DENOISE_MOMENTS take them as they take a uniform frame's. Looked at before
+  // RRT_DENOISE_MOMENTS: the adaptive frame is rendered on one GPU and has the plane. A value that is not a number is refused, not read as 0
+  // (which would quietly give the uniform frame).
+  const char* env_ad = std::getenv("RRT_ADAPTIVE");
+  const bool adaptive = env_ad && *env_ad;
+  rrt_adaptive_params adaptive_params;
+  rrt_adaptive_defaults(&adaptive_params);
+  if (adaptive) {
+    char* end = nullptr;
+    adaptive_params.threshold = std::strtod(env_ad, &end);
+    bool ok = end != env_ad && *end == '\0';
+    const char* env_min = std::getenv("RRT_ADAPTIVE_MIN");
+    const char* env_batch = std::getenv("RRT_ADAPTIVE_BATCH");
+    if (ok && env_min && *env_min) { const unsigned long v = std::strtoul(env_min, &end, 10); ok = end != env_min && *end == '\0' && v <= 0xfffffffful; adaptive_params.min_samples = (uint32_t)v; }
+    if (ok && env_batch && *env_batch) { const unsigned long v = std::strtoul(env_batch, &end, 10); ok = end != env_batch && *end == '\0' && v <= 0xfffffffful; adaptive_params.batch = (uint32_t)v; }
+    if (!ok) {
+      std::fprintf(stderr, "rrt_render: RRT_ADAPTIVE, RRT_ADAPTIVE_MIN and RRT_ADAPTIVE_BATCH must be numbers (threshold, min_samples, batch)\n");
+      rrt_scene_free(scene);
+      return 2;
+    }
+    if (n_gpus > 1) {
+      std::fprintf(stderr, "rrt_render: RRT_ADAPTIVE runs on one GPU: device 0 renders the whole frame\n");
+      n_gpus = 1;
+    }
+  }
   const char* env_dn_path = std::getenv("RRT_DENOISE");
   const char* env_dn_mom = std::getenv("RRT_DENOISE_MOMENTS");
   bool with_moments = env_dn_path && *env_dn_path && env_dn_mom && *env_dn_mom && std::strcmp(env_dn_mom, "0") != 0;   // on for any value but "" and "0", as deploy_render reads it
@@ -135,7 +161,7 @@ int main(int argc, char** argv) {
     }
   }
   unsigned long long rays_generated = 0;
-  if (with_moments) {   // one GPU: the whole frame and its moments plane in one call
+  if (with_moments || adaptive) {   // one GPU: the whole frame and its moments plane in one call
     if (hipSetDevice(0) != hipSuccess || hipMalloc(&moments_dev, film_bytes) != hipSuccess || hipMemset(moments_dev, 0, film_bytes) != hipSuccess) {
       std::fprintf(stderr, "rrt_render: cannot allocate the %zu-byte moments plane on device 0\n", film_bytes);
       cleanup();
@@ -143,8 +169,15 @@ int main(int argc, char** argv) {
     }
     const int32_t rect[4] = {0, 0, W, H};
     rrt_render_stats st;
-    rc = rrt_render_moments(handles[0], rect, 0, 1, films[0], moments_dev, RRT_MEM_DEVICE, &st);
-    if (rc != RRT_OK) { const int e = fail("rrt_render_moments", rc); cleanup(); return e; }
+    if (adaptive) {
+      rc = rrt_render_adaptive(handles[0], rect, &adaptive_params, films[0], moments_dev, nullptr, RRT_MEM_DEVICE, &st);
+      if (rc != RRT_OK) { const int e = fail("rrt_render_adaptive", rc); cleanup(); return e; }
+      const unsigned long long spp = desc->sampler.samples_per_pixel > 1 ? (unsigned long long)desc->sampler.samples_per_pixel - 1ull : 0ull;
+      std::printf("%llu of %llu camera samples taken (adaptive)\n", (unsigned long long)st.camera_samples, (unsigned long long)W * (unsigned long long)H * spp);
+    } else {
+      rc = rrt_render_moments(handles[0], rect, 0, 1, films[0], moments_dev, RRT_MEM_DEVICE, &st);
+      if (rc != RRT_OK) { const int e = fail("rrt_render_moments", rc); cleanup(); return e; }
+    }
     rays_generated = st.camera_rays;
   } else {
     // every GPU renders its interleaved bands at the same time (the calls only enqueue), then one collective, then wait

@@ -525,6 +525,16 @@ RRT_DEV void pass_pixel(const PassDesc& pd, uint32_t lin, uint32_t* px, uint32_t
   *py = (uint32_t)pd.ry0 + ((row / pd.band_h) * pd.n_ranks + pd.rank) * pd.band_h + row % pd.band_h;
 }
 
+// Listed passes (rrt_render_adaptive): the pixel group is a list of kTileW x kTileH tiles of the rect, numbered row-major from the rect's origin
+// (tile t = ty * (rw / kTileW) + tx). Pixel `lin` of the pass (pd.pix_begin + pl, as pass_pixel counts) is pixel `lin % 64` of tile list[lin / 64],
+// row-major inside the tile - the enumeration of a tiled pass with the tile number looked up instead of counted. The slot layout stays
+// sl * npix + pl. A listed pass has no bands (band_h = 2^30, one rank) and pd.tiled = 1.
+RRT_DEV void list_pixel(const PassDesc& pd, const uint32_t* list, uint32_t lin, uint32_t* px, uint32_t* py) {
+  const uint32_t tile = list[lin / (kTileW * kTileH)], within = lin % (kTileW * kTileH), tiles_per_row = (uint32_t)pd.rw / kTileW;
+  *px = (uint32_t)pd.rx0 + (tile % tiles_per_row) * kTileW + within % kTileW;
+  *py = (uint32_t)pd.ry0 + (tile / tiles_per_row) * kTileH + within / kTileW;
+}
+
 // Stage 1 (every slot): Halton index + dims 0..3, film point, lens sample, and the *main* lens trace
 // (generate_ray, camera.rs:534-580). About 70 % of the samples die here (lens samples are drawn in [0.5,1.5)^2,
 // Q5); the survivors are compacted into q_next so that stage 2 runs with full lanes. The main ray waits in the
@@ -566,6 +576,37 @@ __global__ void __launch_bounds__(kBlock) k_raygen(SceneDev<R> s, Pools<R> p, Pa
     if (dbg_dims) {
       double* dd = dbg_dims + 5 * (size_t)(pl * pd.ns + sl);   // [pixel][sample]
       dd[0] = d0; dd[1] = d1; dd[2] = d2; dd[3] = d3; dd[4] = s.sampler_type == 1u ? d4 : halton_dim(s, index, 4);
+    }
+  }
+  __shared__ uint32_t push_lds[kBlock / 64 + 1];
+  const uint32_t q = block_push(&p.counters[C_NEXT], alive, push_lds);
+  if (alive) p.q_next[q] = QEnt{slot, 0u, 0u, 0u};
+}
+
+// k_raygen over a listed pass (list_pixel): the same statements per slot, HaltonSampler only (rrt_render_adaptive refuses the StratifiedSampler)
+// and without the debug dimensions. A kernel of its own, so that the kernel every other pass launches stays the code it is.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_raygen_list(SceneDev<R> s, Pools<R> p, PassDesc pd, const uint32_t* list) {
+  const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t total = pd.npix * pd.ns;
+  bool alive = false;
+  if (slot < total) {
+    const uint32_t pl = slot % pd.npix, sl = slot / pd.npix;
+    uint32_t px, py;
+    list_pixel(pd, list, pd.pix_begin + pl, &px, &py);
+    const uint32_t sample_num = pd.s_begin + sl;
+    const uint32_t index = halton_pixel_offset(s, px, py) + sample_num * s.stride;
+    const double d0 = halton_dim(s, index, 0), d1 = halton_dim(s, index, 1), d2 = halton_cam_dim(s, index, 0), d3 = halton_cam_dim(s, index, 1);
+    const R pfx = (R)px + to_real<R>(d0), pfy = (R)py + to_real<R>(d1);
+    const R lx = to_real<R>(d2) + R(0.5), ly = to_real<R>(d3) + R(0.5);  // Q5
+    RayT<R> ray;
+    const R w = generate_ray(s, pfx, pfy, lx, ly, &ray);
+    alive = w != R(0);
+    p.hindex[slot] = index;
+    p.weight[slot] = alive ? w : R(0);
+    p.samp[slot] = mk4<R>(pfx, pfy, lx, ly);
+    if (alive) {
+      store_ray<R>(p.nray_o, p.nray_d, slot, ray.o, V3<R>(), ray.d, Const<R>::inf, -1);
     }
   }
   __shared__ uint32_t push_lds[kBlock / 64 + 1];
@@ -1814,6 +1855,105 @@ __global__ void __launch_bounds__(kBlock) k_film_wide_moments(SceneDev<R> s, Poo
   }
   px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
   pm[0] = s1; pm[1] = s2; pm[2] = s0; pm[3] = s3;
+}
+
+// k_film_box_moments over a listed pass (list_pixel): the same running sums, added through the same functions in the same sample order in both of its
+// paths, so a pixel that a listed pass continues holds what a longer rect pass would have left in it.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_film_box_moments_list(SceneDev<R> s, Pools<R> p, PassDesc pd, const uint32_t* list, R* film, R* mom) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  list_pixel(pd, list, pd.pix_begin + pl, &px_, &py_);
+  const uint32_t pix = py_ * (uint32_t)s.xres + px_;
+  R* px = film + 4 * (size_t)pix;
+  R* pm = mom + 4 * (size_t)pix;
+  R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];
+  R s1 = pm[0], s2 = pm[1];
+  constexpr uint32_t kBatch = 8;
+  auto add = [&](R w, const typename Vec4T<R>::type& l) {
+    film_box_add(s, cr, cg, cb, wsum, w, l);
+    const R y = film_sample_radiance(s, w, l).y() * w;
+    s1 += y; s2 += y * y;
+  };
+  uint32_t sl = 0;
+  if (pd.npix < (1u << 18))
+  for (; sl + kBatch <= pd.ns; sl += kBatch) {
+    R wb[kBatch];
+    typename Vec4T<R>::type lb[kBatch];
+#pragma unroll
+    for (uint32_t k = 0; k < kBatch; k++) { wb[k] = p.weight[(sl + k) * pd.npix + pl]; lb[k] = p.L[(sl + k) * pd.npix + pl]; }
+#pragma unroll
+    for (uint32_t k = 0; k < kBatch; k++) add(wb[k], lb[k]);
+  }
+  for (; sl < pd.ns; sl++) {
+    const R w = p.weight[sl * pd.npix + pl];
+    typename Vec4T<R>::type l = mk4<R>(R(0), R(0), R(0), R(0));
+    if (w > R(0)) l = p.L[sl * pd.npix + pl];
+    add(w, l);
+  }
+  px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
+  pm[0] = s1; pm[1] = s2; pm[2] = wsum; pm[3] = wsum;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Error map of a moments plane (rrt_tile_error, include/rrt.h) and the stopping rule of rrt_render_adaptive.
+// ------------------------------------------------------------------------------------------------------------
+static_assert(kTileW * kTileH == 64u, "k_tile_error: one wave per tile, one lane per pixel");
+constexpr uint32_t kTeBlock = 256;   // four tiles per workgroup
+
+// One wave per tile, one lane per pixel: one 128-bit load of the pixel's {S1, S2, S0, S3} (a tile row is kTileW consecutive records), the pixel's
+// mean and variance of the mean in double (api.py resolve_moments, statement by statement and never contracted), the two sums over the wave
+// by a butterfly of cross-lane shuffles (a fixed order), one store by lane 0. `list` = the tiles to measure (NULL: tiles 0 .. n - 1);
+// err is indexed by tile number.
+template <typename R>
+__global__ void __launch_bounds__(kTeBlock) k_tile_error(const typename Vec4T<R>::type* mom, uint32_t xres, int32_t rx0, int32_t ry0, uint32_t tiles_per_row,
+                                                         const uint32_t* list, uint32_t n, double* err) {
+#pragma clang fp contract(off)
+  const uint32_t i = blockIdx.x * (kTeBlock / 64u) + threadIdx.x / 64u, lane = threadIdx.x % 64u;
+  if (i >= n) return;   // (the whole wave)
+  const uint32_t tile = list ? list[i] : i;
+  const uint32_t x = (uint32_t)rx0 + (tile % tiles_per_row) * kTileW + lane % kTileW, y = (uint32_t)ry0 + (tile / tiles_per_row) * kTileH + lane / kTileW;
+  const typename Vec4T<R>::type rec = mom[(size_t)y * (size_t)xres + (size_t)x];
+  const double s1 = (double)rec.x, s2 = (double)rec.y, s0 = (double)rec.z, s3 = (double)rec.w;
+  const double n_eff = s3 > 0.0 ? s0 * s0 / s3 : 0.0;
+  const double m = s0 > 0.0 ? s1 / s0 : 0.0;
+  double v = 0.0;
+  if (n_eff >= 2.0) v = fmax(0.0, s2 / s0 - m * m) / (n_eff - 1.0);
+  double M = m, V = v;
+  for (int o = 32; o > 0; o >>= 1) { M += __shfl_xor(M, o, 64); V += __shfl_xor(V, o, 64); }
+  if (lane == 0u) err[tile] = M > 0.0 ? sqrt(V / 64.0) / (M / 64.0) : 0.0;
+}
+
+// The stopping rule, one workgroup: the tiles of list_in (NULL: 0 .. n - 1), kSelBlock at a time in list order. A tile with err < threshold
+// (strict: threshold 0 stops nothing), and every tile when `last`, stops: tile_samples[tile] = k. The others are written to list_out in the
+// order they came in - their position is the running count plus a ballot / popcount scan over the workgroup, no atomic append - so an ascending
+// list stays ascending and two runs issue the same passes. *count_out = the tiles kept.
+constexpr uint32_t kSelBlock = 1024;
+static __global__ void __launch_bounds__(kSelBlock) k_tile_select(const uint32_t* list_in, uint32_t n, const double* err, double threshold, uint32_t k, int last,
+                                                                  uint32_t* list_out, uint32_t* count_out, uint32_t* tile_samples) {
+  __shared__ uint32_t wave_n[kSelBlock / 64u];
+  const uint32_t tid = threadIdx.x, lane = tid % 64u, wave = tid / 64u;
+  uint32_t base = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += kSelBlock) {
+    const uint32_t i = i0 + tid;
+    bool keep = false;
+    uint32_t tile = 0;
+    if (i < n) {
+      tile = list_in ? list_in[i] : i;
+      keep = !last && !(err[tile] < threshold);
+      if (!keep) tile_samples[tile] = k;
+    }
+    const unsigned long long b = __ballot(keep);
+    if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t off = base, tot = 0;
+    for (uint32_t w = 0; w < kSelBlock / 64u; w++) { if (w < wave) off += wave_n[w]; tot += wave_n[w]; }
+    if (keep) list_out[off + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = tile;
+    base += tot;
+    __syncthreads();
+  }
+  if (tid == 0u) *count_out = base;
 }
 
 }  // namespace rrtd

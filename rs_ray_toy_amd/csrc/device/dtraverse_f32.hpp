@@ -1163,6 +1163,16 @@ static __global__ void __launch_bounds__(kBlock) k_pixel_offsets(SceneDev<float>
   p.pix_off[2 * pl + 1] = (py << 16) | px;
 }
 
+// the same for a listed pass (list_pixel, dkernels.hpp): all that k_raygen_main_f32 needs to run over a list of tiles
+static __global__ void __launch_bounds__(kBlock) k_pixel_offsets_list(SceneDev<float> s, Pools<float> p, PassDesc pd, const uint32_t* list) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px, py;
+  list_pixel(pd, list, pd.pix_begin + pl, &px, &py);
+  p.pix_off[2 * pl] = halton_pixel_offset(s, px, py);
+  p.pix_off[2 * pl + 1] = (py << 16) | px;
+}
+
 }  // namespace rrtd
 
 // ------------------------------------------------------------------------------------------------------------

@@ -162,6 +162,49 @@ int rrt_render_moments(rrt_handle* h, const int32_t rect[4], int rank, int world
   return guarded([&]() { h->impl->render_moments(rect, rank, world, film_xyzw, moments, mem, stats); });
 }
 
+void rrt_adaptive_defaults(rrt_adaptive_params* p) {
+  if (!p) return;
+  p->min_samples = 16; p->batch = 16; p->max_samples = 0;
+  p->threshold = 0.05;
+}
+
+namespace {
+// whole kTileW x kTileH tiles anchored at the rect's origin (host arithmetic: asked before any device work)
+bool whole_tiles(const int32_t rect[4]) {
+  const int64_t rw = (int64_t)rect[2] - rect[0], rh = (int64_t)rect[3] - rect[1];
+  return rw > 0 && rh > 0 && rw % (int64_t)rrtd::kTileW == 0 && rh % (int64_t)rrtd::kTileH == 0;
+}
+}  // namespace
+
+int rrt_tile_error(rrt_handle* h, const void* moments, int mem, const int32_t rect[4], double* tile_error) {
+  // the caller's own arguments first, every one before any device work and each with its own message
+  if (!moments) { rrt::set_last_error("rrt_tile_error: null moments plane"); return RRT_EINVAL; }
+  if (!rect) { rrt::set_last_error("rrt_tile_error: null rect"); return RRT_EINVAL; }
+  if (!tile_error) { rrt::set_last_error("rrt_tile_error: null output"); return RRT_EINVAL; }
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_tile_error: bad mem"); return RRT_EINVAL; }
+  if (!whole_tiles(rect)) { rrt::set_last_error("rrt_tile_error: the rect's width and height must be positive multiples of 8 (whole 8 x 8 tiles)"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_tile_error: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->tile_error(moments, mem, rect, tile_error); });
+}
+
+int rrt_render_adaptive(rrt_handle* h, const int32_t rect[4], const rrt_adaptive_params* params, void* film_xyzw, void* moments, uint32_t* tile_samples, int mem,
+                        rrt_render_stats* stats) {
+  // the caller's own arguments first (wrong whichever handle they come with), every one before any device work and each with its own message
+  if (!rect) { rrt::set_last_error("rrt_render_adaptive: null rect"); return RRT_EINVAL; }
+  if (!film_xyzw) { rrt::set_last_error("rrt_render_adaptive: null film"); return RRT_EINVAL; }
+  if (!moments) { rrt::set_last_error("rrt_render_adaptive: null moments plane"); return RRT_EINVAL; }
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_adaptive: bad mem"); return RRT_EINVAL; }
+  rrt_adaptive_params p;
+  rrt_adaptive_defaults(&p);
+  if (params) p = *params;
+  if (p.min_samples < 2) { rrt::set_last_error("rrt_render_adaptive: min_samples must be >= 2 (a variance needs two samples)"); return RRT_EINVAL; }
+  if (p.batch < 1) { rrt::set_last_error("rrt_render_adaptive: batch must be >= 1"); return RRT_EINVAL; }
+  if (!(p.threshold >= 0.0)) { rrt::set_last_error("rrt_render_adaptive: threshold must be >= 0 and not NaN"); return RRT_EINVAL; }
+  if (!whole_tiles(rect)) { rrt::set_last_error("rrt_render_adaptive: the rect's width and height must be positive multiples of 8 (whole 8 x 8 tiles)"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_render_adaptive: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_adaptive(rect, &p, film_xyzw, moments, tile_samples, mem, stats); });
+}
+
 int rrt_set_option(rrt_handle* h, const char* key, double value) {
   if (!h || !key) { rrt::set_last_error("rrt_set_option: null argument"); return RRT_EINVAL; }
   return guarded([&]() { h->impl->set_option(key, value); });

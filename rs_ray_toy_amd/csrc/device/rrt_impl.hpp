@@ -55,6 +55,8 @@ struct HandleBase {
   virtual void render_end(rrt_render_stats* stats) = 0;
   virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
   virtual void render_moments(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, rrt_render_stats* stats) = 0;
+  virtual void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film, void* moments, uint32_t* tile_samples, int mem, rrt_render_stats* stats) = 0;
+  virtual void tile_error(const void* moments, int mem, const int32_t rect[4], double* tile_error) = 0;
   virtual void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) = 0;   // moments may be NULL (rrt_denoise)
   virtual void set_option(const std::string& key, double v) = 0;
   // rrt_film_gather (rrt_comm.hip): events on the handle's stream around the frame's collective, so that the frame's statistics can tell
@@ -766,14 +768,10 @@ class Handle : public HandleBase {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
     const rrt_film& f = desc_.film;
-    // k_film_box is the closed form for the default box filter (radius exactly 0.5: every sample lands in its own pixel with weight 1);
-    // a smaller radius leaves samples near the pixel borders in no pixel at all, a larger one splats: both take the general kernel
-    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
     if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
     if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
       throw std::invalid_argument("render rect outside the film");
     const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    const size_t W = (size_t)f.xres, H = (size_t)f.yres;
     size_t rh_all = (size_t)(rect[3] - rect[1]);
     if (n_ranks > 1) {  // number of rows of this rank's bands
       size_t rows = 0;
@@ -784,10 +782,27 @@ class Handle : public HandleBase {
     const uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;  // samples 1 .. nsamp-1 (Q1)
     if (rpix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }   // a rank that owns no band (world > yres / 16): nothing to add to the caller's film
 
-    // internal full-frame film (zeroed), merged into the caller's buffer at the end
+    const bool with_moments = moments_user != nullptr;
+    frame_setup(with_moments, rpix * (size_t)std::max<uint64_t>(s_total, 1));
+    const bool timing = stats != nullptr || (defer_ && frame_stats_);
+    auto fr = std::make_unique<FrameRec>();
+    fr->timing = timing; fr->camera_samples = (uint64_t)rpix * s_total;
+    if (timing) { fr->ev_begin = fr->make(); fr->ev_end = fr->make(); HIP_CHECK(hipEventRecord(fr->ev_begin, st_)); }
+    rect_passes(rect, band_h, n_ranks, rank, rw, rh, 0, s_total, with_moments, *fr);
+    if (timing) HIP_CHECK(hipEventRecord(fr->ev_end, st_));
+    // merge into the caller's film (+=)
+    const bool wait = !(film_mem == RRT_MEM_DEVICE && defer_);
+    merge_out(film_user, moments_user, film_mem, wait);
+    if (!wait) { frame_ = std::move(fr); return; }   // render_end() synchronises, checks the error flags and reads the statistics
+    check_device_errors();
+    if (stats) frame_stats(*fr, stats);
+  }
+  // internal full-frame film (zeroed; merged into the caller's buffer at the end), the moments buffer beside it in a moments frame, the statistics'
+  // totals, and pools for `want` slots or what max_paths allows
+  void frame_setup(bool with_moments, size_t want) {
+    const size_t W = (size_t)desc_.film.xres, H = (size_t)desc_.film.yres;
     if (film_.n != W * H * 4) film_.alloc(W * H * 4);
     HIP_CHECK(hipMemsetAsync(film_.p, 0, W * H * 4 * sizeof(R), st_));
-    const bool with_moments = moments_user != nullptr;
     if (with_moments) {
       if (moments_.n != W * H * 4) moments_.alloc(W * H * 4);
       HIP_CHECK(hipMemsetAsync(moments_.p, 0, W * H * 4 * sizeof(R), st_));
@@ -796,7 +811,7 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemsetAsync(totals_.p, 0, 12 * sizeof(unsigned long long), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
 
-    size_t P = std::min(max_paths_, std::max<size_t>(rpix * (size_t)std::max<uint64_t>(s_total, 1), 64));
+    size_t P = std::min(max_paths_, std::max<size_t>(want, 64));
     if ((desc_.integrator.type == RRT_INT_DIRECT || desc_.integrator.type == RRT_INT_DEBUG) && (has_transmissive_ || tex_depth_ > 0) && desc_.integrator.max_depth > kTreeMax) {
       // k_direct_tree keeps (max_depth - kTreeMax) overflow frames per slot of a pass: a quarter of the free memory at most
       size_t free_b = 0, total_b = 0;
@@ -811,11 +826,32 @@ class Handle : public HandleBase {
         HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));   // the census ran the camera kernels
       }
     }
+  }
+  // the passes of sample numbers 1 + s_lo .. s_hi of a rect's (or its bands') rw x rh pixels: pixel groups and sample chunks from what the pools hold
+  void rect_passes(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_lo, uint64_t s_hi, bool with_moments, FrameRec& fr) {
+    const size_t rpix = rw * rh;
     const size_t group = std::min(rpix, cap_);                           // pixels per group
     const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);         // samples per pass
-    const bool timing = stats != nullptr || (defer_ && frame_stats_);
-    auto fr = std::make_unique<FrameRec>();
-    fr->timing = timing; fr->camera_samples = (uint64_t)rpix * s_total;
+    for (size_t g0 = 0; g0 < rpix && s_hi > s_lo; g0 += group) {
+      const size_t npix = std::min(group, rpix - g0);
+      for (uint64_t sb = s_lo; sb < s_hi; sb += s_chunk) {
+        const uint64_t ns = std::min<uint64_t>(s_chunk, s_hi - sb);
+        // tile order of the pixels (PassDesc::tiled) where the rect allows it: whole kTileW x kTileH tiles
+        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
+        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, rank, tiled};
+        run_pass(pd, nullptr, rect, with_moments, fr);
+      }
+    }
+  }
+  // one pass: camera kernels, the integrator's launches, the film kernel. list: the tiles of a listed pass (list_pixel; box filter of radius 0.5 and
+  // moments only, no tile trees, no film records), NULL for a pass over the rect's own pixel grid
+  void run_pass(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, FrameRec& fr_ref) {
+    FrameRec* const fr = &fr_ref;
+    const rrt_film& f = desc_.film;
+    // k_film_box is the closed form for the default box filter (radius exactly 0.5: every sample lands in its own pixel with weight 1);
+    // a smaller radius leaves samples near the pixel borders in no pixel at all, a larger one splats: both take the general kernel
+    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
+    const bool timing = fr->timing;
     auto& evs = fr->evs;
     auto tick = [&](int cat, hipStream_t stream = nullptr) {
       if (!timing) return (size_t)0;
@@ -825,162 +861,158 @@ class Handle : public HandleBase {
       return evs.size() - 1;
     };
     auto tock = [&](size_t id, hipStream_t stream = nullptr) { if (timing) HIP_CHECK(hipEventRecord(evs[id].second.second, stream ? stream : st_)); };
-    if (timing) { fr->ev_begin = fr->make(); fr->ev_end = fr->make(); HIP_CHECK(hipEventRecord(fr->ev_begin, st_)); }
     uint64_t& n_closest_launch = fr->n_closest_launch;
     uint64_t& n_any_launch = fr->n_any_launch;
     const int integ = desc_.integrator.type;
     const int max_depth = desc_.integrator.max_depth;
-
-    for (size_t g0 = 0; g0 < rpix && s_total > 0; g0 += group) {
-      const size_t npix = std::min(group, rpix - g0);
-      for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
-        const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
-        // tile order of the pixels (PassDesc::tiled) where the rect allows it: whole kTileW x kTileH tiles
-        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
-        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, rank, tiled};
-        const size_t nslots = npix * (size_t)ns;
-        const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
-        const uint32_t sgrid = (uint32_t)((nslots + ShadeBlock<R>::n - 1) / ShadeBlock<R>::n);
-        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
-        size_t e = tick(0);
-        launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments);
+    const size_t npix = pd.npix;
+    const uint64_t ns = pd.ns;
+    const size_t nslots = npix * (size_t)ns;
+    const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
+    const uint32_t sgrid = (uint32_t)((nslots + ShadeBlock<R>::n - 1) / ShadeBlock<R>::n);
+    hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+    size_t e = tick(0);
+    launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments, list);
+    tock(e);
+    hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
+    if (integ == RRT_INT_PATH) {
+      // bounce b: closest -> shade (NEE + BSDF sample + RR) -> shadow rays; paths live while bounces < max_depth
+      const bool overlap = two_shadow_queues() && shadow_buf_[1][0] && !count_traversal_ && max_depth > 1;
+      auto use_shadow_queue = [&](int k) {
+        pool_.sray_o = shadow_buf_[k][0]; pool_.sray_d = shadow_buf_[k][1]; pool_.sld = shadow_buf_[k][2];
+        pool_.shadow_count = counters_.p + (k ? C_SHADOW2 : C_SHADOW);
+      };
+      for (int b = 0; b < max_depth; b++) {
+        hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
+        e = tick(1);
+        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, b == 0);
+        tock(e); n_closest_launch++;
+        if (b == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
+        if (overlap) {
+          use_shadow_queue(b & 1);
+          if (b > 1) HIP_CHECK(hipStreamWaitEvent(st_, ev_shadow_[b & 1], 0));   // shading refills the queue the shadow launch of bounce b - 2 read
+        }
+        scene_.use_shadow_tabs = use_shadow_lists() ? 1u : 0u;
+        scene_.horizon = (horizon_on_ && horizon_.n) ? horizon_.p : nullptr; scene_.hz_tau = horizon_tau_.p; scene_.hz_axis = hz_axis_;   // (counting frames too: the cull is geometry, not a kernel's arithmetic - their node counters then hold the rays that are traced)
+        e = tick(3);
+        if (tex_depth_ > 0) hipLaunchKernelGGL((k_shade_path<R, 4, true>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
+        else if (has_translucent_) hipLaunchKernelGGL((k_shade_path<R, 4>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
+        else if (shade_kinds_ == kKindsLambert) {
+          constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsLambert>();
+          const dim3 g(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u));
+          if (area_lights_ || shade_kinds_ == kAllKinds) hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, true>), g, dim3(kB), 0, st_, scene_, pool_);
+          else hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, false>), g, dim3(kB), 0, st_, scene_, pool_);
+        }
+        else if (shade_kinds_ == kKindsGlossy) {
+          constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsGlossy>();
+          hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsGlossy>), dim3(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u)), dim3(kB), 0, st_, scene_, pool_);
+        }
+        else hipLaunchKernelGGL((k_shade_path<R, 2>), dim3(std::min(sgrid, 16384u)), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_);
         tock(e);
-        hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
-        if (integ == RRT_INT_PATH) {
-          // bounce b: closest -> shade (NEE + BSDF sample + RR) -> shadow rays; paths live while bounces < max_depth
-          const bool overlap = two_shadow_queues() && shadow_buf_[1][0] && !count_traversal_ && max_depth > 1;
-          auto use_shadow_queue = [&](int k) {
-            pool_.sray_o = shadow_buf_[k][0]; pool_.sray_d = shadow_buf_[k][1]; pool_.sld = shadow_buf_[k][2];
-            pool_.shadow_count = counters_.p + (k ? C_SHADOW2 : C_SHADOW);
-          };
-          for (int b = 0; b < max_depth; b++) {
-            hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
-            e = tick(1);
-            launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, b == 0);
-            tock(e); n_closest_launch++;
-            if (b == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
-            if (overlap) {
-              use_shadow_queue(b & 1);
-              if (b > 1) HIP_CHECK(hipStreamWaitEvent(st_, ev_shadow_[b & 1], 0));   // shading refills the queue the shadow launch of bounce b - 2 read
-            }
+        if (scene_.horizon) hipLaunchKernelGGL(k_accumulate_sky, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
+        if (overlap) {
+          HIP_CHECK(hipEventRecord(ev_shade_, st_));
+          HIP_CHECK(hipStreamWaitEvent(st2_, ev_shade_, 0));
+          hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st2_, pool_.shadow_count, totals_.p);
+          e = tick(2, st2_);
+          launch_shadow(grid, st2_);
+          tock(e, st2_); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st2_, counters_.p, 6 + (b & 1));   // this shadow queue + the any-hit work counter
+          HIP_CHECK(hipEventRecord(ev_shadow_[b & 1], st2_));
+          swap_queues();
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 5);    // active <- next, closest work counter
+        } else {
+          hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st_, pool_.shadow_count, totals_.p);
+          e = tick(2);
+          launch_shadow(grid);
+          tock(e); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
+          swap_queues();
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);
+        }
+      }
+      if (overlap) {   // the film kernel reads L
+        HIP_CHECK(hipStreamWaitEvent(st_, ev_shadow_[(max_depth - 1) & 1], 0));
+        use_shadow_queue(0);
+      }
+    } else if (integ == RRT_INT_DIRECT || integ == RRT_INT_DEBUG) {
+      if (has_transmissive_ || tex_depth_ > 0) {   // binary recursion with depth-first sampler dimensions / inherited ray differentials: one thread per camera sample
+        size_t e2 = tick(3);
+        // frames below level kTreeMax of the per-sample recursion live in a strided global array, sized for this pass
+        TreeFrame<R>* deep = nullptr;
+        if (max_depth > kTreeMax) {
+          const size_t need = (size_t)(max_depth - kTreeMax) * nslots;
+          if (tree_deep_.n < need) { HIP_CHECK(hipStreamSynchronize(st_)); tree_deep_.alloc(need); }
+          deep = tree_deep_.p;
+        }
+        if (tex_depth_ > 0) hipLaunchKernelGGL((k_direct_tree<R, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots);
+        else hipLaunchKernelGGL((k_direct_tree<R, false>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots);
+        tock(e2);
+      } else {
+      const bool all = integ == RRT_INT_DEBUG || desc_.integrator.light_strategy == RRT_STRATEGY_ALL;
+      // level k handles reference depth k+1; specular recursion while depth + 1 < max_depth
+      for (int level = 0; level < std::max(1, max_depth - 1); level++) {
+        hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
+        e = tick(1);
+        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, level == 0);
+        tock(e); n_closest_launch++;
+        if (level == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
+        if (desc_.n_lights > 0) {
+          const int nl = all ? (int)desc_.n_lights : 1;
+          for (int j = 0; j < nl; j++) {
+            hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);
             scene_.use_shadow_tabs = use_shadow_lists() ? 1u : 0u;
-            scene_.horizon = (horizon_on_ && horizon_.n) ? horizon_.p : nullptr; scene_.hz_tau = horizon_tau_.p; scene_.hz_axis = hz_axis_;   // (counting frames too: the cull is geometry, not a kernel's arithmetic - their node counters then hold the rays that are traced)
             e = tick(3);
-            if (tex_depth_ > 0) hipLaunchKernelGGL((k_shade_path<R, 4, true>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
-            else if (has_translucent_) hipLaunchKernelGGL((k_shade_path<R, 4>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
-            else if (shade_kinds_ == kKindsLambert) {
-              constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsLambert>();
-              const dim3 g(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u));
-              if (area_lights_ || shade_kinds_ == kAllKinds) hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, true>), g, dim3(kB), 0, st_, scene_, pool_);
-              else hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, false>), g, dim3(kB), 0, st_, scene_, pool_);
-            }
-            else if (shade_kinds_ == kKindsGlossy) {
-              constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsGlossy>();
-              hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsGlossy>), dim3(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u)), dim3(kB), 0, st_, scene_, pool_);
-            }
-            else hipLaunchKernelGGL((k_shade_path<R, 2>), dim3(std::min(sgrid, 16384u)), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_);
+            hipLaunchKernelGGL((k_shade_nee<R>), dim3(sgrid), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_, all ? j : -1, j == 0 ? 1 : 0);
             tock(e);
-            if (scene_.horizon) hipLaunchKernelGGL(k_accumulate_sky, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
-            if (overlap) {
-              HIP_CHECK(hipEventRecord(ev_shade_, st_));
-              HIP_CHECK(hipStreamWaitEvent(st2_, ev_shade_, 0));
-              hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st2_, pool_.shadow_count, totals_.p);
-              e = tick(2, st2_);
-              launch_shadow(grid, st2_);
-              tock(e, st2_); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
-              hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st2_, counters_.p, 6 + (b & 1));   // this shadow queue + the any-hit work counter
-              HIP_CHECK(hipEventRecord(ev_shadow_[b & 1], st2_));
-              swap_queues();
-              hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 5);    // active <- next, closest work counter
-            } else {
-              hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st_, pool_.shadow_count, totals_.p);
-              e = tick(2);
-              launch_shadow(grid);
-              tock(e); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
-              swap_queues();
-              hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);
-            }
-          }
-          if (overlap) {   // the film kernel reads L
-            HIP_CHECK(hipStreamWaitEvent(st_, ev_shadow_[(max_depth - 1) & 1], 0));
-            use_shadow_queue(0);
-          }
-        } else if (integ == RRT_INT_DIRECT || integ == RRT_INT_DEBUG) {
-          if (has_transmissive_ || tex_depth_ > 0) {   // binary recursion with depth-first sampler dimensions / inherited ray differentials: one thread per camera sample
-            size_t e2 = tick(3);
-            // frames below level kTreeMax of the per-sample recursion live in a strided global array, sized for this pass
-            TreeFrame<R>* deep = nullptr;
-            if (max_depth > kTreeMax) {
-              const size_t need = (size_t)(max_depth - kTreeMax) * nslots;
-              if (tree_deep_.n < need) { HIP_CHECK(hipStreamSynchronize(st_)); tree_deep_.alloc(need); }
-              deep = tree_deep_.p;
-            }
-            if (tex_depth_ > 0) hipLaunchKernelGGL((k_direct_tree<R, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots);
-            else hipLaunchKernelGGL((k_direct_tree<R, false>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots);
-            tock(e2);
-          } else {
-          const bool all = integ == RRT_INT_DEBUG || desc_.integrator.light_strategy == RRT_STRATEGY_ALL;
-          // level k handles reference depth k+1; specular recursion while depth + 1 < max_depth
-          for (int level = 0; level < std::max(1, max_depth - 1); level++) {
-            hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
-            e = tick(1);
-            launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, level == 0);
-            tock(e); n_closest_launch++;
-            if (level == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
-            if (desc_.n_lights > 0) {
-              const int nl = all ? (int)desc_.n_lights : 1;
-              for (int j = 0; j < nl; j++) {
-                hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);
-                scene_.use_shadow_tabs = use_shadow_lists() ? 1u : 0u;
-                e = tick(3);
-                hipLaunchKernelGGL((k_shade_nee<R>), dim3(sgrid), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_, all ? j : -1, j == 0 ? 1 : 0);
-                tock(e);
-                hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st_, pool_.shadow_count, totals_.p);
-                e = tick(2);
-                launch_shadow(grid);
-                tock(e); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
-              }
-            }
-            e = tick(3);
-            hipLaunchKernelGGL((k_shade_specular<R>), dim3(sgrid), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_, (desc_.n_lights == 0 && integ == RRT_INT_DEBUG) ? 1 : 0);
-            tock(e);
-            swap_queues();
-            hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);
-          }
+            hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st_, pool_.shadow_count, totals_.p);
+            e = tick(2);
+            launch_shadow(grid);
+            tock(e); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
           }
         }
-        e = tick(4);
-        if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
-          if constexpr (std::is_same<R, float>::value)
-            hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_.p, film_runs_.p, (uint32_t)(ns / 8));
-        }
-        else if (!wide_filter) {
-          const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
-          if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p);
-          else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
-        }
-        else {
-          // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
-          const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-          const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-          const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-          const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-          const dim3 fg((uint32_t)((en + kBlock - 1) / kBlock));
-          if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-          else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-        }
+        e = tick(3);
+        hipLaunchKernelGGL((k_shade_specular<R>), dim3(sgrid), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_, (desc_.n_lights == 0 && integ == RRT_INT_DEBUG) ? 1 : 0);
         tock(e);
-        HIP_CHECK(hipGetLastError());
+        swap_queues();
+        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);
+      }
       }
     }
-    if (timing) HIP_CHECK(hipEventRecord(fr->ev_end, st_));
-    // merge into the caller's film (+=)
+    e = tick(4);
+    if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
+      if constexpr (std::is_same<R, float>::value)
+        hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_.p, film_runs_.p, (uint32_t)(ns / 8));
+    }
+    else if (!wide_filter) {
+      const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
+      if (list) hipLaunchKernelGGL((k_film_box_moments_list<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_.p, moments_.p);
+      else if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p);
+      else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
+    }
+    else {
+      // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
+      const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+      const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+      const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+      const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
+      const dim3 fg((uint32_t)((en + kBlock - 1) / kBlock));
+      if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+      else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+    }
+    tock(e);
+    HIP_CHECK(hipGetLastError());
+  }
+  // the internal film, converted to XYZ, and the internal moments buffer (where moments_user is given) added to the caller's buffers (+=); wait = 0
+  // (device memory only): enqueued, not waited for
+  void merge_out(void* film_user, void* moments_user, int film_mem, bool wait) {
+    const size_t W = (size_t)desc_.film.xres, H = (size_t)desc_.film.yres;
+    const bool with_moments = moments_user != nullptr;
     const size_t nfilm = W * H * 4, npx = W * H;
     if (film_mem == RRT_MEM_DEVICE) {
       hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)film_.p, (R*)film_user, npx);
       if (with_moments) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((nfilm + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)moments_.p, (R*)moments_user, nfilm);
       HIP_CHECK(hipGetLastError());
-      if (defer_) { frame_ = std::move(fr); return; }   // render_end() synchronises, checks the error flags and reads the statistics
+      if (!wait) return;
       HIP_CHECK(hipStreamSynchronize(st_));
     } else {
       if (film_xyz_.n != nfilm) film_xyz_.alloc(nfilm);
@@ -999,8 +1031,99 @@ class Handle : public HandleBase {
         for (size_t i = 0; i < nfilm; i++) dm[i] += tmp[i];
       }
     }
+  }
+  // ---- rrt_render_adaptive: a moments frame that stops sampling the 8 x 8 tiles whose error estimate fell below the threshold ------------------------------
+  // Round 0 is the moments frame's own passes over the rect for sample numbers 1 .. k0 (tile trees and all). After each round k_tile_error measures the
+  // active tiles from the internal moments buffer and k_tile_select writes the next round's tile list in ascending order and its length, which the host
+  // reads (4 bytes: the one synchronisation of a round) to size the listed passes of the next sample numbers. The internal film and moments buffers are
+  // zeroed once and run on across the rounds; a pixel's sums are added in sample order whatever the pass, so a tile that stopped at k holds the bits
+  // of a k-sample frame.
+  void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film_user, void* moments_user, uint32_t* tile_samples_user, int mem, rrt_render_stats* stats) override {
+    if (pending_) throw std::invalid_argument("render_adaptive: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    const rrt_film& f = desc_.film;
+    if (desc_.sampler.type == RRT_SAMPLER_STRATIFIED)
+      throw UnsupportedError("render_adaptive: StratifiedSampler (the first k samples of a stratified pixel are not a k-sample stratified pixel; use the HaltonSampler)");
+    if (f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5)
+      throw UnsupportedError("render_adaptive: pixel filters other than the box filter of radius 0.5 (a wider filter splats across tiles with different sample counts)");
+    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_adaptive: rect outside the film");
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
+    const uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
+    const uint64_t K = std::min<uint64_t>(ap->max_samples ? ap->max_samples : s_total, s_total), k0 = std::min<uint64_t>(ap->min_samples, K);
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = (size_t)(rect[3] - rect[1]), rpix = rw * rh;
+    const uint32_t tiles_x = (uint32_t)(rw / kTileW), n_tiles = tiles_x * (uint32_t)(rh / kTileH);
+    const auto kind = mem == RRT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (ad_samples_.n < n_tiles) { ad_list_[0].alloc(n_tiles); ad_list_[1].alloc(n_tiles); ad_err_.alloc(n_tiles); ad_samples_.alloc(n_tiles); }
+    if (ad_count_.n == 0) ad_count_.alloc(1);
+    HIP_CHECK(hipMemsetAsync(ad_samples_.p, 0, n_tiles * sizeof(uint32_t), st_));
+    frame_setup(true, rpix * (size_t)std::max<uint64_t>(K, 1));
+    const bool timing = stats != nullptr;
+    FrameRec fr;
+    fr.timing = timing;
+    if (timing) { fr.ev_begin = fr.make(); fr.ev_end = fr.make(); HIP_CHECK(hipEventRecord(fr.ev_begin, st_)); }
+    rect_passes(rect, 1u << 30, 1u, 0u, rw, rh, 0, k0, true, fr);
+    fr.camera_samples = (uint64_t)rpix * k0;
+    const uint32_t* list_in = nullptr;   // (round 0 took every tile)
+    uint32_t n_active = n_tiles;
+    int cur = 0;
+    for (uint64_t k = k0; K > 0;) {
+      // (at k == K every tile stops whatever its error: k_tile_select does not read it)
+      if (k < K) hipLaunchKernelGGL((k_tile_error<R>), dim3((n_active + kTeBlock / 64u - 1) / (kTeBlock / 64u)), dim3(kTeBlock), 0, st_, (const typename Vec4T<R>::type*)moments_.p, (uint32_t)f.xres, rect[0], rect[1],
+                         tiles_x, list_in, n_active, ad_err_.p);
+      hipLaunchKernelGGL(k_tile_select, dim3(1), dim3(kSelBlock), 0, st_, list_in, n_active, (const double*)ad_err_.p, ap->threshold, (uint32_t)k, k == K ? 1 : 0, ad_list_[cur].p, ad_count_.p, ad_samples_.p);
+      HIP_CHECK(hipGetLastError());
+      if (k == K) break;
+      uint32_t n_next = 0;
+      HIP_CHECK(hipMemcpyAsync(&n_next, ad_count_.p, sizeof(n_next), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipStreamSynchronize(st_));
+      if (n_next == 0) break;
+      if (n_next > n_active) throw DeviceError("internal: k_tile_select kept more tiles than it was given");
+      const uint64_t nb = std::min<uint64_t>(ap->batch, K - k);
+      // listed passes: groups of whole tiles and sample chunks from what the pools hold, as rect_passes cuts a rect
+      const size_t group = std::max<size_t>(1, std::min<size_t>(n_next, cap_ / (kTileW * kTileH)));         // tiles per group
+      const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / (group * kTileW * kTileH));                   // samples per pass
+      for (size_t g0 = 0; g0 < n_next; g0 += group) {
+        const size_t nt = std::min(group, (size_t)n_next - g0);
+        for (uint64_t sb = 0; sb < nb; sb += s_chunk) {
+          const uint64_t ns = std::min<uint64_t>(s_chunk, nb - sb);
+          PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)(g0 * kTileW * kTileH), (uint32_t)(nt * kTileW * kTileH), (uint32_t)(1 + k + sb), (uint32_t)ns, 1u << 30, 1u, 0u, 1u};
+          run_pass(pd, ad_list_[cur].p, rect, true, fr);
+        }
+      }
+      fr.camera_samples += (uint64_t)n_next * (kTileW * kTileH) * nb;
+      k += nb;
+      list_in = ad_list_[cur].p; n_active = n_next; cur ^= 1;
+    }
+    if (timing) HIP_CHECK(hipEventRecord(fr.ev_end, st_));
+    if (tile_samples_user) HIP_CHECK(hipMemcpyAsync(tile_samples_user, ad_samples_.p, n_tiles * sizeof(uint32_t), kind, st_));
+    merge_out(film_user, moments_user, mem, true);
     check_device_errors();
-    if (stats) frame_stats(*fr, stats);
+    if (stats) frame_stats(fr, stats);
+  }
+  // ---- rrt_tile_error: k_tile_error over every tile of the rect, on the caller's plane --------------------------------------------------------------------
+  void tile_error(const void* moments, int mem, const int32_t rect[4], double* out) override {
+    if (pending_) throw std::invalid_argument("tile_error: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    const rrt_film& f = desc_.film;
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("tile_error: rect outside the film");
+    HIP_CHECK(hipSetDevice(dev_));
+    using V4 = typename Vec4T<R>::type;
+    const size_t npix = (size_t)f.xres * (size_t)f.yres;
+    const uint32_t tiles_x = (uint32_t)(rect[2] - rect[0]) / kTileW, n_tiles = tiles_x * ((uint32_t)(rect[3] - rect[1]) / kTileH);
+    const V4* mom = (const V4*)moments;
+    if (mem == RRT_MEM_HOST) {
+      if (!dn_stage_m_.p || dn_stage_m_.n != npix) dn_stage_m_.alloc(npix);
+      HIP_CHECK(hipMemcpyAsync(dn_stage_m_.p, moments, npix * sizeof(V4), hipMemcpyHostToDevice, st_));
+      mom = dn_stage_m_.p;
+    }
+    if (te_out_.n < n_tiles) te_out_.alloc(n_tiles);
+    hipLaunchKernelGGL((k_tile_error<R>), dim3((n_tiles + kTeBlock / 64u - 1) / (kTeBlock / 64u)), dim3(kTeBlock), 0, st_, mom, (uint32_t)f.xres, rect[0], rect[1], tiles_x, (const uint32_t*)nullptr, n_tiles, te_out_.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, te_out_.p, n_tiles * sizeof(double), mem == RRT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
   }
   // ---- first-hit feature buffers (rrt_render_aov): the frame's camera samples, traced once, into albedo / normal / depth planes -------------
   // The pass loop of render_impl (same pixel groups and sample chunks from cap_) with three launches per pass: camera kernels, closest hit,
@@ -1292,6 +1415,8 @@ class Handle : public HandleBase {
   DevBuf<R> film_;       // per pixel: running RGB contribution sum + filter weight sum of the frame being rendered
   DevBuf<R> film_xyz_;   // the same merged to XYZ, staging for a host film
   DevBuf<R> moments_;    // render_moments: per pixel running {S1, S2, S0, S3} of the frame being rendered (allocated by the first call)
+  DevBuf<uint32_t> ad_list_[2], ad_count_, ad_samples_;   // render_adaptive: the tile lists of this round and the next, the next round's length, the tiles' sample counts
+  DevBuf<double> ad_err_, te_out_;                        // k_tile_error's output per tile: of render_adaptive's rounds / of tile_error (allocated by the first call)
   DevBuf<R> aov_planes_;   // render_aov: running sums of the albedo, normal and depth planes, W x H x 4 each (allocated by the first call)
   DevBuf<typename Vec4T<R>::type> dn_c_[2], dn_g_, dn_p_, dn_stage_;   // denoise: the record planes C (ping-pong), G, P of dfilter.hpp, and the staging of host-memory calls (allocated by the first call)
   DevBuf<typename Vec4T<R>::type> dn_stage_m_;   // denoise with a moments plane in host memory: its staging
@@ -1888,7 +2013,8 @@ class Handle : public HandleBase {
   // camera ray generation: the dense lean-arithmetic kernels in fp32 (dtraverse_f32.hpp), the generic two-stage kernels (main trace, auxiliary traces; the
   // reference's operation order) in f64 and for what the dense ones do not cover
   // for_render: the queue feeds the integrator (camera rays that miss the root box may be answered here); otherwise every survivor's ray is wanted (rrt_camera_samples)
-  void launch_raygen(const PassDesc& pd, uint32_t grid, double* dims_out, int enqueue, bool for_render = false, bool film_records = true) {
+  // list: the tiles of a listed pass (list_pixel): the same camera kernels behind the list form of k_pixel_offsets, or k_raygen_list; no tile trees
+  void launch_raygen(const PassDesc& pd, uint32_t grid, double* dims_out, int enqueue, bool for_render = false, bool film_records = true, const uint32_t* list = nullptr) {
     tt_pass_ok_ = false;
     film_runs_ok_ = false;
     scene_.root_cull = 0u;
@@ -1910,7 +2036,8 @@ class Handle : public HandleBase {
         pool_.pix_off = pix_off_.p;
         const rrt_film& f = desc_.film;
         const int write_samp = (f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5) ? 1 : 0;   // only k_film_wide reads p_film
-        hipLaunchKernelGGL(k_pixel_offsets, dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, scene_, pool_, pd);
+        if (list) hipLaunchKernelGGL(k_pixel_offsets_list, dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, scene_, pool_, pd, list);
+        else hipLaunchKernelGGL(k_pixel_offsets, dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, scene_, pool_, pd);
         // (dead samples: weight 0, Q2 - written by k_raygen_main_f32 itself, one coalesced store per sample)
         {   // dense two-stage version with the lean lens arithmetic
           const float2* safe_r2 = (aux_margin_ && tex_depth_ == 0) ? reinterpret_cast<const float2*>(lens_safe_.p) : nullptr;   // textured scenes keep the auxiliary rays themselves (ray differentials)
@@ -1921,7 +2048,7 @@ class Handle : public HandleBase {
           const uint32_t spb = (pd.tiled && pd.ns >= (uint32_t)rg_spb_) ? (uint32_t)std::max(1, std::min(rg_spb_, kRgDense / 64)) : 1u, ppb = kRgDense / spb;
           const uint32_t n_pb = (pd.npix + ppb - 1) / ppb, gz = (n_pb + 65534u) / 65535u, gy = (n_pb + gz - 1) / gz;
           // tile trees: the pass qualifies when it covers the whole pixel grid of its rect in tile order with one 8 x 8 tile x 8 samples per camera workgroup
-          if (tt_state_ == 1 && tile_trees_on_ && enqueue && pd.tiled && spb == 8 && ppb == kTileW * kTileH && pd.pix_begin == 0 && pd.npix % ((uint32_t)pd.rw * kTileH) == 0 &&
+          if (!list && tt_state_ == 1 && tile_trees_on_ && enqueue && pd.tiled && spb == 8 && ppb == kTileW * kTileH && pd.pix_begin == 0 && pd.npix % ((uint32_t)pd.rw * kTileH) == 0 &&
               pd.ns % spb == 0 && use_persistent() && trav_mode_ == 3 && !count_traversal_) {
             const size_t n_chunks = (size_t)gy * gz * ((pd.ns + spb - 1) / spb);
             if (tt_chunks_.n < n_chunks) { HIP_CHECK(hipStreamSynchronize(st_)); tt_chunks_.alloc(n_chunks); }
@@ -1945,7 +2072,8 @@ class Handle : public HandleBase {
         return;
       }
     }
-    hipLaunchKernelGGL((k_raygen<R>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, pd, dims_out);
+    if (list) hipLaunchKernelGGL((k_raygen_list<R>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, pd, list);
+    else hipLaunchKernelGGL((k_raygen<R>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, pd, dims_out);
     hipLaunchKernelGGL((k_raygen_aux<R>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, enqueue);
     hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 4);   // q_next was only a staging queue
     HIP_CHECK(hipGetLastError());
