@@ -461,6 +461,22 @@ int rrt_denoise(rrt_handle*, const void* film_xyzw, const rrt_aov* aov, const rr
 int rrt_render_moments(rrt_handle*, const int32_t rect[4], int rank, int world, void* film_xyzw, void* moments, int mem,
                        rrt_render_stats* stats /* may be NULL */);
 
+/* The moments frame and its feature buffers from one camera pass (no counterpart in the reference): everything rrt_denoise_moments reads, from
+ * one call. film_xyzw and moments are added to (+=) with the very bits rrt_render_moments(h, rect, rank, world, film_xyzw, moments, mem, stats)
+ * adds, and the statistics hold the same camera_samples, camera_rays, closest_queries, any_queries, root_culled, sky_culled, tile_launches and
+ * list_launches; `moments` may be NULL (the plane is not produced; the film is still the moments frame's). The non-NULL planes of `aov` are
+ * added to (+=) with the very bits rrt_render_aov(h, rect, rank, world, aov_max_samples, aov) adds: aov->mem must equal mem, aov->precision the
+ * handle's, and aov_max_samples has rrt_render_aov's meaning (0 takes all samples, k takes sample_num 1..min(k, nsamp-1)) - the frame always
+ * takes all of its samples. Where the frame's passes begin with a closest-hit launch over the camera rays (the Path integrator; DirectLighting
+ * and Debug on scenes without transmissive or textured materials) the first hits are shaded from that launch's queue and no camera ray is traced
+ * twice; a camera ray the frame's root cull answered is the miss it is. Every other scene renders the frame and then rrt_render_aov's own
+ * pass: the interface is total and the bits are the same. The handle is left as it was. Errors: the union of the two calls', each with its own
+ * message - RRT_EINVAL for a NULL handle, rect, film or aov, all planes NULL, a bad mem and aov->mem != mem (all before any device work), bad
+ * rank / world, a rect outside the film, a precision that is not the handle's, a frame in flight; otherwise what rrt_render_rect gives for the
+ * scene. There is no _begin / _end form and no adaptive form: rrt_render_adaptive keeps its signature and hands out no feature buffers. */
+int rrt_render_frame_aov(rrt_handle*, const int32_t rect[4], int rank, int world, void* film_xyzw, void* moments /* may be NULL: plane not produced */,
+                         int mem, uint64_t aov_max_samples, rrt_aov* aov, rrt_render_stats* stats /* may be NULL */);
+
 /* rrt_denoise with the variance of the pixels' means taken from the plane of rrt_render_moments (summed over rects / bands by the caller, in
  * aov->mem) where a pixel has one: the same prepare, iterations, finish and argument checks, and RRT_EINVAL for a NULL moments. Only the
  * `variance` step differs. Per pixel p with data, in double in both precision modes:

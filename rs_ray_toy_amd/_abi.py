@@ -197,6 +197,8 @@ PROTOTYPES = {
     "rrt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "rrt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
+    "rrt_render_frame_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Aov),
+                                       C.POINTER(RenderStats)]),
     "rrt_denoise_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_tile_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
     "rrt_adaptive_defaults": (None, [C.POINTER(AdaptiveParams)]),

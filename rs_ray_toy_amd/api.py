@@ -240,6 +240,38 @@ class Renderer:
         _check(A.lib().rrt_render_moments(self._h, r, rank, world, film_ptr, moments_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
         return st
 
+    # rrt_render_frame_aov: the frame of render_moments() and the planes of render_aov() from one camera pass - every input of denoise(..., moments=)
+    def render_frame_aov(self, rect=None, rank=0, world=1, max_samples=0, film=None, moments=True, planes=("albedo", "normal", "depth"), stats=False):
+        """-> (film, moments_or_None, aov_dict[, stats]): film and moments as render_moments gives them (moments: True = a new plane, False / None =
+        not produced, an array = added to), aov_dict as render_aov(rect, max_samples, rank, world, planes) gives it."""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        if film is None:
+            film = np.zeros((H, W, 4), self.dtype)
+        if moments is True:
+            moments = np.zeros((H, W, 4), self.dtype)
+        elif moments is False:
+            moments = None
+        for a in (film, moments):
+            if a is not None and (a.dtype != self.dtype or a.shape != (H, W, 4) or not a.flags.c_contiguous):
+                raise ValueError("render_frame_aov: film and moments are C-contiguous (H, W, 4) arrays of the handle's precision")
+        out = {k: np.zeros((H, W, 4), self.dtype) for k in planes}
+        ptr = {k: (out[k].ctypes.data if k in out else None) for k in ("albedo", "normal", "depth")}
+        aov = A.Aov(A.RRT_MEM_HOST, self.precision, ptr["albedo"], ptr["normal"], ptr["depth"])
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_frame_aov(self._h, r, rank, world, film.ctypes.data, None if moments is None else moments.ctypes.data, A.RRT_MEM_HOST,
+                                            max_samples, C.byref(aov), C.byref(st) if stats else None))
+        return (film, moments, out, st) if stats else (film, moments, out)
+
+    def render_frame_aov_device(self, rect, film_ptr, moments_ptr, albedo_ptr, normal_ptr, depth_ptr, max_samples=0, rank=0, world=1, stats=True):
+        """The same on device buffers (raw pointers; moments_ptr and any plane but one may be None)."""
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        aov = A.Aov(A.RRT_MEM_DEVICE, self.precision, albedo_ptr, normal_ptr, depth_ptr)
+        _check(A.lib().rrt_render_frame_aov(self._h, r, rank, world, film_ptr, moments_ptr, A.RRT_MEM_DEVICE, max_samples, C.byref(aov), C.byref(st) if stats else None))
+        return st
+
     # rrt_render_adaptive: the moments frame with 8 x 8 tiles that stop once their error estimate (rrt_tile_error) is below the threshold
     def _adaptive_params(self, params):
         p = A.AdaptiveParams()
@@ -459,7 +491,7 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     r = Renderer(scene, device, precision)
     for w in r.warnings:
         print(w, flush=True)
-    moments = None
+    moments = aov = None
     with_moments = bool(os.environ.get("RRT_DENOISE")) and os.environ.get("RRT_DENOISE_MOMENTS", "0") not in ("", "0")
     if os.environ.get("RRT_ADAPTIVE"):   # as rrt_render: rrt_render_adaptive in the frame's place
         params = {"threshold": float(os.environ["RRT_ADAPTIVE"])}
@@ -470,8 +502,8 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
         moments = plane if with_moments else None
         W, H = scene.resolution
         print(f"{st.camera_samples} of {W * H * max(0, scene.desc.sampler.samples_per_pixel - 1)} camera samples taken (adaptive)")
-    elif with_moments:   # as rrt_render: the same frame, and its sample-variance plane
-        film, moments, st = r.render_moments(stats=True)
+    elif with_moments:   # as rrt_render: the same frame, its sample-variance plane and the denoiser's feature planes from one camera pass
+        film, moments, aov, st = r.render_frame_aov(max_samples=32, stats=True)
     else:
         film, st = r.render(stats=True)
     print(f"{st.camera_rays} rays generated")
@@ -480,6 +512,6 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
         write_aov_pngs(os.environ["RRT_AOV"], r.render_aov())
     if os.environ.get("RRT_DENOISE"):   # as rrt_render: the filtered frame, guided by the planes of at most 32 samples per pixel
-        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, r.render_aov(max_samples=32), moments=moments), scene.desc.film.scale))
+        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, aov if aov is not None else r.render_aov(max_samples=32), moments=moments), scene.desc.film.scale))
     r.close()
     return film, st

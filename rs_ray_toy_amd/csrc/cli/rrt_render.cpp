@@ -13,7 +13,8 @@
 // RRT_DENOISE = <path.png> writes the denoised frame beside the ordinary one: rrt_render_aov with max_samples 32 on device 0, then rrt_denoise
 // (default parameters) over the gathered film,
 // RRT_DENOISE_MOMENTS = 1 (any value but "" and "0") beside RRT_DENOISE (one GPU): the frame is rendered by rrt_render_moments - the same film, bit for bit, so the ordinary
-// PNG is unchanged - and the denoised frame comes from rrt_denoise_moments under the frame's sample-variance plane.
+// PNG is unchanged - and the denoised frame comes from rrt_denoise_moments under the frame's sample-variance plane. That frame and the planes of
+// its first 32 samples come from one call, rrt_render_frame_aov: the same bits as rrt_render_moments followed by rrt_render_aov, one camera pass less.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -62,14 +63,24 @@ int write_aov(rrt_handle* h, int precision, int W, int H, const std::string& pre
   return rc;
 }
 
-// the gathered film, filtered by rrt_denoise under the planes of at most 32 samples per pixel -> one 8-bit image
+// the gathered film, filtered by rrt_denoise under the planes of at most 32 samples per pixel -> one 8-bit image. planes_dev: the three planes as
+// rrt_render_frame_aov left them on device 0, one after the other; NULL = rendered here by rrt_render_aov
 template <typename R>
-int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, const void* film, const void* moments /* NULL: rrt_denoise */, const char* path) {
+int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, const void* film, const void* moments /* NULL: rrt_denoise */, const void* planes_dev,
+                   const char* path) {
   const size_t npx = (size_t)W * (size_t)H;
   std::vector<R> alb(4 * npx, R(0)), nrm(4 * npx, R(0)), dep(4 * npx, R(0)), out(4 * npx, R(0));
   rrt_aov aov{RRT_MEM_HOST, precision, alb.data(), nrm.data(), dep.data()};
   const int32_t rect[4] = {0, 0, W, H};
-  int rc = rrt_render_aov(h, rect, 0, 1, 32, &aov);
+  int rc = RRT_OK;
+  if (planes_dev) {
+    R* dst[3] = {alb.data(), nrm.data(), dep.data()};
+    for (int k = 0; k < 3; k++)
+      if (hipMemcpy(dst[k], (const R*)planes_dev + (size_t)k * 4 * npx, 4 * npx * sizeof(R), hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "rrt_render: feature plane copy-out failed\n");
+        return RRT_EDEVICE;
+      }
+  } else rc = rrt_render_aov(h, rect, 0, 1, 32, &aov);
   if (rc == RRT_OK) rc = moments ? rrt_denoise_moments(h, film, &aov, moments, nullptr, out.data()) : rrt_denoise(h, film, &aov, nullptr, out.data());
   std::vector<uint8_t> rgba(4 * npx);
   if (rc == RRT_OK) rc = rrt_resolve_rgba8(out.data(), precision, W, H, scale, rgba.data());
@@ -142,8 +153,10 @@ int main(int argc, char** argv) {
   std::vector<rrt_handle*> handles(n_gpus, nullptr);
   std::vector<void*> films(n_gpus, nullptr);
   void* moments_dev = nullptr;   // the sample-variance plane of device 0 (RRT_DENOISE_MOMENTS)
+  void* planes_dev = nullptr;    // albedo, normal and depth planes of device 0, one after the other (rrt_render_frame_aov)
   auto cleanup = [&]() {
     if (moments_dev) { (void)hipSetDevice(0); (void)hipFree(moments_dev); }
+    if (planes_dev) { (void)hipSetDevice(0); (void)hipFree(planes_dev); }
     for (int i = 0; i < n_gpus; i++) {
       if (handles[i]) rrt_destroy(handles[i]);
       if (films[i]) { (void)hipSetDevice(i); (void)hipFree(films[i]); }
@@ -174,9 +187,16 @@ int main(int argc, char** argv) {
       if (rc != RRT_OK) { const int e = fail("rrt_render_adaptive", rc); cleanup(); return e; }
       const unsigned long long spp = desc->sampler.samples_per_pixel > 1 ? (unsigned long long)desc->sampler.samples_per_pixel - 1ull : 0ull;
       std::printf("%llu of %llu camera samples taken (adaptive)\n", (unsigned long long)st.camera_samples, (unsigned long long)W * (unsigned long long)H * spp);
-    } else {
-      rc = rrt_render_moments(handles[0], rect, 0, 1, films[0], moments_dev, RRT_MEM_DEVICE, &st);
-      if (rc != RRT_OK) { const int e = fail("rrt_render_moments", rc); cleanup(); return e; }
+    } else {   // the frame, its moments plane and the denoiser's feature planes (at most 32 samples per pixel) from one camera pass
+      if (hipMalloc(&planes_dev, 3 * film_bytes) != hipSuccess || hipMemset(planes_dev, 0, 3 * film_bytes) != hipSuccess) {
+        std::fprintf(stderr, "rrt_render: cannot allocate the %zu-byte feature planes on device 0\n", 3 * film_bytes);
+        cleanup();
+        return 1;
+      }
+      unsigned char* pl = (unsigned char*)planes_dev;
+      rrt_aov aov{RRT_MEM_DEVICE, precision, pl, pl + film_bytes, pl + 2 * film_bytes};
+      rc = rrt_render_frame_aov(handles[0], rect, 0, 1, films[0], moments_dev, RRT_MEM_DEVICE, 32, &aov, &st);
+      if (rc != RRT_OK) { const int e = fail("rrt_render_frame_aov", rc); cleanup(); return e; }
     }
     rays_generated = st.camera_rays;
   } else {
@@ -220,8 +240,8 @@ int main(int argc, char** argv) {
       }
     }
     const void* mom = with_moments ? host_moments.data() : nullptr;
-    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), mom, env_dn)
-                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), mom, env_dn);
+    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), mom, planes_dev, env_dn)
+                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), mom, planes_dev, env_dn);
     if (rc != RRT_OK) { const int e = fail(with_moments ? "rrt_denoise_moments" : "rrt_denoise", rc); cleanup(); return e; }
   }
   cleanup();

@@ -1775,6 +1775,99 @@ __global__ void k_aov_merge(const R* src, R* dst, size_t n) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Frame forms of the three kernels above (rrt_render_frame_aov, include/rrt.h): the feature buffers from the frame's own bounce-0 queue.
+// A frame's camera kernels run with the root cull: a live camera ray that misses the root box has weight[slot] > 0 and never enters the
+// queue, so "every live sample is in the queue" does not hold and nothing writes its rec_a - the slot keeps what an earlier pass left.
+// Such a sample is a miss. The shading kernel therefore stamps rec_a.w with {serial of the pass << 1 | hit bit}; the serial is non-zero and
+// used by no earlier pass that wrote into the handle's record buffers (the host counts it up, and the buffers are zeroed when allocated;
+// k_aov_shade's own flag words 0 and 1 carry serial 0), and the gather kernels read every other stamp as a miss. Kernels of their own, not
+// a template flag: the code rrt_render_aov launches stays what it is. The sums go through aov_rho, aov_add, aov_load, aov_store and
+// film_wide_weight, so the arithmetic per sample is the same expressions, in the same order.
+// ------------------------------------------------------------------------------------------------------------
+// rec_a as a gather kernel of the frame form takes it: the record of this pass's own stamp, a miss otherwise
+template <typename R>
+RRT_DEV typename Vec4T<R>::type aov_frame_rec(const typename Vec4T<R>::type* rec_a, uint32_t slot, uint32_t serial) {
+  typename Vec4T<R>::type a = rec_a[slot];
+  const uint32_t stamp = real_to_bits(a.w);
+  // aov_add's flag word: the hit bit of this pass's own record; any other stamp = unwritten in this pass: root-culled, provably a miss
+  a.w = bits_to_real((stamp >> 1) == serial ? (stamp & 1u) : 0u, R(0));
+  return a;
+}
+
+// k_aov_shade over the queue the frame's first closest-hit launch of a pass leaves. slot_end: the slots of the leading samples that the
+// feature buffers take (slot = sl * npix + pl, so a prefix of the samples is a prefix of the slots); entries beyond it are skipped.
+template <typename R, bool TEX>
+__global__ void __launch_bounds__(kBlock) k_aov_shade_frame(SceneDev<R> s, Pools<R> p, typename Vec4T<R>::type* rec_a, typename Vec4T<R>::type* rec_b, uint32_t serial, uint32_t slot_end) {
+  using V4 = typename Vec4T<R>::type;
+  const uint32_t n = p.counters[C_ACTIVE];
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t slot = p.q_active[i].slot;
+    if (slot >= slot_end) continue;
+    const V4 h = p.hit[i];
+    const int prim = (int)real_to_bits(h.y);
+    if (prim < 0) { rec_a[slot] = mk4u<R>(R(0), R(0), R(0), serial << 1); continue; }
+    const V4 ro = p.ray_o[i], rd = p.ray_d[i];
+    SurfExt<R> ext;
+    const Surf<R> si = build_surface(s, prim, V3<R>(ro.x, ro.y, ro.z), V3<R>(rd.x, rd.y, rd.z), h.x, h.z, h.w, TEX ? &ext : nullptr);
+    if (!si.ok) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_SHADING_NORMAL);   // primitives.rs:66, as the frame reports it
+    TexCtx<R> tc;
+    if (TEX) {   // dpdx = dpdy = 0, dudx .. dvdy = 0 (TexCtx's defaults)
+      tc.p = si.p; tc.u = ext.u; tc.v = ext.v;
+      tc.pd = V3<double>((double)si.p.x + (double)si.p_lo.x, (double)si.p.y + (double)si.p_lo.y, (double)si.p.z + (double)si.p_lo.z);
+    }
+    const Rgb<R> rho = aov_rho<R, TEX>(s, s.materials[si.material], tc);
+    if (TEX) { if (tc.err) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_MIPMAP); }
+    const V3<R> nn = vnormalize(si.n);
+    rec_a[slot] = mk4u<R>(rho.r, rho.g, rho.b, (serial << 1) | 1u);
+    rec_b[slot] = mk4<R>(nn.x, nn.y, nn.z, h.x);
+  }
+}
+
+// k_aov_box over the leading pd.ns samples of a frame's pass (the host cuts pd.ns to the feature buffers' prefix)
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_aov_box_frame(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b, uint32_t serial) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  const size_t pix = (size_t)py_ * (size_t)s.xres + px_, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
+  AovPixel<R> px = aov_load(planes, plane_n, pix);
+  for (uint32_t sl = 0; sl < pd.ns; sl++) {
+    const uint32_t slot = sl * pd.npix + pl;
+    if (!(p.weight[slot] > R(0))) continue;   // dead sample
+    aov_add(px, R(1), aov_frame_rec<R>(rec_a, slot, serial), rec_b, slot);   // box filter table weight 1
+  }
+  aov_store(planes, plane_n, pix, px);
+}
+
+// k_aov_wide over the leading pd.ns samples of a frame's pass
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_aov_wide_frame(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b, uint32_t serial,
+                                                            int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint32_t)ew * (uint32_t)eh) return;
+  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
+  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
+  AovPixel<R> px = aov_load(planes, plane_n, pix);
+  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
+    if (sy < 0 || sy >= ymax) continue;
+    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+      uint32_t pl;
+      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
+      for (uint32_t sl = 0; sl < pd.ns; sl++) {
+        const uint32_t slot = sl * pd.npix + pl;
+        if (!(p.weight[slot] > R(0))) continue;
+        const typename Vec4T<R>::type cs = p.samp[slot];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
+        aov_add(px, fw, aov_frame_rec<R>(rec_a, slot, serial), rec_b, slot);
+      }
+    }
+  }
+  aov_store(planes, plane_n, pix, px);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Sample-variance plane beside the film (rrt_render_moments, include/rrt.h): per film pixel {S1 = sum fw y, S2 = sum fw y^2, S0 = sum fw,
 // S3 = sum fw^2} over every sample whose footprint covers the pixel, y = the luminance of L w after the film's own clamps. Kernels of their
 // own, not a template flag on k_film_box / k_film_wide: the kernels a plain frame launches stay the code they are. The film sums go through

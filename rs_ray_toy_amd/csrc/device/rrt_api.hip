@@ -162,6 +162,20 @@ int rrt_render_moments(rrt_handle* h, const int32_t rect[4], int rank, int world
   return guarded([&]() { h->impl->render_moments(rect, rank, world, film_xyzw, moments, mem, stats); });
 }
 
+int rrt_render_frame_aov(rrt_handle* h, const int32_t rect[4], int rank, int world, void* film_xyzw, void* moments, int mem, uint64_t aov_max_samples, rrt_aov* aov,
+                         rrt_render_stats* stats) {
+  // every check that needs no device before any device work, each with its own message; the caller's own arguments first (wrong whichever
+  // handle they come with), as rrt_render_aov has it; `moments` may be NULL (the plane is not produced)
+  if (!rect) { rrt::set_last_error("rrt_render_frame_aov: null rect"); return RRT_EINVAL; }
+  if (!film_xyzw) { rrt::set_last_error("rrt_render_frame_aov: null film"); return RRT_EINVAL; }
+  if (!aov) { rrt::set_last_error("rrt_render_frame_aov: null plane description (rrt_aov)"); return RRT_EINVAL; }
+  if (!aov->albedo && !aov->normal && !aov->depth) { rrt::set_last_error("rrt_render_frame_aov: no plane requested (albedo, normal and depth are all NULL)"); return RRT_EINVAL; }
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_frame_aov: bad mem"); return RRT_EINVAL; }
+  if (aov->mem != mem) { rrt::set_last_error("rrt_render_frame_aov: the planes must live in the film's memory kind (aov->mem != mem)"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_render_frame_aov: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_frame_aov(rect, rank, world, film_xyzw, moments, mem, aov_max_samples, aov, stats); });
+}
+
 void rrt_adaptive_defaults(rrt_adaptive_params* p) {
   if (!p) return;
   p->min_samples = 16; p->batch = 16; p->max_samples = 0;

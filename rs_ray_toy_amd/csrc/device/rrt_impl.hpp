@@ -55,6 +55,7 @@ struct HandleBase {
   virtual void render_end(rrt_render_stats* stats) = 0;
   virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
   virtual void render_moments(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, rrt_render_stats* stats) = 0;
+  virtual void render_frame_aov(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, uint64_t aov_max_samples, const rrt_aov* aov, rrt_render_stats* stats) = 0;   // moments may be NULL
   virtual void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film, void* moments, uint32_t* tile_samples, int mem, rrt_render_stats* stats) = 0;
   virtual void tile_error(const void* moments, int mem, const int32_t rect[4], double* tile_error) = 0;
   virtual void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) = 0;   // moments may be NULL (rrt_denoise)
@@ -763,8 +764,36 @@ class Handle : public HandleBase {
       throw std::invalid_argument("render_moments: rect outside the film");
     render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user);
   }
-  // moments_user: the caller's sample-variance plane (same memory kind as the film) = the frame's moments mode; NULL = a plain frame
-  void render_impl(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, void* film_user, int film_mem, rrt_render_stats* stats, void* moments_user = nullptr) {
+  // ---- rrt_render_frame_aov: the moments frame and the feature buffers of rrt_render_aov from one camera pass --------------------------------------------
+  // Which scenes take which route. A frame whose passes begin with a queued closest-hit launch over the camera rays - the Path integrator, and
+  // DirectLighting / Debug on scenes without transmissive or textured materials (the level loop of run_pass) - is fused: run_pass shades the first
+  // hits from the bounce-0 queue (k_aov_shade_frame) and gathers them beside the moments film kernel (k_aov_box_frame / k_aov_wide_frame). A frame
+  // that runs no such launch - the AO integrator, a Path integrator of depth 0, and DirectLighting / Debug on transmissive or textured scenes
+  // (k_direct_tree: one thread per camera sample, no queue) - renders as a moments frame and render_aov's own pass follows it. Both routes add the
+  // same bits.
+  void render_frame_aov(const int32_t rect[4], int rank, int world, void* film_user, void* moments_user, int mem, uint64_t aov_max_samples, const rrt_aov* aov, rrt_render_stats* stats) override {
+    if (pending_) throw std::invalid_argument("render_frame_aov: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (aov->precision != precision()) throw std::invalid_argument("render_frame_aov: plane precision must match the handle");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_frame_aov: bad rank/world");
+    const rrt_film& f = desc_.film;
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_frame_aov: rect outside the film");
+    const int integ = desc_.integrator.type;
+    const bool queued = (integ == RRT_INT_PATH && desc_.integrator.max_depth > 0) || ((integ == RRT_INT_DIRECT || integ == RRT_INT_DEBUG) && !(has_transmissive_ || tex_depth_ > 0));
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
+    uint64_t prefix = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
+    if (aov_max_samples != 0) prefix = std::min<uint64_t>(prefix, aov_max_samples);
+    FrameAov fa{aov, queued ? prefix : 0};
+    render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user, &fa);
+    if (!queued) render_aov(rect, rank, world, aov_max_samples, aov);
+  }
+  // the feature buffers a frame was asked for: the caller's planes, and the leading samples that run_pass shades and gathers (0: none - the frame is
+  // only held to its moments mode)
+  struct FrameAov { const rrt_aov* out; uint64_t prefix; };
+  // moments_user: the caller's sample-variance plane (same memory kind as the film) = the frame's moments mode; NULL = a plain frame, unless `fa` asks
+  // for a moments-mode frame whose plane is not handed out
+  void render_impl(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, void* film_user, int film_mem, rrt_render_stats* stats, void* moments_user = nullptr,
+                   const FrameAov* fa = nullptr) {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
     const rrt_film& f = desc_.film;
@@ -782,8 +811,16 @@ class Handle : public HandleBase {
     const uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;  // samples 1 .. nsamp-1 (Q1)
     if (rpix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }   // a rank that owns no band (world > yres / 16): nothing to add to the caller's film
 
-    const bool with_moments = moments_user != nullptr;
+    const bool with_moments = moments_user != nullptr || fa != nullptr;
     frame_setup(with_moments, rpix * (size_t)std::max<uint64_t>(s_total, 1));
+    struct AovOff { Handle* h; ~AovOff() { h->aov_prefix_ = 0; } } aov_off{this};   // run_pass shades first hits for this frame only
+    aov_prefix_ = fa ? fa->prefix : 0;
+    if (aov_prefix_ > 0) {   // (setup, not the pass loop: frame_setup has sized the pools)
+      const size_t plane_n = (size_t)f.xres * (size_t)f.yres * 4;
+      if (aov_planes_.n != 3 * plane_n) aov_planes_.alloc(3 * plane_n);
+      HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
+      ensure_aov_recs();
+    }
     const bool timing = stats != nullptr || (defer_ && frame_stats_);
     auto fr = std::make_unique<FrameRec>();
     fr->timing = timing; fr->camera_samples = (uint64_t)rpix * s_total;
@@ -794,6 +831,7 @@ class Handle : public HandleBase {
     const bool wait = !(film_mem == RRT_MEM_DEVICE && defer_);
     merge_out(film_user, moments_user, film_mem, wait);
     if (!wait) { frame_ = std::move(fr); return; }   // render_end() synchronises, checks the error flags and reads the statistics
+    if (aov_prefix_ > 0) aov_merge_out(fa->out);
     check_device_errors();
     if (stats) frame_stats(*fr, stats);
   }
@@ -870,6 +908,9 @@ class Handle : public HandleBase {
     const size_t nslots = npix * (size_t)ns;
     const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
     const uint32_t sgrid = (uint32_t)((nslots + ShadeBlock<R>::n - 1) / ShadeBlock<R>::n);
+    // rrt_render_frame_aov: the leading samples of this pass that the feature buffers take (a pass that begins beyond the prefix: none)
+    const uint64_t s_off = (uint64_t)pd.s_begin - 1;
+    const uint32_t aov_ns = (!list && aov_prefix_ > s_off) ? (uint32_t)std::min<uint64_t>(ns, aov_prefix_ - s_off) : 0u;
     hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
     size_t e = tick(0);
     launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments, list);
@@ -888,6 +929,7 @@ class Handle : public HandleBase {
         launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, b == 0);
         tock(e); n_closest_launch++;
         if (b == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
+        if (b == 0 && aov_ns > 0) launch_aov_shade_frame(pd, aov_ns, grid);
         if (overlap) {
           use_shadow_queue(b & 1);
           if (b > 1) HIP_CHECK(hipStreamWaitEvent(st_, ev_shadow_[b & 1], 0));   // shading refills the queue the shadow launch of bounce b - 2 read
@@ -956,6 +998,7 @@ class Handle : public HandleBase {
         launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, level == 0);
         tock(e); n_closest_launch++;
         if (level == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
+        if (level == 0 && aov_ns > 0) launch_aov_shade_frame(pd, aov_ns, grid);
         if (desc_.n_lights > 0) {
           const int nl = all ? (int)desc_.n_lights : 1;
           for (int j = 0; j < nl; j++) {
@@ -1000,7 +1043,66 @@ class Handle : public HandleBase {
       else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
     }
     tock(e);
+    if (aov_ns > 0) launch_aov_gather_frame(pd, aov_ns, rect, wide_filter);
     HIP_CHECK(hipGetLastError());
+  }
+  // rrt_render_frame_aov, first half of a pass: the first hits of the queue the bounce-0 closest-hit launch has just answered, under a stamp that no
+  // earlier pass has written into the record buffers. It reads the queue and writes its own records: the shadow stream is not involved.
+  void launch_aov_shade_frame(const PassDesc& pd, uint32_t aov_ns, uint32_t grid) {
+    if (aov_serial_ >= 0x7fffffffu) {   // the stamp's 31 bits are used up: start over on clean flag words
+      HIP_CHECK(hipMemsetAsync(aov_rec_a_.p, 0, aov_rec_a_.n * sizeof(typename Vec4T<R>::type), st_));
+      aov_serial_ = 0;
+    }
+    aov_serial_++;
+    const uint32_t slot_end = aov_ns * pd.npix;
+    const dim3 sg(std::min(grid, 16384u));
+    if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade_frame<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, aov_serial_, slot_end);
+    else hipLaunchKernelGGL((k_aov_shade_frame<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, aov_serial_, slot_end);
+  }
+  // second half, beside the moments film kernel: the pass's PassDesc with ns cut to the feature buffers' samples, gathered into the internal planes
+  void launch_aov_gather_frame(PassDesc pd, uint32_t aov_ns, const int32_t rect[4], bool wide_filter) {
+    using V4 = typename Vec4T<R>::type;
+    const rrt_film& f = desc_.film;
+    pd.ns = aov_ns;
+    if (!wide_filter) {
+      hipLaunchKernelGGL((k_aov_box_frame<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_);
+      return;
+    }
+    // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as run_pass)
+    const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+    const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+    const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+    const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
+    hipLaunchKernelGGL((k_aov_wide_frame<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_,
+                       ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+  }
+  // the per-slot records of the first-hit shading kernels, sized like the pools; rec_a - the flag words - zeroed when allocated, so that a slot no
+  // kernel has written yet carries no pass's stamp (k_aov_shade_frame)
+  void ensure_aov_recs() {
+    if (aov_rec_a_.n >= cap_) return;
+    HIP_CHECK(hipStreamSynchronize(st_));
+    aov_rec_a_.alloc(cap_); aov_rec_b_.alloc(cap_);
+    HIP_CHECK(hipMemsetAsync(aov_rec_a_.p, 0, cap_ * sizeof(typename Vec4T<R>::type), st_));
+  }
+  // the internal feature planes added to the caller's non-NULL planes (+=)
+  void aov_merge_out(const rrt_aov* out) {
+    const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
+    void* user[3] = {out->albedo, out->normal, out->depth};
+    if (out->mem == RRT_MEM_DEVICE) {
+      for (int k = 0; k < 3; k++)
+        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)(aov_planes_.p + k * plane_n), (R*)user[k], plane_n);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(st_));
+    } else {
+      std::vector<R> tmp(plane_n);
+      for (int k = 0; k < 3; k++) {
+        if (!user[k]) continue;
+        HIP_CHECK(hipMemcpyAsync(tmp.data(), aov_planes_.p + k * plane_n, plane_n * sizeof(R), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipStreamSynchronize(st_));
+        R* dst = (R*)user[k];
+        for (size_t i = 0; i < plane_n; i++) dst[i] += tmp[i];
+      }
+    }
   }
   // the internal film, converted to XYZ, and the internal moments buffer (where moments_user is given) added to the caller's buffers (+=); wait = 0
   // (device memory only): enqueued, not waited for
@@ -1164,7 +1266,7 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
     ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
-    if (aov_rec_a_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); aov_rec_a_.alloc(cap_); aov_rec_b_.alloc(cap_); }
+    ensure_aov_recs();
     const size_t group = std::min(rpix, cap_);                     // pixels per group
     const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
     for (size_t g0 = 0; g0 < rpix; g0 += group) {
@@ -1194,23 +1296,7 @@ class Handle : public HandleBase {
         HIP_CHECK(hipGetLastError());
       }
     }
-    // merge into the caller's planes (+=)
-    void* user[3] = {out->albedo, out->normal, out->depth};
-    if (out->mem == RRT_MEM_DEVICE) {
-      for (int k = 0; k < 3; k++)
-        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)(aov_planes_.p + k * plane_n), (R*)user[k], plane_n);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipStreamSynchronize(st_));
-    } else {
-      std::vector<R> tmp(plane_n);
-      for (int k = 0; k < 3; k++) {
-        if (!user[k]) continue;
-        HIP_CHECK(hipMemcpyAsync(tmp.data(), aov_planes_.p + k * plane_n, plane_n * sizeof(R), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        R* dst = (R*)user[k];
-        for (size_t i = 0; i < plane_n; i++) dst[i] += tmp[i];
-      }
-    }
+    aov_merge_out(out);   // into the caller's planes (+=)
     check_device_errors();
   }
   // ---- rrt_denoise (device/dfilter.hpp): prepare, initial variance, one a-trous launch per iteration, finish ---------------------------------------------
@@ -1422,6 +1508,8 @@ class Handle : public HandleBase {
   DevBuf<typename Vec4T<R>::type> dn_stage_m_;   // denoise with a moments plane in host memory: its staging
   bool dn_lds_ = true;       // option "dn_lds"
   DevBuf<typename Vec4T<R>::type> aov_rec_a_, aov_rec_b_;   // k_aov_shade's per-slot records {rho.rgb, hit flag}, {n.xyz, t}: sized like pool.L
+  uint64_t aov_prefix_ = 0;   // render_frame_aov: the leading samples whose first hits run_pass shades and gathers; 0 outside such a frame
+  uint32_t aov_serial_ = 0;   // k_aov_shade_frame's stamp of the pass last shaded: counted up per pass over the handle's life, never 0 in a record
 
   // which materials the aggregate really uses (declared-but-unused ones never reach a kernel)
   void scan_materials(const rrt_scene_desc* d) {
