@@ -205,6 +205,33 @@ struct Scene {
   void UV(uint32_t i, double* u, double* v) const { *u = d->uvs[2 * i]; *v = d->uvs[2 * i + 1]; }
 };
 
+// What a traversal can report beside its result (oracle_trace_*_probe): the peak occupancy of nodes_to_visit, and the triangle tests'
+// counterpart of box_intersect_p's `margin`: the smallest gap of every comparison that every triangle test of the walk made, the
+// rejected and the overwritten tests as much as the accepted ones (under Q10 any flipped acceptance changes t_max and the rest of the
+// walk). The gaps, in the order triangle.rs compares: | |a| - 1e-7 | / max(|a|, 1e-7); u against 0 and 1, v against 0, u + v against 1
+// (barycentrics are already relative to the triangle: plain differences); |t - 1e-7| / max(|t|, 1e-7). A test that returns early
+// made only the comparisons before its return.
+// peak_hit counts only the stack entries whose box the ray's slabs hit (t_max left out): the occupancy of a walk that pushes the other child only
+// when its slabs are hit, as the fp32 pair-node kernels do (they test both children's boxes at the parent) - peak is an upper bound of it.
+struct WalkProbe {
+  uint32_t peak = 0, peak_hit = 0; double tri_margin = INF;
+  std::vector<uint8_t> flagged; uint32_t n_flagged = 0;
+  void push(bool slabs_hit, size_t to_visit) {
+    if (flagged.size() < to_visit) flagged.resize(to_visit * 2, 0);
+    flagged[to_visit - 1] = slabs_hit ? 1 : 0;
+    if (slabs_hit && ++n_flagged > peak_hit) peak_hit = n_flagged;
+    if (to_visit > peak) peak = (uint32_t)to_visit;
+  }
+  void pop(size_t to_visit_after) { if (to_visit_after < flagged.size() && flagged[to_visit_after]) n_flagged--; }
+};
+struct TriGaps {
+  double* m;
+  void a(double a) const { if (m) *m = rmin(*m, std::fabs(std::fabs(a) - 0.0000001) / rmax(std::fabs(a), 0.0000001)); }
+  void u(double u) const { if (m) *m = rmin(*m, rmin(std::fabs(u), std::fabs(u - 1.0))); }
+  void v(double u, double v) const { if (m) *m = rmin(*m, rmin(std::fabs(v), std::fabs(u + v - 1.0))); }
+  void t(double t) const { if (m) *m = rmin(*m, std::fabs(t - 0.0000001) / rmax(std::fabs(t), 0.0000001)); }
+};
+
 // ---- Triangle (shape/triangle.rs) ------------------------------------------------------------------
 // intersect_p :167-205 (E2 = p2 - p1: Q11)
 // device upload formula (rrt_impl.hpp upload_scene): row-major affine product, left-to-right sums
@@ -214,40 +241,50 @@ inline V3 flat_pt(const double* m, V3 p) {
 inline V3 flat_nrm(const double* mi, V3 n) {
   return {mi[0] * n.x + mi[4] * n.y + mi[8] * n.z, mi[1] * n.x + mi[5] * n.y + mi[9] * n.z, mi[2] * n.x + mi[6] * n.y + mi[10] * n.z};
 }
-bool tri_intersect_p(const Scene& sc, const rrt_tri& t, const Ray& r, const rrt_xform* fx = nullptr) {
+bool tri_intersect_p(const Scene& sc, const rrt_tri& t, const Ray& r, const rrt_xform* fx = nullptr, double* tri_margin = nullptr) {
+  const TriGaps gap{tri_margin};
   V3 p0 = sc.P(t.v[0]), p1 = sc.P(t.v[1]), p2 = sc.P(t.v[2]);
   if (fx) { p0 = flat_pt(fx->m, p0); p1 = flat_pt(fx->m, p1); p2 = flat_pt(fx->m, p2); }
   V3 E1 = p1 - p0, E2 = p2 - p1, D = r.d;
   V3 Pv = cross(D, E2);
   double a = dot(E1, Pv);
+  gap.a(a);
   if (a > -0.0000001 && a < 0.0000001) return false;
   double f = 1.0 / a;
   V3 T = r.o - p0;
   double u = f * dot(T, Pv);
+  gap.u(u);
   if (u < 0.0 || u > 1.0) return false;
   V3 Q = cross(T, E1);
   double v = f * dot(D, Q);
+  gap.v(u, v);
   if (v < 0.0 || (u + v) > 1.0) return false;
   double tt = f * dot(E2, Q);
+  gap.t(tt);
   if (tt < 0.0000001) return false;
   return true;
 }
 // intersect :226-391 (never compares t with ray.t_max: Q10)
-bool tri_intersect(const Scene& sc, const rrt_tri& t, const Ray& r, double* thit, SI* ist, double* bu, double* bv, const rrt_xform* fx = nullptr) {
+bool tri_intersect(const Scene& sc, const rrt_tri& t, const Ray& r, double* thit, SI* ist, double* bu, double* bv, const rrt_xform* fx = nullptr, double* tri_margin = nullptr) {
+  const TriGaps gap{tri_margin};
   V3 p0 = sc.P(t.v[0]), p1 = sc.P(t.v[1]), p2 = sc.P(t.v[2]);
   if (fx) { p0 = flat_pt(fx->m, p0); p1 = flat_pt(fx->m, p1); p2 = flat_pt(fx->m, p2); }
   V3 E1 = p1 - p0, E2 = p2 - p0, D = r.d;
   V3 Pv = cross(D, E2);
   double a = dot(E1, Pv);
+  gap.a(a);
   if (a > -0.0000001 && a < 0.0000001) return false;
   double f = 1.0 / a;
   V3 T = r.o - p0;
   double u = f * dot(T, Pv);
+  gap.u(u);
   if (u < 0.0 || u > 1.0) return false;
   V3 Q = cross(T, E1);
   double v = f * dot(D, Q);
+  gap.v(u, v);
   if (v < 0.0 || (u + v) > 1.0) return false;
   double tt = f * dot(E2, Q);
+  gap.t(tt);
   if (tt < 0.0000001) return false;
   *thit = tt;
   // get_uvs :113-128
@@ -751,11 +788,11 @@ inline bool box_intersect_p(const double* b, const Ray& ray, V3 inv_dir, const i
 }
 
 // GeometricPrimitive / TransformedPrimitive ::intersect primitives.rs:51-68,124-139
-bool prim_intersect(const Scene& sc, uint32_t pi, Ray* r, SI* si, double* bu, double* bv) {
+bool prim_intersect(const Scene& sc, uint32_t pi, Ray* r, SI* si, double* bu, double* bv, double* tri_margin = nullptr) {
   const rrt_prim& p = sc.d->prims[pi];
   auto geometric = [&](Ray* rr) {
     double t_hit = 0.0;
-    if (p.type == RRT_PRIM_TRIANGLE) { if (!tri_intersect(sc, sc.d->tris[p.shape], *rr, &t_hit, si, bu, bv)) return false; }
+    if (p.type == RRT_PRIM_TRIANGLE) { if (!tri_intersect(sc, sc.d->tris[p.shape], *rr, &t_hit, si, bu, bv, nullptr, tri_margin)) return false; }
     else { *bu = 0; *bv = 0; if (!sphere_intersect(sphere_ref(sc, p.shape), *rr, &t_hit, si)) return false; }
     si->prim = (int)pi;
     si->valid = true;
@@ -767,7 +804,7 @@ bool prim_intersect(const Scene& sc, uint32_t pi, Ray* r, SI* si, double* bu, do
   const rrt_xform& x = sc.d->xforms[p.instance];
   if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(x.m)) {
     double t_hit = 0.0;
-    if (!tri_intersect(sc, sc.d->tris[p.shape], *r, &t_hit, si, bu, bv, &x)) return false;
+    if (!tri_intersect(sc, sc.d->tris[p.shape], *r, &t_hit, si, bu, bv, &x, tri_margin)) return false;
     si->prim = (int)pi; si->valid = true;
     r->t_max = t_hit;
     if (!(dot(si->n, si->sn) >= 0.0)) throw OraclePanic{"primitives.rs:66 assert!(dot3(&si.ist.n, &si.shading.n) >= 0.0)"};
@@ -779,13 +816,13 @@ bool prim_intersect(const Scene& sc, uint32_t pi, Ray* r, SI* si, double* bu, do
   if (!is_identity(x.m)) si_transform(si, x.m, x.m_inv);
   return true;
 }
-bool prim_intersect_p(const Scene& sc, uint32_t pi, const Ray& r) {  // primitives.rs:41-45,117-122
+bool prim_intersect_p(const Scene& sc, uint32_t pi, const Ray& r, double* tri_margin = nullptr) {  // primitives.rs:41-45,117-122
   const rrt_prim& p = sc.d->prims[pi];
   auto geometric = [&](const Ray& rr) {
-    return p.type == RRT_PRIM_TRIANGLE ? tri_intersect_p(sc, sc.d->tris[p.shape], rr) : sphere_intersect_p(sphere_ref(sc, p.shape), rr);
+    return p.type == RRT_PRIM_TRIANGLE ? tri_intersect_p(sc, sc.d->tris[p.shape], rr, nullptr, tri_margin) : sphere_intersect_p(sphere_ref(sc, p.shape), rr);
   };
   if (p.instance < 0) return geometric(r);
-  if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(sc.d->xforms[p.instance].m)) return tri_intersect_p(sc, sc.d->tris[p.shape], r, &sc.d->xforms[p.instance]);
+  if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(sc.d->xforms[p.instance].m)) return tri_intersect_p(sc, sc.d->tris[p.shape], r, &sc.d->xforms[p.instance], tri_margin);
   return geometric(xf_ray(sc.d->xforms[p.instance].m_inv, r));
 }
 
@@ -793,7 +830,7 @@ struct HitInfo { int order_index = -1; double u = 0, v = 0; };
 
 // BVHAccel::intersect bvh.rs:183-236. The reference's nodes_to_visit is [usize; 64]; deeper trees index
 // out of bounds there (panic) — reported as such unless the tree was built with the fixed builder.
-bool scene_intersect(const Scene& sc, Ray* r, SI* si, HitInfo* hi, Counters* cnt, uint32_t* nodes_c = nullptr, uint32_t* prims_c = nullptr, double* margin = nullptr) {
+bool scene_intersect(const Scene& sc, Ray* r, SI* si, HitInfo* hi, Counters* cnt, uint32_t* nodes_c = nullptr, uint32_t* prims_c = nullptr, double* margin = nullptr, WalkProbe* probe = nullptr) {
   if (len(r->d) == 0.0) throw OraclePanic{"scene.rs:70 assert_ne!(r.d.length(), 0.0)"};
   if (cnt) cnt->closest++;
   bool hit = false;
@@ -817,21 +854,22 @@ bool scene_intersect(const Scene& sc, Ray* r, SI* si, HitInfo* hi, Counters* cnt
         for (uint32_t i = 0; i < node.n_primitives; i++) {
           np++;
           double bu, bv;
-          if (prim_intersect(sc, d->prim_order[node.offset + i], r, si, &bu, &bv)) {
+          if (prim_intersect(sc, d->prim_order[node.offset + i], r, si, &bu, &bv, probe ? &probe->tri_margin : nullptr)) {
             hit = true;
             if (hi) { hi->order_index = (int)(node.offset + i); hi->u = bu; hi->v = bv; }
           }
         }
         if (to_visit == 0) break;
-        cur = stack[--to_visit];
+        cur = stack[--to_visit]; if (probe) probe->pop(to_visit);
       } else {
         if (strict64 && to_visit >= 64) throw OraclePanic{"bvh.rs:217 nodes_to_visit[64] index out of bounds (tree deeper than 64)"};
         if (dir_is_neg[node.axis]) { stack[to_visit++] = cur + 1; cur = node.offset; }
         else { stack[to_visit++] = node.offset; cur = cur + 1; }
+        if (probe) { Ray unb = *r; unb.t_max = INF; probe->push(box_intersect_p(d->bvh_nodes[stack[to_visit - 1]].bounds, unb, inv_dir, dir_is_neg), to_visit); }
       }
     } else {
       if (to_visit == 0) break;
-      cur = stack[--to_visit];
+      cur = stack[--to_visit]; if (probe) probe->pop(to_visit);
     }
   }
   if (cnt) { cnt->nodes += nn; cnt->prims += np; }
@@ -840,7 +878,7 @@ bool scene_intersect(const Scene& sc, Ray* r, SI* si, HitInfo* hi, Counters* cnt
   return hit;
 }
 // BVHAccel::intersect_p bvh.rs:124-173
-bool scene_intersect_p(const Scene& sc, const Ray& r, Counters* cnt, uint32_t* nodes_c = nullptr, uint32_t* prims_c = nullptr, double* margin = nullptr) {
+bool scene_intersect_p(const Scene& sc, const Ray& r, Counters* cnt, uint32_t* nodes_c = nullptr, uint32_t* prims_c = nullptr, double* margin = nullptr, WalkProbe* probe = nullptr) {
   if (len(r.d) == 0.0) throw OraclePanic{"scene.rs:77 assert_ne!(r.d.length(), 0.0)"};
   if (cnt) cnt->any++;
   const rrt_scene_desc* d = sc.d;
@@ -862,19 +900,20 @@ bool scene_intersect_p(const Scene& sc, const Ray& r, Counters* cnt, uint32_t* n
       if (node.n_primitives > 0) {
         for (uint32_t i = 0; i < node.n_primitives; i++) {
           np++;
-          if (prim_intersect_p(sc, d->prim_order[node.offset + i], r)) { result = true; break; }
+          if (prim_intersect_p(sc, d->prim_order[node.offset + i], r, probe ? &probe->tri_margin : nullptr)) { result = true; break; }
         }
         if (result) break;
         if (to_visit == 0) break;
-        cur = stack[--to_visit];
+        cur = stack[--to_visit]; if (probe) probe->pop(to_visit);
       } else {
         if (strict64 && to_visit >= 64) throw OraclePanic{"bvh.rs:154 nodes_to_visit[64] index out of bounds (tree deeper than 64)"};
         if (dir_is_neg[node.axis]) { stack[to_visit++] = cur + 1; cur = node.offset; }
         else { stack[to_visit++] = node.offset; cur = cur + 1; }
+        if (probe) { Ray unb = r; unb.t_max = INF; probe->push(box_intersect_p(d->bvh_nodes[stack[to_visit - 1]].bounds, unb, inv_dir, dir_is_neg), to_visit); }
       }
     } else {
       if (to_visit == 0) break;
-      cur = stack[--to_visit];
+      cur = stack[--to_visit]; if (probe) probe->pop(to_visit);
     }
   }
   if (cnt) { cnt->nodes += nn; cnt->prims += np; }
@@ -2237,6 +2276,59 @@ int oracle_trace_any(const rrt_scene_desc* d, const double* o, const double* dir
       if (margin_out) margin_out[i] = margin;
       if (nodes) nodes[i] = nn;
       if (prims) prims[i] = np;
+    }
+    if (!panic.empty()) throw OraclePanic{panic};
+  });
+}
+
+// The same walks with the two per-ray outputs of WalkProbe beside the results (the signatures above stay as they are): peak = the largest
+// number of entries nodes_to_visit held, peak_hit = the same over the entries whose box the slabs hit, tri_margin = the smallest gap of the walk's
+// triangle tests (INF where none was made).
+int oracle_trace_closest_probe(const rrt_scene_desc* d, const double* o, const double* dir, const double* tmax, size_t n,
+                               double* t_out, int32_t* prim_out, double* u_out, double* v_out, uint32_t* nodes, uint32_t* prims,
+                               int mode /* bit0: flat */, double* margin_out, uint32_t* peak_out, double* tri_margin_out, uint32_t* peak_hit_out) {
+  return guarded([&]() {
+    Scene sc{d, (mode & 1) != 0};
+    std::string panic;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long i = 0; i < (long)n; i++) {
+      Ray r; r.o = V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]); r.d = V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]); r.t_max = tmax[i];
+      SI si; HitInfo hi; WalkProbe probe;
+      uint32_t nn = 0, np = 0;
+      double margin = INF;
+      bool hit = false;
+      try { hit = scene_intersect(sc, &r, &si, &hi, nullptr, &nn, &np, &margin, &probe); }
+      catch (const OraclePanic& e) {
+#pragma omp critical
+        if (panic.empty()) panic = e.msg;
+      }
+      t_out[i] = r.t_max;
+      prim_out[i] = hit ? hi.order_index : -1;
+      u_out[i] = hi.u; v_out[i] = hi.v;
+      nodes[i] = nn; prims[i] = np;
+      margin_out[i] = margin; peak_out[i] = probe.peak; tri_margin_out[i] = probe.tri_margin; peak_hit_out[i] = probe.peak_hit;
+    }
+    if (!panic.empty()) throw OraclePanic{panic};
+  });
+}
+int oracle_trace_any_probe(const rrt_scene_desc* d, const double* o, const double* dir, const double* tmax, size_t n, uint8_t* occluded,
+                           uint32_t* nodes, uint32_t* prims, int mode, double* margin_out, uint32_t* peak_out, double* tri_margin_out, uint32_t* peak_hit_out) {
+  return guarded([&]() {
+    Scene sc{d, (mode & 1) != 0};
+    std::string panic;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long i = 0; i < (long)n; i++) {
+      Ray r; r.o = V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]); r.d = V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]); r.t_max = tmax[i];
+      uint32_t nn = 0, np = 0;
+      double margin = INF;
+      WalkProbe probe;
+      try { occluded[i] = scene_intersect_p(sc, r, nullptr, &nn, &np, &margin, &probe) ? 1 : 0; }
+      catch (const OraclePanic& e) {
+#pragma omp critical
+        if (panic.empty()) panic = e.msg;
+      }
+      nodes[i] = nn; prims[i] = np;
+      margin_out[i] = margin; peak_out[i] = probe.peak; tri_margin_out[i] = probe.tri_margin; peak_hit_out[i] = probe.peak_hit;
     }
     if (!panic.empty()) throw OraclePanic{panic};
   });

@@ -152,9 +152,10 @@ class Renderer:
         return occ.astype(bool)
 
     # device-resident variants (raw pointers, e.g. torch tensors' data_ptr()) used by bench.py
-    def trace_closest_device(self, ptrs7, n, t_ptr, prim_ptr, u_ptr=None, v_ptr=None):
-        rays = A.Rays(A.RRT_MEM_DEVICE, self.precision, *ptrs7, None)
-        hits = A.Hits(A.RRT_MEM_DEVICE, self.precision, t_ptr, prim_ptr, u_ptr, v_ptr, None, None)
+    def trace_closest_device(self, ptrs7, n, t_ptr, prim_ptr, u_ptr=None, v_ptr=None, skip_ptr=None, nodes_ptr=None, prims_ptr=None):
+        """nodes_ptr and prims_ptr (both or neither): n uint32 each, the per-ray node / primitive-test counters (rrt_hits::nodes_visited, prims_tested)."""
+        rays = A.Rays(A.RRT_MEM_DEVICE, self.precision, *ptrs7, skip_ptr)
+        hits = A.Hits(A.RRT_MEM_DEVICE, self.precision, t_ptr, prim_ptr, u_ptr, v_ptr, nodes_ptr, prims_ptr)
         _check(A.lib().rrt_trace_closest(self._h, C.byref(rays), n, C.byref(hits)))
 
     def trace_any_device(self, ptrs7, n, occluded_ptr, skip_ptr=None):

@@ -29,6 +29,8 @@ def lib():
         L.oracle_surface_differentials.argtypes = [C.c_void_p, C.c_void_p]
         L.oracle_trace_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         L.oracle_trace_any.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.oracle_trace_closest_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4
+        L.oracle_trace_any_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         L.oracle_camera_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_render_rect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         _lib = L
@@ -81,6 +83,31 @@ def trace_any(scene, o, d, tmax, flat=False):
     _check(lib().oracle_trace_any(_d(scene), o.ctypes.data, d.ctypes.data, tmax.ctypes.data, n, occ.ctypes.data, nodes.ctypes.data, prims.ctypes.data,
                                   1 if flat else 0, margin.ctypes.data))
     return dict(occluded=occ.astype(bool), nodes=nodes, prims=prims, margin=margin)
+
+
+def trace_closest_probe(scene, o, d, tmax, flat=False):
+    """trace_closest and two more per-ray outputs: peak = the largest number of entries the walk's stack held, peak_hit = the same
+    counting only entries whose box the ray's slabs hit (what a walk holds that tests a child's box before it pushes it: the fp32 pair-node kernels), tri_margin = the smallest
+    gap of every comparison of every triangle test the walk made (WalkProbe in rrt_oracle.cpp; inf where it tested none)."""
+    n = len(tmax)
+    o = np.ascontiguousarray(o, np.float64); d = np.ascontiguousarray(d, np.float64); tmax = np.ascontiguousarray(tmax, np.float64)
+    t = np.empty(n); prim = np.empty(n, np.int32); u = np.empty(n); v = np.empty(n)
+    nodes = np.empty(n, np.uint32); prims = np.empty(n, np.uint32)
+    margin = np.zeros(n); peak = np.zeros(n, np.uint32); tri_margin = np.zeros(n); peak_hit = np.zeros(n, np.uint32)
+    _check(lib().oracle_trace_closest_probe(_d(scene), o.ctypes.data, d.ctypes.data, tmax.ctypes.data, n, t.ctypes.data, prim.ctypes.data, u.ctypes.data,
+                                            v.ctypes.data, nodes.ctypes.data, prims.ctypes.data, 1 if flat else 0, margin.ctypes.data, peak.ctypes.data,
+                                            tri_margin.ctypes.data, peak_hit.ctypes.data))
+    return dict(t=t, prim=prim, u=u, v=v, nodes=nodes, prims=prims, margin=margin, peak=peak, tri_margin=tri_margin, peak_hit=peak_hit)
+
+
+def trace_any_probe(scene, o, d, tmax, flat=False):
+    n = len(tmax)
+    o = np.ascontiguousarray(o, np.float64); d = np.ascontiguousarray(d, np.float64); tmax = np.ascontiguousarray(tmax, np.float64)
+    occ = np.zeros(n, np.uint8); nodes = np.empty(n, np.uint32); prims = np.empty(n, np.uint32)
+    margin = np.zeros(n); peak = np.zeros(n, np.uint32); tri_margin = np.zeros(n); peak_hit = np.zeros(n, np.uint32)
+    _check(lib().oracle_trace_any_probe(_d(scene), o.ctypes.data, d.ctypes.data, tmax.ctypes.data, n, occ.ctypes.data, nodes.ctypes.data, prims.ctypes.data,
+                                        1 if flat else 0, margin.ctypes.data, peak.ctypes.data, tri_margin.ctypes.data, peak_hit.ctypes.data))
+    return dict(occluded=occ.astype(bool), nodes=nodes, prims=prims, margin=margin, peak=peak, tri_margin=tri_margin, peak_hit=peak_hit)
 
 
 def camera_samples(scene, rect, s0, s1):
