@@ -577,6 +577,9 @@ int rrt_film_gather_all(rrt_handle* const* handles, void* const* films_device, i
  *                                 every lens interface by the calibrated margin                                  auxiliary-ray displacement measured at scene load (16 384 host
  *                                                                                                                samples of the scene's own lens); validated bit for bit against
  *                                                                                                                the full traces (test_aux_margins_change_nothing)
+ * lens_cull             1  fp32   tiled passes of untextured scenes: camera samples whose (r_film, p_lens) cell   invariant (tests/test_lens_cull.py, tests/test_lens_shapes.py);
+ *                                 the host found dead for the scene's lens are dropped before any lens            the table's own promise: tests/test_lens_cull_table.py
+ *                                 arithmetic, the survivors packed into whole waves before the first interface
  * horizon_cull          1  fp32   path integrator: a bounce ray whose elevation exceeds everything visible from  invariant (test_horizon_cull_changes_nothing);
  *                                 its start triangle in its azimuth sector (host-built tables) is answered as    counted in closest_queries and sky_culled
  *                                 the miss it is, never queued. The tables are built by rrt_create (host, all

@@ -521,7 +521,8 @@ inline void validate_desc(const rrt_scene_desc* d) {
     const rrt_texture& t = d->textures[i];
     if (t.type < RRT_TEX_CONSTANT || t.type > RRT_TEX_IMAGE || t.mapping < RRT_MAP_UV || t.mapping > RRT_MAP_IDENTITY3D) bad("unknown texture / mapping type");
   }
-  if (d->camera.n_elems < 1 || d->camera.n_elems > 64 || !d->camera.elems) bad("camera lens description missing");
+  if (d->camera.n_elems < 1 || !d->camera.elems) bad("camera lens description missing");
+  if (d->camera.n_elems > 64) bad("camera lens has " + std::to_string(d->camera.n_elems) + " interfaces, the limit is 64");
   if (d->film.xres < 1 || d->film.yres < 1) bad("empty film");
   if (d->sampler.type == RRT_SAMPLER_HALTON && d->sampler.n_perms && !d->sampler.perms) bad("Halton permutation table missing");
 }

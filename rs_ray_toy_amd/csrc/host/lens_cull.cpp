@@ -16,7 +16,8 @@
 // only when it AND its 26 neighbours are lattice-dead (erosion by one cell). What that one cell of margin covers:
 //   - the samples between lattice points: the set of passing samples is bounded by smooth surfaces (aperture circles and element rims seen through
 //     smooth refractions, the critical angle), so a passing region that reaches into a dead cell would have to slip between the lattice points of a
-//     3 x 3 x 3 block of cells; tests/test_lens_cull_table.py checks every dead cell on a lattice 4x denser than this one with an independent f64 trace;
+//     3 x 3 x 3 block of cells; tests/test_lens_cull_table.py checks every dead cell on a lattice 4x denser than this one with an independent f64 trace,
+//     and 4 M uniform random samples per lens against the table (a sliver thinner than a quarter cell), also on lenses of 2, 3, 5 and 64 interfaces;
 //   - the kernel's cell index: floor(r_film * inv_dr) and floor((p_lens - 0.5) * 96) in fp32 are off by at most one ulp of the product, far below one
 //     cell, so a sample is looked up in its own cell or a neighbour of it, and every neighbour of a dead cell is lattice-dead;
 //   - the fp32 lean lens arithmetic (dtraverse_f32.hpp rg_begin_lean / rg_step_lean): it evaluates the trace of a sample displaced by its rounding.
@@ -24,7 +25,9 @@
 //     interfaces add ~1e-7 relative each, and the lens does not amplify a displacement of the ray (calibrate_aux_margins() measures c_i = 0.3-0.5
 //     per interface for the scene.json lens), so 13 interfaces move the verdict's argument by < 1e-5 of the pupil extent, while a cell is 1 / 96
 //     of the box (and 1 / 32 of r_max). The margin exceeds the arithmetic's displacement by about three orders of magnitude.
-// The GPU side of the promise is tests/test_lens_cull.py: frames, weights and counters bit-identical with and without the table.
+// (The c_i quoted above are the scene.json lens's. The argument needs only that they are of order 1; on the hand-built prescriptions of tests/lens_shapes.py -
+// a strong singlet with total internal reflection inside the rim among them - the table changed no bit either.)
+// The GPU side of the promise is tests/test_lens_cull.py and tests/test_lens_shapes.py: frames, weights and counters bit-identical with and without the table.
 #include "lens_cull.hpp"
 
 #include <algorithm>

@@ -3,7 +3,9 @@
 The camera kernel drops a sample before any lens arithmetic when its cell over (r_film, p_lens) is marked dead. The builder decides that from f64
 traces at the cell corners with an erosion by one cell; these tests hold it to the promise with an independent f64 restatement of
 trace_lenses_from_film (camera.rs:163-211, the reference's operation order, numpy): every point of a lattice 4x denser than the builder's inside
-every dead cell, cell edges included, is stopped by the lens. The GPU side of the promise is tests/test_lens_cull.py (frames identical bit for bit).
+every dead cell, cell edges included, is stopped by the lens - on the scene.json lens, perturbed copies of it and hand-built prescriptions of 2 to 64
+interfaces (tests/lens_shapes.py) - and of 4 M uniform random samples per lens none that gets through lies in a dead cell. The GPU side of the promise is
+tests/test_lens_cull.py and tests/test_lens_shapes.py (frames identical bit for bit).
 """
 import ctypes as C
 import time
@@ -11,6 +13,7 @@ import time
 import numpy as np
 import pytest
 
+import lens_shapes as LS
 from rs_ray_toy_amd import RRT_FIXED_BVH, Scene, scenes
 from rs_ray_toy_amd import _abi as A
 
@@ -126,6 +129,8 @@ CASES = {
     "random_lens_1": lambda wd: _random_lens_cfg(wd, 1),
     "random_lens_5": lambda wd: _random_lens_cfg(wd, 5),
 }
+# hand-built prescriptions (tests/lens_shapes.py): 2, 3, 5 and 64 rows, a stop at index 0, total internal reflection inside the rim
+CASES.update({name: (lambda wd, name=name: LS.sample_scene(wd, name, xres=256, yres=160)) for name in ("singlet_2", "stop_front_3", "two_singlets_5", "strong_singlet_2", "padded_64")})
 
 
 @pytest.mark.parametrize("which", sorted(CASES))
@@ -164,6 +169,10 @@ def test_dead_cells_are_dead_on_a_denser_lattice(which, workdir):
             ply = pb[1] * (1.0 - ly) + pb[3] * ly
             through = trace_through(elems, rf, plx, ply)
             assert not through.any(), f"box {b}: {int(through.sum())} lattice points of dead cells get through, e.g. cell {cc[np.argmax(through) // su.size]}"
+    if which == "padded_64":      # open stop planes behind the real stop: the builder traces the same lens, and the table is the double Gauss's bit for bit
+        cfg13, root13 = LS.sample_scene(workdir, "double_gauss_13", xres=256, yres=160)
+        dead13, r_max13, inv_dr13, *_ = lens_cull(Scene.loads(cfg13, root13, flags=RRT_FIXED_BVH))
+        assert r_max13 == r_max and inv_dr13 == inv_dr and np.array_equal(dead13, dead)
 
 
 def test_the_table_culls_what_it_should(workdir):
@@ -184,3 +193,40 @@ def test_the_table_culls_what_it_should(workdir):
     through = trace_through(_elems(sc), (cr[use] + 0.5) * dr, pb[0] * (1.0 - lx) + pb[2] * lx, pb[1] * (1.0 - ly) + pb[3] * ly)
     assert not (through & dead[0][use]).any()
     assert through.mean() > 0.2 and (~dead[0][use]).mean() > through.mean()
+
+
+RANDOM_CASES = {
+    "double_gauss_13": {},
+    "double_gauss_13_diagonal_70": dict(diagonal=70),
+    "double_gauss_13_aperture_2": dict(aperture_diameter=2),
+    "singlet_2": {},
+    "two_singlets_5": {},
+    "stop_front_3_aperture_3": dict(aperture_diameter=3),
+}
+
+
+@pytest.mark.parametrize("which", sorted(RANDOM_CASES))
+def test_no_random_sample_passes_in_a_dead_cell(which, workdir):
+    """4 M uniform (r_film, p_lens) samples over the table's domain, the exit-pupil box chosen as the kernel chooses it, traced in f64: none that gets
+    through lies in a dead cell. The lattice test above cannot see a passing sliver thinner than a quarter cell; this one can."""
+    name = which.split("_diagonal")[0].split("_aperture")[0]
+    cfg, root = LS.sample_scene(workdir, name, xres=256, yres=160, **RANDOM_CASES[which])
+    sc = Scene.loads(cfg, root, flags=RRT_FIXED_BVH)
+    dead, r_max, inv_dr, share, traces, secs = lens_cull(sc)
+    assert dead.any(), "no cell culled"
+    elems, cam, film = _elems(sc), sc.desc.camera, sc.desc.film
+    rng = np.random.default_rng(20)
+    n_through = n_dead = 0
+    for _ in range(8):
+        n = 500_000
+        rf, lx, ly = rng.random(n) * r_max, 0.5 + rng.random(n), 0.5 + rng.random(n)
+        box = (rf / (film.diagonal / 2.0) >= 1.0).astype(int)      # rg_begin_lean's choice (Q6)
+        pb = np.array([list(cam.exit_pupil_bounds[0]), list(cam.exit_pupil_bounds[63])])[box]
+        through = trace_through(elems, rf, pb[:, 0] * (1.0 - lx) + pb[:, 2] * lx, pb[:, 1] * (1.0 - ly) + pb[:, 3] * ly)
+        cr, cx, cy = np.minimum((rf * (KR / r_max)).astype(int), KR - 1), np.minimum(((lx - 0.5) * KX).astype(int), KX - 1), np.minimum(((ly - 0.5) * KY).astype(int), KY - 1)
+        in_dead = dead[box, cr, cy, cx]
+        n_through += int(through.sum()); n_dead += int(in_dead.sum())
+        bad = through & in_dead
+        assert not bad.any(), f"{int(bad.sum())} passing samples in dead cells, e.g. r_film {rf[bad][0]}, p_lens ({lx[bad][0]}, {ly[bad][0]}), box {box[bad][0]}"
+    print(f"{which}: {share:.3f} of the cells dead; of 4 M samples {n_through} get through, {n_dead} lie in dead cells, none does both")
+    assert n_through > 0 and n_dead > 0
