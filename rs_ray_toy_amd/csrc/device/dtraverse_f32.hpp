@@ -44,28 +44,6 @@ constexpr int kTravBlock = 512;     // 8 waves share one LDS copy of the treelet
 constexpr int kStackLds = 8;        // LDS stack entries per thread (8 B each); deeper entries spill to global (>= kAnyList: a list starts on the LDS part)
 constexpr int kTreeletNodes = 512;  // top of the tree (BFS order) staged in LDS: 512 pair nodes = 32 KB
 
-// Field order chosen for the packed fp32 VALU forms (v_pk_add_f32 / v_pk_mul_f32 work on aligned register pairs, and a 128-bit load
-// lands in four consecutive registers): every 64-bit half of the three box words pairs two plane coordinates with the SAME ray
-// constants - (x, y) against (o.x, o.y) / (inv.x, inv.y), (z, z) against o.z / inv.z - so the 24 subtract / multiply operations of the two
-// slab tests are 12 packed instructions. The child words are what the traversal stack holds, ready made.
-struct alignas(64) PairNode {
-  float xy0[4];               // first child (linear index + 1):  bmin.x, bmin.y, bmax.x, bmax.y
-  float xy1[4];               // second child:                    bmin.x, bmin.y, bmax.x, bmax.y
-  float zz[4];                // first child bmin.z, bmax.z, second child bmin.z, bmax.z
-  uint32_t id0, id1;          // child words: interior = byte offset of its PairNode (bit 31 clear); leaf = kLeafBit | kSpecialLeaf? | n_prims << 19 | first triangle
-  uint32_t axis;              // split axis (bvh.rs:183-236: dir_is_neg[axis] visits the second child first)
-  uint32_t pad;
-};
-constexpr uint32_t kLeafBit = 0x80000000u;
-// Leaf word = kLeafBit | kSpecialLeaf? | n_prims (11 bits) << 19 | first primitive (19 bits). kSpecialLeaf: the leaf holds a primitive that is
-// not a world-space triangle - a sphere (Tri::plane == kSphereMark) or a triangle of a kept instance (Tri::material & kInstFlag, tested in
-// object space through the instance's own ray transform, primitives.rs:115-139) - and takes the rare path special_leaf_f32(); only the
-// MIXED instantiations of the kernels look at the bit (scenes without such primitives never set it).
-constexpr uint32_t kSpecialLeaf = 0x40000000u;
-constexpr uint32_t kLeafCountMask = 0x7ffu;
-// t_max of the pool's shadow rays (spawn_ray_to: 1 - SHADOW_EPSILON with a unit direction, Q9): the any-hit kernels give every pool shadow
-// ray this length, and the host's any-hit start lists (build_pairs()) derive their reach from the same constant
-constexpr float kShadowTmax = 1.0f - 0.0001f;
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 struct F4 { float x, y, z, w; };
@@ -88,7 +66,7 @@ struct LaneRay {
 //                1 + 2 gamma(3) on the far planes absorbs: 24 subtract / multiply operations per pair node (12 packed instructions, half rate).
 //  RRT_SLAB_FMA  t = fma(b, inv, -(o * inv)): 12 full-rate instructions per pair node, no subtraction. The rounding of o * inv is an ABSOLUTE error in t
 //                of u |o| |inv| (u = 2^-24), i.e. a plane shifted by up to u (2 |o| + |b|) in world units; the host pads every fp32 box outward by
-//                kSlabPadUlps u M (M = the largest coordinate of the root box and of the camera, rrt_impl.hpp upload_scene), so a box the exact
+//                kSlabPadUlps u M (M = the largest coordinate of the root box and of the camera, host/scene_flatten.cpp flatten_scene), so a box the exact
 //                arithmetic hits is never missed - conservative like the reference's test, for rays that start within M of the world origin.
 //                |inv| is clamped to 1e30 so that an axis-parallel ray gives +-huge plane distances of the right sign instead of inf - inf.
 RRT_DEV void lane_ray_set_inv(LaneRay& r) {
@@ -213,9 +191,6 @@ struct TravScene {
 
 // A lane's position in the walk is one child word: an interior node to visit (byte offset of its PairNode, < kIdle), a leaf to test
 // (kLeafBit set), or kIdle. The traversal stack holds the same words with the child's entry distance.
-constexpr uint32_t kIdle = 0x7fffffffu;
-constexpr uint32_t kSkip0 = 1u, kSkip1 = 2u;   // any-hit list entries (TravScene::any_list): low bits of an interior child word
-constexpr int kAnyList = 6;                    // flagged entries per list
 RRT_DEV bool is_node(uint32_t w) { return w < kIdle; }
 RRT_DEV bool is_leaf(uint32_t w) { return (int32_t)w < 0; }
 
@@ -427,14 +402,6 @@ __global__ void __launch_bounds__(kTravBlock) k_trace_pairs_f32(TravScene ts, Po
 // The three split axes ride in bits 28-29 of the first three child words (leaf words keep 9 bits of primitive count, interior words are
 // byte offsets below 2^28).
 // ------------------------------------------------------------------------------------------------------------
-struct alignas(128) QuadNode {
-  float mnx[4], mny[4], mnz[4];   // bmin of the four slots, one axis per 16-byte word
-  float mxx[4], mxy[4], mxz[4];   // bmax
-  uint32_t id[4];                 // child words (interior: byte offset of its QuadNode); bits 28-29: split axis of N / of its first child / of its second child / -
-  uint32_t pad[4];
-};
-constexpr uint32_t kQuadAxisShift = 28u, kQuadAxisMask = 3u << 28;
-constexpr uint32_t kQuadLeafMax = 511u;   // primitives per leaf the stolen bits leave room for
 #ifndef RRT_QUAD_TREELET
 #define RRT_QUAD_TREELET 32
 #endif
@@ -725,7 +692,7 @@ __global__ void __launch_bounds__(kPtBlock) RRT_PT_ATTR k_trace_pt_f32(TravScene
 // The camera rays of a 32 x 32-pixel patch of the image - some 80 000 of them at 256 spp - visit 260-290 DISTINCT interior nodes of config 4's
 // 49 000 (tools/tile_subtree_stats.py: an 8 x 8 tile 64-150, 16 x 16 170-205), 33-55 each: their node fetches are the same few hundred lines
 // over and over, through the unit the persistent kernel keeps busiest (the vector L1: 39 cycles per 64-lane gather instruction against 8 for
-// a ds_read_b128). Per patch the host lists the kTtNodes pair nodes its rays visit most (rrt_impl.hpp build_tile_trees(): a census with a few
+// a ds_read_b128). Per patch the host lists the kTtNodes pair nodes its rays visit most (host/trav_tables.cpp build_tile_trees(): a census with a few
 // camera rays per pixel; counts only decide WHICH nodes are copied) and stores a local copy of them whose child words say "slot k of this
 // copy" (byte offsets below kTtNodes * 64) or "node n of the whole tree" (offsets from there on: TravScene::pairs of this launch is a copy of
 // the whole tree behind kTtNodes unused slots, its interior child words shifted alike). Boxes, leaf words and split axes are the tree's own,
@@ -772,7 +739,6 @@ constexpr int kTtBlock = RRT_TT_BLOCK, kTtStack = RRT_TT_STACK;
 constexpr uint32_t kTtNodes = RRT_TT_NODES;      // pair nodes per local copy (15 KB + 64 KB of stacks: two workgroups per CU, 8 waves per SIMD)
 // LDS byte address of slot k of a copy = the child word that names it (see the kernel): 16 bytes of padding after every four slots, so that slots
 // never overlap and the lanes of one read spread over every bank group. kTtLocalBytes: the first byte offset that means "node of the whole tree".
-constexpr uint32_t tt_local_addr(uint32_t k) { return 64u * k + 16u * (k >> 2); }
 constexpr uint32_t kTtLocalBytes = (tt_local_addr(kTtNodes - 1u) + 64u + 63u) & ~63u;
 constexpr bool tt_local_layout_ok() { for (uint32_t k = 0; k + 1u < kTtNodes; k++) if (tt_local_addr(k + 1u) < tt_local_addr(k) + 64u) return false; return true; }
 static_assert(tt_local_layout_ok() && kTtLocalBytes + kTtTris * 48u + (uint32_t)kTtStack * kTtBlock * 8u + 8u <= (160u * 1024u) / RRT_TT_WG_PER_CU - 512u, "tile trees: LDS layout / budget");
@@ -970,15 +936,13 @@ __global__ void __launch_bounds__(kTtBlock) __attribute__((amdgpu_waves_per_eu(R
 // hit" - the tree only finds those leaves. A pool shadow ray starts on a known triangle T, is kShadowTmax long (Q9) and points at a light
 // whose position (point lights: all at the world origin, Q17) or direction (distant lights) is fixed: the leaves such a ray can reach at all
 // are few and can be listed per (light, T) at scene load - the host sweeps T towards the light over the ray's length, fattens that prism by
-// the spread of directions over T and by the fp32 slack, and collects every leaf whose box meets it (rrt_impl.hpp build_shadow_lists()).
+// the spread of directions over T and by the fp32 slack, and collects every leaf whose box meets it (host/shadow_lists.cpp build_shadow_lists()).
 // Here a ray runs down its list: the reference's own slab test on each leaf's box (same function, same box), the reference's triangle tests on
 // the leaves that pass. Same boxes tested as the walk would test at the leaves, less the ones that cannot pass; same verdict, bit for bit
 // (tests/test_gpu_parity.py::test_shadow_candidate_lists_change_nothing). 17.8 pair-node steps per shadow ray become ~8 leaf-box tests.
 // A triangle without a list (light closer than a few triangle sizes, more than kShadowListMax candidates) walks the tree right here.
 // ------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kShadowListMax = 48u;        // candidates per (light table, triangle); 0xff in the header = no list: walk the tree
 constexpr uint32_t kShadowTabShift = 24u;       // a pool shadow ray's start word: triangle (24 bits) | light table + 1 (bits 24-27)
-struct LeafRec { float bmin[3]; uint32_t word; float bmax[3]; uint32_t pad; };   // a BVH leaf: its (fp32, outward) box and its leaf word
 struct ShadowLists {
   const uint32_t* headers;   // [table][triangle]: (first entry / 4) << 8 | count (0xff: none)
   const uint32_t* entries;   // leaf ids
@@ -1229,7 +1193,7 @@ RRT_DEV float rg_begin_lean(const SceneDev<float>& s, float pfx, float pfy, floa
 // kernels step all lanes together): the element is a scalar operand and stop-vs-sphere is a scalar branch. Returns false = blocked.
 // `safe` (optional): cleared unless this interface is passed with the margin within which an auxiliary ray (0.05 px beside this one)
 // cannot be blocked either: radius below aperture - 16 c_i m (safe_lim = {aperture, 16 c_i}, m = the sample's displacement scale),
-// parameter t above 4 x that margin, away from grazing incidence and from total internal reflection (rrt_impl.hpp
+// parameter t above 4 x that margin, away from grazing incidence and from total internal reflection (host/scene_flatten.cpp
 // calibrate_aux_margins()).
 RRT_DEV bool rg_step_lean(const float4 el, const float2 el2, RgLane* L, const float2 safe_lim = make_float2(0.0f, 0.0f), float m = 0.0f, bool* safe = nullptr) {
   L->element_z -= el.y;

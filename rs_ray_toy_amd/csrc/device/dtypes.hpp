@@ -7,132 +7,8 @@
 #include <stdint.h>
 
 #include "horizon_build.hpp"   // hz_sector(): shared with the host builder
+#include "records.hpp"          // Node, Tri, Material, Light, ... : the plain records, shared with the host scene preparation
 namespace rrtd {
-// LinearBVHNode bvh.rs:103-109, narrowed: f32 = 32 B (bounds rounded outward from the f64 build), f64 = 64 B.
-// Block tables of a sampler dimension's digit loop (fp32 mode): the sample index is split as hi * block + lo, block = base^low_digits;
-// lo[lo_off + lo] = the permuted reversal of exactly low_digits digits, hi[hi_off + hi] = {permuted reversal of hi's digits, base^(digits of hi),
-// the two words of the f64 inv_base^(all digits) the loop's running product arrives at}. See scrambled_radical_inverse_tab() in dmath.hpp.
-struct HaltonBlk {
-  uint32_t block;         // 0 = no table for this dimension
-  uint32_t shift;         // l - 1 of the division by `block` (div_base())
-  uint32_t magic;         // m'
-  uint32_t lo_off, hi_off;
-  uint32_t pad[3];
-};
-
-template <typename R>
-struct alignas(sizeof(R) * 8) Node {
-  R bmin[3];
-  R bmax[3];
-  uint32_t offset;   // leaf: first triangle (traversal order); interior: second child
-  uint32_t meta;     // n_primitives << 2 | axis
-  // f64: 48 + 8 = 56 -> padded to 64 by alignas
-};
-
-// One triangle = 3 world-space vertices + 3 words (48 B in f32). Read by the traversal kernels.
-template <typename R>
-struct alignas(16) Tri {
-  R p0[3], p1[3], p2[3];
-  uint32_t material;   // index into materials
-  uint32_t shade;      // index into TriShade (0xffffffff: no normals / uvs -> defaults)
-  uint32_t plane;      // id shared by exactly coplanar triangles (host, see plane_ids()); used by self_prim()
-};
-
-// A sphere primitive of the aggregate occupies one Tri slot (so node.offset still indexes one array in traversal
-// order): plane == kSphereMark, shade = index into SceneDev::spheres, material as usual.
-constexpr uint32_t kSphereMark = 0xfffffffeu;
-
-// A triangle of a NON-RIGID instance (scale / shear) is not flattened either: the reference transforms the ray into the instance's space,
-// re-normalises its direction there and copies the object-space t back to the world ray (TransformedPrimitive::intersect
-// primitives.rs:115-139, transform.rs:525-537: Q15), which no world-space triangle reproduces. Such a Tri keeps the mesh's raw vertices
-// and carries its instance in the material word: kInstFlag | instance index (15 bits) << 16 | material (16 bits). Its plane id is
-// computed from the world-space vertices like everybody's (coplanarity is the same in both spaces).
-constexpr uint32_t kInstFlag = 0x80000000u;
-template <typename R>
-struct InstDev {
-  R m[12], mi[12];      // primitive_to_world / its inverse, rows 0..2
-  uint32_t identity;    // Transform::is_identity (value compare): the interaction is not transformed then
-  uint32_t pad[3];
-};
-
-// Sphere (shape/sphere.rs:14-49) + the TransformedPrimitive around it (primitives.rs:100-139). Spheres are not
-// flattened: the reference's own sequence of ray transforms is replayed, including its quirks (Q15, Q16).
-template <typename R>
-struct SphereDev {
-  R m[12], mi[12];       // the sphere's obj_to_world / world_to_obj (rows 0..2)
-  R im[12], imi[12];     // instance primitive_to_world / its inverse
-  R radius, z_min, z_max, theta_min, theta_max, phi_max;
-  uint32_t has_inst;     // 0: GeometricPrimitive used directly; 1: wrapped in a TransformedPrimitive
-  uint32_t inst_identity;  // TransformedPrimitive::intersect skips the interaction transform for the identity
-};
-
-// Optional per-triangle shading attributes (meshes with vn / vt), world space.
-template <typename R>
-struct TriShade {
-  R n[3][3];
-  R uv[3][2];
-  uint32_t has_n, has_uv;  // mesh_has_* of rrt_tri (0,1,2)
-};
-
-template <typename R>
-struct Material {
-  int32_t type, remap_roughness;
-  R kd[3], ks[3], kr[3], eta[3], k[3];
-  R sigma, roughness, u_roughness, v_roughness;
-  R kt[3], reflect[3], transmit[3], index;   // glass / translucent
-  int32_t tex[13];       // RRT_P_* slot -> SceneDev::textures index evaluated at every hit, -1 = the constant above
-  int32_t has_tex;       // any slot >= 0
-  int32_t bump, pad;     // bump_map texture (Material::bump), -1 = none
-};
-
-// one node of the texture graph (rrt_texture, include/rrt.h): float textures carry their value in all three channels
-template <typename R>
-struct TexDev {
-  int32_t type, mapping, aa_none, octaves;
-  int32_t child[3], image;   // image: index into SceneDev::images (ImageTexture)
-  R fallback[3][3];
-  R v[4][3];
-  R omega;
-  R map[4];
-  R vs[3], vt[3];
-  R w2t[12];             // world_to_texture rows 0..2 (affine; the loader only composes T * R * S)
-};
-
-// MIPMap (rrt_image, include/rrt.h): per level the BlockedArray's data vector as the reference's index expression fills it
-struct ImageLevelDev { uint32_t u_res, v_res, u_blocks, n; uint32_t offset, pad[3]; };   // offset / n in texels of SceneDev::image_texels
-template <typename R>
-struct ImageDev {
-  int32_t do_trilinear, wrap, n_levels, pad;
-  R max_aniso, pad2;
-  ImageLevelDev levels[16];
-};
-
-template <typename R>
-struct Light {
-  int32_t type, shape_type;
-  R spectrum[3];
-  R p_light[3];
-  R area;
-  // sphere light shape (object space + transform) / triangle light shape (raw mesh vertices, Q13)
-  R m[12], mi[12];                 // obj_to_world rows 0..2 (affine), and inverse
-  R radius, z_min, z_max, theta_min, theta_max, phi_max;
-  R tp[3][3];                      // triangle vertices
-  R tn[3][3];                      // triangle vertex normals (if tri_has_n)
-  uint32_t tri_has_n;
-  R w_light[3], world_radius;      // DistantLight (lights/distant.rs)
-  uint32_t shadow_tab;             // fp32: shadow candidate table of this light + 1 (dtraverse_f32.hpp), 0 = none
-};
-
-template <typename R>
-struct LensElem { R curvature_radius, thickness, eta, aperture_radius; };
-
-struct HaltonDim {   // one entry per sampler dimension >= 2
-  uint32_t base;
-  uint32_t perm_offset;   // PRIME_SUMS[dim]
-  uint64_t magic;         // m' | (l - 1) << 32 of div_base(): exact a / base for every 32-bit a
-  double inv;             // 1 / base: a / base for any 32-bit a = (uint32_t)(a * inv) with a +-1 fix-up (div_base())
-  double tail;            // inv * perm[0] / (1 - inv): the infinitely many trailing zero digits of the scrambled radical inverse
-};
 
 template <typename R>
 struct SceneDev {

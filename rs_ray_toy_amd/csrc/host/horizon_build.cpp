@@ -2,7 +2,9 @@
 #include "horizon_build.hpp"
 #include <algorithm>
 #include <atomic>
+#include <deque>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -394,6 +396,27 @@ HzTables build_horizons(const HzNode* nodes, size_t n_nodes, const HzTri* tris, 
     res.checked = tested; res.check_hits = hits;
   }
   return res;
+}
+
+// Horizon tables (host/horizon_build.cpp) are a function of the fp32 geometry alone, and a process usually opens several handles on one scene (an fp32 and an f64
+// one, one per stream, a bench's second configuration): the last few results are kept, keyed by the CONTENT of the builder's input (never by address).
+std::shared_ptr<const HzTables> horizons_cached(const std::vector<HzNode>& hn, const std::vector<HzTri>& ht, long check_rays, bool* was_cached) {
+  struct Entry { uint64_t key[2]; size_t n_nodes, n_tris; std::shared_ptr<const HzTables> tab; };
+  static std::mutex mu;
+  static std::deque<Entry> kept;
+  auto hash = [](const void* p, size_t n, uint64_t h) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 0x100000001b3ull; } return h; };
+  const uint64_t k0 = hash(ht.data(), ht.size() * sizeof(HzTri), hash(hn.data(), hn.size() * sizeof(HzNode), 0xcbf29ce484222325ull));
+  const uint64_t k1 = hash(hn.data(), hn.size() * sizeof(HzNode), hash(ht.data(), ht.size() * sizeof(HzTri), 0x9e3779b97f4a7c15ull));
+  *was_cached = false;
+  if (check_rays <= 0) {   // (a self-check wants the build to happen)
+    std::lock_guard<std::mutex> lk(mu);
+    for (const Entry& e : kept) if (e.key[0] == k0 && e.key[1] == k1 && e.n_nodes == hn.size() && e.n_tris == ht.size()) { *was_cached = true; return e.tab; }
+  }
+  auto tab = std::make_shared<const HzTables>(build_horizons(hn.data(), hn.size(), ht.data(), ht.size(), check_rays));
+  std::lock_guard<std::mutex> lk(mu);
+  kept.push_back(Entry{{k0, k1}, hn.size(), ht.size(), tab});
+  while (kept.size() > 4u) kept.pop_front();
+  return tab;
 }
 }  // namespace rrtd
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <vector>
 #include <cmath>
 
@@ -34,4 +35,6 @@ struct HzTables {
   long checked = 0, check_hits = 0;   // self-check (check_rays > 0): rays declared free / those of them that hit a triangle (must be 0)
 };
 HzTables build_horizons(const HzNode* nodes, size_t n_nodes, const HzTri* tris, size_t n_tris, long check_rays);
+// build_horizons() behind a small process-wide cache keyed by the content of its input (several handles on one scene build once); check_rays > 0 always builds
+std::shared_ptr<const HzTables> horizons_cached(const std::vector<HzNode>& hn, const std::vector<HzTri>& ht, long check_rays, bool* was_cached);
 }  // namespace rrtd

@@ -1,6 +1,6 @@
 """Hand-built BVH shapes over the triangles of a loaded scene. Test infrastructure only.
 
-include/rrt.h lets a caller fill the scene description, and validate_desc (rrt_impl.hpp) checks the links, the pre-order and the depth bound of a
+include/rrt.h lets a caller fill the scene description, and validate_desc (host/scene_flatten.cpp) checks the links, the pre-order and the depth bound of a
 caller's tree before anything reaches a device - so a hand-built tree is legitimate input, and the only way to walk the traversal kernels through
 tree shapes the project's own builder never makes: chains deeper than the 8-entry LDS stacks and than the 64-entry private stack, a root that is a
 leaf, leaves at the limits of the pair-node and quad-node leaf words.

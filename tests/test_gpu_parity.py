@@ -557,7 +557,7 @@ def test_any_hit_entry_nodes_change_nothing(which, workdir):
     if which == "cfg4": cfg, root = scenes.cfg4(workdir, xres=128, yres=128, nsamp=9, max_depth=6, n=96)
     elif which == "cfg4_far":
         # the scene 1e5 units from the origin (an instance translation; camera moved along): fp32 coordinates there have an ulp of 0.008, which
-        # the lists' reach must cover on top of the ray length (rrt_impl.hpp build_pairs(): 8 ulp of the largest coordinate)
+        # the lists' reach must cover on top of the ray length (host/trav_tables.cpp build_pairs(): 8 ulp of the largest coordinate)
         cfg, root = scenes.cfg4(workdir, xres=128, yres=128, nsamp=9, max_depth=6, n=96)
         far = np.array([1.0e5, -7.0e4, 3.0e4])
         cfg["Aggregate"]["primitives"][0]["instances"] = [{"world_pos": list(far)}]
@@ -589,7 +589,7 @@ def test_any_hit_entry_nodes_change_nothing(which, workdir):
 def test_shading_kernel_specialisation(which, workdir):
     """The path shading kernel is instantiated per lobe-kind set (dmath.hpp "Lobe-kind sets"): scenes whose used materials can only produce
     Lambertian lobes, or Lambertian / Oren-Nayar / microfacet-reflection lobes, run a kernel without the other BxDFs' code and registers; the
-    host picks the set from the materials (rrt_impl.hpp scan_materials()). Same arithmetic per lobe in every instantiation - the compiler may
+    host picks the set from the materials (host/scene_flatten.cpp scan_materials()). Same arithmetic per lobe in every instantiation - the compiler may
     contract multiply-adds differently, so the frames agree to fp32 rounding, not bitwise; weights and query counts are identical - and both
     hold the fp32 bar against the oracle. cfg2_mixed uses a mirror: only the general kernel fits, the option changes nothing at all."""
     if which == "cfg4_lambert": cfg, root = scenes.cfg4(workdir, xres=96, yres=96, nsamp=9, max_depth=6, n=64)
@@ -656,7 +656,7 @@ def test_tile_order_of_the_pixels_changes_nothing(which, workdir):
 @pytest.mark.parametrize("which", ["cfg4", "cfg4_odd_width", "cfg4_two_groups", "cfg4_bands", "cfg4_direct", "cfg4_passes", "cfg2_small_tree", "cfg4_2048"])
 def test_tile_trees_change_nothing(which, workdir):
     """Camera rays walk the tree through per-patch local copies of its most visited pair nodes in LDS (dtraverse_f32.hpp k_trace_tiles_f32,
-    rrt_impl.hpp build_tile_trees()): the copies hold the tree's own boxes, leaf words and split axes - only the child words of a copy say
+    host/trav_tables.cpp build_tile_trees()): the copies hold the tree's own boxes, leaf words and split axes - only the child words of a copy say
     "slot k of this copy" or "node n of the tree" - and the queue is not reordered, so every ray makes the same decisions in the same order
     whatever the census chose to copy. Frames, weights and query counts with and without are identical bit for bit: whole 32-pixel patches and
     a width of 13 tiles, one and two sample groups per tile, a rank's bands, DirectLighting's first level, a 2048^2 film (more 8 x 8 tiles than one grid
@@ -739,7 +739,7 @@ def test_quad_nodes_change_nothing(which, workdir):
 @pytest.mark.parametrize("which", ["cfg4", "rough_1", "rough_2", "rough_z_up", "cfg2", "cfg3", "cfg5", "stacked", "cfg4_passes", "boxes_1", "boxes_2", "cfg4_compat_bvh"])
 def test_horizon_cull_changes_nothing(which, workdir, monkeypatch):
     """The path shading kernel answers a bounce ray as the miss it is when its elevation exceeds everything the host found visible from ANY point of its start
-    triangle in its azimuth sector (rrt_impl.hpp build_horizons(): per triangle 2 x 16 quantised horizons about the scene's flattest axis; touching neighbours bounded
+    triangle in its azimuth sector (host/horizon_build.cpp build_horizons(): per triangle 2 x 16 quantised horizons about the scene's flattest axis; touching neighbours bounded
     through the cone of their vertex differences, far geometry node by node). Three of four bounce rays leave an open terrain, each after walking the ~18 ancestors of
     its own leaf. Frames, weights and query counts (the culled rays stay closest-hit queries, rrt_render_stats::sky_culled) are identical bit for bit with and without:
     the gentle BASELINE terrain, steep noisy ones (valleys whose walls start on a triangle's own edge; also with z as the flat axis), the reference's tilted cubes and
@@ -881,7 +881,7 @@ def test_root_cull_changes_nothing(which, workdir):
 @pytest.mark.parametrize("which", ["cfg4", "cfg4_distant", "cfg4_far", "cfg2", "cfg3", "cfg3_direct", "cfg5_area", "cfg5_area_near", "cfg5_area_xform"])
 def test_shadow_candidate_lists_change_nothing(which, workdir):
     """Shadow rays towards point / distant lights run down a per-(light, triangle) list of candidate leaves instead of walking the tree
-    (dtraverse_f32.hpp k_shadow_lists_f32, rrt_impl.hpp build_shadow_lists()): a leaf's box test implies its ancestors', an occlusion query does
+    (dtraverse_f32.hpp k_shadow_lists_f32, host/shadow_lists.cpp build_shadow_lists()): a leaf's box test implies its ancestors', an occlusion query does
     not depend on the order, and the host lists every leaf whose box can meet a ray that starts on the triangle and points at the light. The
     same slab test on the same leaf boxes, the same triangle tests: frames and query counts with and without the lists are identical bit for
     bit - mesh at the origin and 1e5 units away, axis-aligned instanced cubes, an enclosure whose light sits inside it. Sphere-shaped area
@@ -1001,7 +1001,7 @@ AUX_CASES.update({f"random_lens_{seed}": _random_lens(seed) for seed in range(1,
 @pytest.mark.parametrize("which", sorted(AUX_CASES))
 def test_aux_margins_change_nothing(which, workdir):
     """The fp32 camera kernels do not trace the auxiliary rays of generate_ray_differential (camera.rs:582-628) for a main ray that
-    clears every lens interface by 16x the measured displacement of an auxiliary ray (rrt_impl.hpp calibrate_aux_margins()); all
+    clears every lens interface by 16x the measured displacement of an auxiliary ray (host/scene_flatten.cpp calibrate_aux_margins()); all
     they decide on untextured scenes is whether the sample keeps its weight. Bar: with and without the shortcut every sample has
     the same weight and the frames are identical bit for bit - and the shortcut must actually be taken for most survivors."""
     cfg, root = AUX_CASES[which](workdir)
