@@ -15,6 +15,7 @@
 //
 // Build: g++ -O2 -ffp-contract=off (no FMA contraction: Rust does not contract) -fopenmp.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -1389,6 +1390,13 @@ void tex_map_2d(const rrt_texture& t, const SI& si, double st[2], double dstdx[2
 inline double bump_int(double x) { return std::floor(x / 2.0) + 2.0 * rmax(x / 2.0 - std::floor(x / 2.0) - 0.5, 0.0); }   // checkerboard.rs:46-48
 
 // ---- MIPMap lookups mipmap.rs:98-268 over the level storage the loader built (rrt_image, include/rrt.h) ----------------
+// Lookup census (oracle_mip_census): which branch of the lookups below every call took, so that a test frame can be shown to reach the branch it
+// is named after from the reference side. The counters only count (relaxed: frames render on several threads); no result reads them.
+enum MipCensus { MC_TRI_BELOW, MC_TRI_LAST, MC_TRI_BETWEEN, MC_EWA_DEGENERATE, MC_EWA_CLAMPED, MC_EWA_PLAIN, MC_EWA_NAN, MC_EWA_OK,
+                 MC_TEXEL_OUT, MC_TEXEL_IN, MC_TRIANGLE_NEGATIVE, MC_COUNT };
+std::atomic<uint64_t> g_mip_census[MC_COUNT];
+inline void mip_count(MipCensus k) { g_mip_census[k].fetch_add(1, std::memory_order_relaxed); }
+
 struct OracleMip {
   const rrt_scene_desc* d;
   const rrt_image& im;
@@ -1403,6 +1411,7 @@ struct OracleMip {
   Rgb texel(size_t level, size_t s, size_t t) const {   // :107-131
     if (level >= levels()) throw OraclePanic{"mipmap.rs:108 assert!(level < self.pyramid.len())"};
     const rrt_image_level& L = im.levels[level];
+    mip_count(s >= L.u_res || t >= L.v_res ? MC_TEXEL_OUT : MC_TEXEL_IN);
     size_t ts = 0, tt = 0;
     if (im.wrap == RRT_WRAP_REPEAT) { ts = s - (s / L.u_res) * L.u_res; tt = t - (t / L.v_res) * L.v_res; }
     else if (im.wrap == RRT_WRAP_BLACK) { if (s >= L.u_res || t >= L.v_res) return Rgb(); }   // in range: texel (0, 0), as written there
@@ -1413,6 +1422,7 @@ struct OracleMip {
     level = level > levels() - 1 ? levels() - 1 : level;
     const rrt_image_level& L = im.levels[level];
     const double s = st[0] * (double)L.u_res - 0.5, t = st[1] * (double)L.v_res - 0.5;
+    if (s < 0.0 || t < 0.0) mip_count(MC_TRIANGLE_NEGATIVE);
     const size_t s0 = f2usize(std::floor(s)), t0 = f2usize(std::floor(t));
     const double ds = s - std::trunc(s), dt = t - std::trunc(t);   // f64::fract
     return texel(level, s0, t0) * (1.0 - ds) * (1.0 - dt) + texel(level, s0, t0 + 1) * (1.0 - ds) * dt + texel(level, s0 + 1, t0) * ds * (1.0 - dt) +
@@ -1420,8 +1430,9 @@ struct OracleMip {
   }
   Rgb lookup_w(const double st[2], double width) const {   // :132-149
     const double level = (double)levels() - 1.0 + std::log2(rmax(width, 1e-8));
-    if (level < 0.0) return triangle(0, st);
-    if (level >= (double)(levels() - 1)) return texel(levels() - 1, 0, 0);
+    if (level < 0.0) { mip_count(MC_TRI_BELOW); return triangle(0, st); }
+    if (level >= (double)(levels() - 1)) { mip_count(MC_TRI_LAST); return texel(levels() - 1, 0, 0); }
+    mip_count(MC_TRI_BETWEEN);
     const size_t il = f2usize(std::floor(level));
     const double delta = level - std::trunc(level);
     return triangle(il, st) * (1.0 - delta) + triangle(il + 1, st) * delta;
@@ -1458,6 +1469,7 @@ struct OracleMip {
         }
       }
     }
+    mip_count(sum_wts > 0.0 ? MC_EWA_OK : MC_EWA_NAN);   // (sum_wts is a sum of positive weights: zero only where no texel passed r2 < 1)
     return sum / sum_wts;
   }
   Rgb lookup_d(const double st[2], const double dstdx[2], const double dstdy[2]) const {   // :150-192
@@ -1470,12 +1482,14 @@ struct OracleMip {
     else { dst0[0] = dstdx[0]; dst0[1] = dstdx[1]; dst1[0] = dstdy[0]; dst1[1] = dstdy[1]; }
     const double major_length = std::sqrt(dst0[0] * dst0[0] + dst0[1] * dst0[1]);
     double minor_length = std::sqrt(dst1[0] * dst1[0] + dst1[1] * dst1[1]);
-    if (minor_length * im.max_aniso < major_length && minor_length > 0.0) {
+    const bool clamped = minor_length * im.max_aniso < major_length && minor_length > 0.0;
+    if (clamped) {
       const double scale = major_length / (minor_length * im.max_aniso);
       dst1[0] *= scale; dst1[1] *= scale;
       minor_length *= scale;
     }
-    if (minor_length == 0.0) return triangle(0, st);
+    if (minor_length == 0.0) { mip_count(MC_EWA_DEGENERATE); return triangle(0, st); }
+    mip_count(clamped ? MC_EWA_CLAMPED : MC_EWA_PLAIN);
     const double lod = rmax((double)(levels() - 1) + std::log2(minor_length), 0.0);
     const size_t i_lod = f2usize(std::floor(lod));
     const double fr = lod - std::trunc(lod);
@@ -2209,6 +2223,13 @@ int oracle_texture_eval(const rrt_scene_desc* d, int32_t tex, const double* si15
     Rgb v = tex_eval(d, tex, si);
     out3[0] = v.c[0]; out3[1] = v.c[1]; out3[2] = v.c[2];
   });
+}
+// The MIPMap lookup census since the last reset (process-wide; MipCensus order, 11 counters): trilinear level < 0 | level >= levels - 1 | between
+// levels; EWA minor_length == 0 | anisotropy clamp applied | plain; ewa() results 0 / 0 | with sum_wts > 0; texel() calls out of | in range;
+// triangle() calls with a negative s or t.
+void oracle_mip_census(uint64_t* out, int reset) {
+  for (int k = 0; k < MC_COUNT; k++)
+    out[k] = reset ? g_mip_census[k].exchange(0, std::memory_order_relaxed) : g_mip_census[k].load(std::memory_order_relaxed);
 }
 // SurfaceInteraction::compute_differentials: in24 = {n, p, dpdu, dpdv, rx_origin, rx_direction, ry_origin, ry_direction},
 // out10 = {dpdx.xyz, dpdy.xyz, dudx, dvdx, dudy, dvdy}

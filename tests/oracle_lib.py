@@ -33,6 +33,8 @@ def lib():
         L.oracle_trace_any_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         L.oracle_camera_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_render_rect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.oracle_mip_census.restype = None
+        L.oracle_mip_census.argtypes = [C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -149,6 +151,20 @@ def texture_eval(scene, tex, p=(0, 0, 0), uv=(0, 0), dpdx=(0, 0, 0), dpdy=(0, 0,
     out = np.zeros(3)
     _check(lib().oracle_texture_eval(_d(scene), tex, si.ctypes.data, out.ctypes.data))
     return out
+
+
+MIP_CENSUS = ("tri_below", "tri_last", "tri_between", "ewa_degenerate", "ewa_clamped", "ewa_plain", "ewa_nan", "ewa_ok", "texel_out", "texel_in",
+              "triangle_negative")
+
+
+def mip_census(reset=True):
+    """What the oracle's MIPMap lookups did since the last reset (MipCensus in rrt_oracle.cpp), process-wide: trilinear lookups with level < 0
+    (tri_below), level >= levels - 1 (tri_last) and between two levels; EWA lookups with minor_length == 0, with the anisotropy clamp applied and
+    plain; ewa() results that are 0 / 0 (ewa_nan) and that have sum_wts > 0 (two ewa() calls per lookup); texel() calls with s >= u_res or
+    t >= v_res and in range; triangle() calls with a negative s or t. Call it once to reset, render, call it again to read."""
+    out = (C.c_uint64 * len(MIP_CENSUS))()
+    lib().oracle_mip_census(out, 1 if reset else 0)
+    return dict(zip(MIP_CENSUS, (int(v) for v in out)))
 
 
 def surface_differentials(n, p, dpdu, dpdv, rxo, rxd, ryo, ryd):
