@@ -410,6 +410,36 @@ typedef struct rrt_aov {
 } rrt_aov;            /* any plane may be NULL (not produced); all NULL = RRT_EINVAL */
 int rrt_render_aov(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples, rrt_aov* out);
 
+/* Feature buffers through mirrors and glass (no counterpart in the reference): rrt_render_aov's planes with the record of the first
+ * non-specular surface along the chain of perfectly specular bounces a camera ray starts - what a denoiser wants on a wall mirror or a
+ * window, which first-hit planes show as one flat surface. rect, rank / world, max_samples, the planes' layout, the += semantics, live
+ * samples, fw and "the handle is left as it was" are rrt_render_aov's. max_follow = 0..16 is the longest chain followed. Per live sample
+ * with camera ray (o, d):
+ *   state:   k = 0, throughput thr = (1, 1, 1), path length T = 0.
+ *   segment: segment k is traced as rrt_trace_closest would. In fp32 the triangle the segment starts on is excluded, as the frame's spawned
+ *            rays exclude it; f64 keeps the reference's behaviour (the origin's own triangle is met at t ~ 1e-15 and refused by t < 1e-7).
+ *   miss:    at k = 0 a live miss: it adds only fw to albedo[3]. At k > 0 the sample keeps the record of surface k - 1.
+ *   hit:     at t on surface S: T += t; n = the normalised geometric normal, exactly rrt_render_aov's; rho_S from rrt_render_aov's table
+ *            (textured parameters with zero differentials). The sample's record becomes {thr * rho_S, n, T}, and it counts as a hit sample
+ *            in all three planes from here on, whatever later segments do.
+ *   follow:  S is followed iff k < max_follow and one of these rules applies. sn = the shading normal as the reference holds it after
+ *            Triangle / Sphere::intersect and the instance transform, before any bump_map; clamp0 = every channel clamped to >= 0.
+ *              Mirror: tint = clamp0(Kr), not black; d' = d - 2 (d . sn) sn.
+ *              Glass with u_roughness == 0 && v_roughness == 0 at the hit, before any remap (glass.rs:74): eta = "index" at the hit;
+ *                refract() of reflection.rs:122-134 with wo = -d, entering = wo . sn > 0, the ratio 1 / eta when entering and eta when
+ *                leaving, the normal turned towards wo. If a refracted direction exists and clamp0(Kt) is not black: d' = that direction,
+ *                tint = clamp0(Kt). Otherwise d' as for Mirror with tint = clamp0(Kr), if that is not black (total internal reflection).
+ *              Rough glass, every other material and a black tint end the chain on S.
+ *            On follow: thr *= tint, o' = the hit point exactly (spawn_ray applies no offset, Q8), d' normalised, k += 1.
+ * The planes receive the final record as rrt_render_aov's receive theirs: albedo holds the tinted reflectance of the last surface on the
+ * chain, depth the path length T and its square. max_follow = 0 adds bit for bit what rrt_render_aov adds, and for every max_follow the
+ * three weight channels (albedo[3], normal[3], depth[2]) are bit for bit rrt_render_aov's: the same fw in the same order.
+ * A specular *sphere* starts its follow ray under sphere.rs's epsilon-free self-hit test: its chain carries the
+ * reference's own coin in f64 and the known bias in fp32.
+ * Not provided: a fused form inside rrt_render_frame_aov, an adaptive form, _begin / _end.
+ * Errors: rrt_render_aov's, and RRT_EINVAL for max_follow > 16 (before any device work). */
+int rrt_render_aov_follow(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, rrt_aov* out);
+
 /* Denoiser (no counterpart in the reference): an edge-avoiding a-trous wavelet filter over a film, guided by the three planes of rrt_render_aov, with
  * albedo demodulation and a luminance edge-stop scaled by a spatially estimated variance that the iterations carry along (the spatial half of SVGF).
  * film_xyzw and the planes are full-frame W*H*4 sums of the handle's precision, exactly as rrt_render_rect / rrt_render_aov leave them, all in

@@ -194,6 +194,7 @@ PROTOTYPES = {
     "rrt_render_end": (C.c_int, [C.c_void_p]),
     "rrt_render_end_stats": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     "rrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.POINTER(Aov)]),
+    "rrt_render_aov_follow": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(Aov)]),
     "rrt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "rrt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),

@@ -208,14 +208,18 @@ class Renderer:
         return (film, st) if stats else film
 
     # first-hit feature buffers (rrt_render_aov): the raw filtered sums, (H, W, 4) each; resolve_aov() divides them out
-    def render_aov(self, rect=None, max_samples=0, rank=0, world=1, planes=("albedo", "normal", "depth")):
+    # follow > 0 (rrt_render_aov_follow): the planes of the first non-specular surface along chains of up to `follow` mirror / smooth-glass bounces
+    def render_aov(self, rect=None, max_samples=0, rank=0, world=1, planes=("albedo", "normal", "depth"), follow=0):
         W, H = self.scene.resolution
         rect = rect or (0, 0, W, H)
         out = {k: np.zeros((H, W, 4), self.dtype) for k in planes}
         ptr = {k: (out[k].ctypes.data if k in out else None) for k in ("albedo", "normal", "depth")}
         aov = A.Aov(A.RRT_MEM_HOST, self.precision, ptr["albedo"], ptr["normal"], ptr["depth"])
         r = (C.c_int32 * 4)(*rect)
-        _check(A.lib().rrt_render_aov(self._h, r, rank, world, max_samples, C.byref(aov)))
+        if follow > 0:
+            _check(A.lib().rrt_render_aov_follow(self._h, r, rank, world, max_samples, follow, C.byref(aov)))
+        else:
+            _check(A.lib().rrt_render_aov(self._h, r, rank, world, max_samples, C.byref(aov)))
         return out
 
     # rrt_render_moments: the frame of render() / render_bands() and the sample-variance plane {S1, S2, S0, S3} beside it; resolve_moments() divides it out
@@ -494,6 +498,7 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
         print(w, flush=True)
     moments = aov = None
     with_moments = bool(os.environ.get("RRT_DENOISE")) and os.environ.get("RRT_DENOISE_MOMENTS", "0") not in ("", "0")
+    follow = int(os.environ.get("RRT_AOV_FOLLOW") or 0)   # as rrt_render: > 0 takes the planes of RRT_AOV / RRT_DENOISE from rrt_render_aov_follow
     if os.environ.get("RRT_ADAPTIVE"):   # as rrt_render: rrt_render_adaptive in the frame's place
         params = {"threshold": float(os.environ["RRT_ADAPTIVE"])}
         for key, var in (("min_samples", "RRT_ADAPTIVE_MIN"), ("batch", "RRT_ADAPTIVE_BATCH")):
@@ -503,6 +508,8 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
         moments = plane if with_moments else None
         W, H = scene.resolution
         print(f"{st.camera_samples} of {W * H * max(0, scene.desc.sampler.samples_per_pixel - 1)} camera samples taken (adaptive)")
+    elif with_moments and follow > 0:   # as rrt_render: the moments frame; the followed planes come from their own call below
+        film, moments, st = r.render_moments(stats=True)
     elif with_moments:   # as rrt_render: the same frame, its sample-variance plane and the denoiser's feature planes from one camera pass
         film, moments, aov, st = r.render_frame_aov(max_samples=32, stats=True)
     else:
@@ -511,8 +518,8 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     rgba = resolve_rgba8(film, scene.desc.film.scale)
     write_png(save_to, rgba)
     if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
-        write_aov_pngs(os.environ["RRT_AOV"], r.render_aov())
+        write_aov_pngs(os.environ["RRT_AOV"], r.render_aov(follow=follow))
     if os.environ.get("RRT_DENOISE"):   # as rrt_render: the filtered frame, guided by the planes of at most 32 samples per pixel
-        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, aov if aov is not None else r.render_aov(max_samples=32), moments=moments), scene.desc.film.scale))
+        write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, aov if aov is not None else r.render_aov(max_samples=32, follow=follow), moments=moments), scene.desc.film.scale))
     r.close()
     return film, st

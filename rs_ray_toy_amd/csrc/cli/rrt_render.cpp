@@ -15,6 +15,8 @@
 // RRT_DENOISE_MOMENTS = 1 (any value but "" and "0") beside RRT_DENOISE (one GPU): the frame is rendered by rrt_render_moments - the same film, bit for bit, so the ordinary
 // PNG is unchanged - and the denoised frame comes from rrt_denoise_moments under the frame's sample-variance plane. That frame and the planes of
 // its first 32 samples come from one call, rrt_render_frame_aov: the same bits as rrt_render_moments followed by rrt_render_aov, one camera pass less.
+// RRT_AOV_FOLLOW = <n> (1..16) makes RRT_AOV and RRT_DENOISE take their planes from rrt_render_aov_follow(max_follow = n): the feature buffers of the
+// first non-specular surface behind mirrors and smooth glass. With RRT_DENOISE_MOMENTS that is rrt_render_moments followed by that call.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -35,12 +37,12 @@ int fail(const char* what, int rc) {
 
 // the sums of rrt_render_aov (rrt_aov in rrt.h) -> three 8-bit images
 template <typename R>
-int write_aov(rrt_handle* h, int precision, int W, int H, const std::string& prefix) {
+int write_aov(rrt_handle* h, int precision, int W, int H, uint32_t follow, const std::string& prefix) {
   const size_t npx = (size_t)W * (size_t)H;
   std::vector<R> alb(4 * npx, R(0)), nrm(4 * npx, R(0)), dep(4 * npx, R(0));
   rrt_aov out{RRT_MEM_HOST, precision, alb.data(), nrm.data(), dep.data()};
   const int32_t rect[4] = {0, 0, W, H};
-  int rc = rrt_render_aov(h, rect, 0, 1, 0, &out);
+  int rc = follow > 0 ? rrt_render_aov_follow(h, rect, 0, 1, 0, follow, &out) : rrt_render_aov(h, rect, 0, 1, 0, &out);
   if (rc != RRT_OK) return rc;
   double dmin = INFINITY, dmax = -INFINITY;
   for (size_t i = 0; i < npx; i++)
@@ -67,7 +69,7 @@ int write_aov(rrt_handle* h, int precision, int W, int H, const std::string& pre
 // rrt_render_frame_aov left them on device 0, one after the other; NULL = rendered here by rrt_render_aov
 template <typename R>
 int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, const void* film, const void* moments /* NULL: rrt_denoise */, const void* planes_dev,
-                   const char* path) {
+                   uint32_t follow, const char* path) {
   const size_t npx = (size_t)W * (size_t)H;
   std::vector<R> alb(4 * npx, R(0)), nrm(4 * npx, R(0)), dep(4 * npx, R(0)), out(4 * npx, R(0));
   rrt_aov aov{RRT_MEM_HOST, precision, alb.data(), nrm.data(), dep.data()};
@@ -80,7 +82,7 @@ int write_denoised(rrt_handle* h, int precision, int W, int H, double scale, con
         std::fprintf(stderr, "rrt_render: feature plane copy-out failed\n");
         return RRT_EDEVICE;
       }
-  } else rc = rrt_render_aov(h, rect, 0, 1, 32, &aov);
+  } else rc = follow > 0 ? rrt_render_aov_follow(h, rect, 0, 1, 32, follow, &aov) : rrt_render_aov(h, rect, 0, 1, 32, &aov);
   if (rc == RRT_OK) rc = moments ? rrt_denoise_moments(h, film, &aov, moments, nullptr, out.data()) : rrt_denoise(h, film, &aov, nullptr, out.data());
   std::vector<uint8_t> rgba(4 * npx);
   if (rc == RRT_OK) rc = rrt_resolve_rgba8(out.data(), precision, W, H, scale, rgba.data());
@@ -146,6 +148,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rrt_render: RRT_DENOISE_MOMENTS runs on one GPU: the denoised frame keeps the spatial variance estimate\n");
     with_moments = false;
   }
+  // RRT_AOV_FOLLOW=<n>: the planes of RRT_AOV / RRT_DENOISE through up to n specular bounces (rrt_render_aov_follow). Not a number: refused, not read as 0
+  uint32_t follow = 0;
+  if (const char* env_follow = std::getenv("RRT_AOV_FOLLOW"); env_follow && *env_follow) {
+    char* end = nullptr;
+    const unsigned long v = std::strtoul(env_follow, &end, 10);
+    if (end == env_follow || *end != '\0' || v > 0xfffffffful) {
+      std::fprintf(stderr, "rrt_render: RRT_AOV_FOLLOW must be a number (max_follow, 0..16)\n");
+      rrt_scene_free(scene);
+      return 2;
+    }
+    follow = (uint32_t)v;
+  }
   const size_t word = precision == RRT_F32 ? 4 : 8, film_bytes = (size_t)W * (size_t)H * 4 * word;
   // the tiles banner of integrator/mod.rs:59-62
   std::fprintf(stderr, "Rendering %d x %d, %d tile rows of 16 over %d GPU(s)\n", W, H, (H + 15) / 16, n_gpus);
@@ -187,6 +201,9 @@ int main(int argc, char** argv) {
       if (rc != RRT_OK) { const int e = fail("rrt_render_adaptive", rc); cleanup(); return e; }
       const unsigned long long spp = desc->sampler.samples_per_pixel > 1 ? (unsigned long long)desc->sampler.samples_per_pixel - 1ull : 0ull;
       std::printf("%llu of %llu camera samples taken (adaptive)\n", (unsigned long long)st.camera_samples, (unsigned long long)W * (unsigned long long)H * spp);
+    } else if (follow > 0) {   // the moments frame alone: the followed planes are rendered by write_denoised
+      rc = rrt_render_moments(handles[0], rect, 0, 1, films[0], moments_dev, RRT_MEM_DEVICE, &st);
+      if (rc != RRT_OK) { const int e = fail("rrt_render_moments", rc); cleanup(); return e; }
     } else {   // the frame, its moments plane and the denoiser's feature planes (at most 32 samples per pixel) from one camera pass
       if (hipMalloc(&planes_dev, 3 * film_bytes) != hipSuccess || hipMemset(planes_dev, 0, 3 * film_bytes) != hipSuccess) {
         std::fprintf(stderr, "rrt_render: cannot allocate the %zu-byte feature planes on device 0\n", 3 * film_bytes);
@@ -226,7 +243,7 @@ int main(int argc, char** argv) {
   if (rc != RRT_OK) { const int e = fail("write_image", rc); cleanup(); return e; }
   if (const char* env_aov = std::getenv("RRT_AOV"); env_aov && *env_aov) {
     if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_AOV runs on one GPU: the feature buffers are rendered on device 0 alone\n");
-    rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, env_aov) : write_aov<double>(handles[0], precision, W, H, env_aov);
+    rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, follow, env_aov) : write_aov<double>(handles[0], precision, W, H, follow, env_aov);
     if (rc != RRT_OK) { const int e = fail("rrt_render_aov", rc); cleanup(); return e; }
   }
   if (const char* env_dn = env_dn_path; env_dn && *env_dn) {
@@ -240,8 +257,8 @@ int main(int argc, char** argv) {
       }
     }
     const void* mom = with_moments ? host_moments.data() : nullptr;
-    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), mom, planes_dev, env_dn)
-                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), mom, planes_dev, env_dn);
+    rc = precision == RRT_F32 ? write_denoised<float>(handles[0], precision, W, H, film_scale, host.data(), mom, planes_dev, follow, env_dn)
+                              : write_denoised<double>(handles[0], precision, W, H, film_scale, host.data(), mom, planes_dev, follow, env_dn);
     if (rc != RRT_OK) { const int e = fail(with_moments ? "rrt_denoise_moments" : "rrt_denoise", rc); cleanup(); return e; }
   }
   cleanup();

@@ -1868,6 +1868,120 @@ __global__ void __launch_bounds__(kBlock) k_aov_wide_frame(SceneDev<R> s, Pools<
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Feature buffers through mirrors and glass (rrt_render_aov_follow, include/rrt.h): the record of the first non-specular surface along
+// the chain of perfectly specular bounces a camera ray starts. A kernel of its own, not a template flag on k_aov_shade: the code
+// rrt_render_aov and rrt_render_frame_aov launch stays what it is. The first hits' records are k_aov_shade's own, rho goes through aov_rho and
+// the planes through k_aov_box / k_aov_wide unchanged, so a chain of length 0 leaves rrt_render_aov's bits.
+// ------------------------------------------------------------------------------------------------------------
+// The continuation of the chain at a hit, by the rules on the prototype: Mirror reflects about the shading normal; smooth Glass refracts
+// (reflection.rs:122-134, wo = -d, the normal turned towards wo) and reflects where there is no refracted direction or Kt is black. `m` has
+// its textured parameters evaluated at the hit, `kr` = its Kr clamped to >= 0. false: the chain ends on this surface.
+template <typename R>
+RRT_DEV bool aov_follow_dir(const Material<R>& m, Rgb<R> kr, V3<R> d, V3<R> sn, V3<R>* d_next, Rgb<R>* tint) {
+  if (m.type != 3 && m.type != 5) return false;
+  if (m.type == 5) {
+    if (!(m.u_roughness == R(0) && m.v_roughness == R(0))) return false;   // rough glass (glass.rs:74, before any remap)
+    const Rgb<R> kt = rgb_clamp0(Rgb<R>(m.kt));
+    const V3<R> wo = -d;
+    const bool entering = dot(wo, sn) > R(0);
+    V3<R> wt;
+    if (!kt.is_black() && refract(wo, faceforward(sn, wo), entering ? R(1) / m.index : m.index, &wt)) {
+      *d_next = vnormalize(wt); *tint = kt;
+      return true;
+    }
+  }
+  if (kr.is_black()) return false;
+  *d_next = vnormalize(d - sn * (R(2) * dot(d, sn)));
+  *tint = kr;
+  return true;
+}
+
+// The chain's own record arithmetic, never contracted: the TEX and non-TEX instantiations form the same bits
+template <typename R>
+RRT_DEV typename Vec4T<R>::type aov_follow_scale(const typename Vec4T<R>::type& st, Rgb<R> c, R t) {
+#pragma clang fp contract(off)
+  return mk4<R>(st.x * c.r, st.y * c.g, st.z * c.b, st.w + t);
+}
+// the material build_surface reports for a hit on `prim`
+template <typename R>
+RRT_DEV uint32_t aov_hit_material(const SceneDev<R>& s, int prim) {
+  const Tri<R>& tr = s.tris[prim];
+  return (tr.plane != kSphereMark && is_inst_tri(tr)) ? (tr.material & 0xffffu) : tr.material;
+}
+
+// One level of the chain: one thread per entry of the active queue, in queue order (slot word, ray, hit and the entry's {thr.rgb, T}
+// record in p.path - the role npath plays for beta: 128-bit loads). A hit writes the slot's record {thr * rho, hit flag}, {n, T + t}, so the
+// record of the last surface hit is always in place: a later miss, or a chain that has used up its levels, needs no fix-up.
+// level0: the queue is the camera kernels' and k_aov_shade ITSELF has just written its records (rec_a for every entry, hit or miss - a record
+// an earlier pass left in a slot is never read): with thr = 1 and T = 0 they are the chain's, and only k_aov_shade's own code leaves
+// k_aov_shade's bits - a second copy of its statements inside this kernel is contracted differently by the compiler (the normal plane of a
+// chain of length 0 then differs from rrt_render_aov's in its last bit: measured). So level 0 here only decides and spawns, for the hits on
+// Mirror / Glass. may_follow: followed entries go to q_next through block_push with their ray (store_ray: the self-triangle exclusion and the
+// low word of the origin) and {thr * tint, T + t}. The grid walks the queue with block-uniform trip counts, as block_push needs.
+template <typename R, bool TEX>
+__global__ void __launch_bounds__(kBlock) k_aov_follow(SceneDev<R> s, Pools<R> p, typename Vec4T<R>::type* rec_a, typename Vec4T<R>::type* rec_b, int level0, int may_follow) {
+  using V4 = typename Vec4T<R>::type;
+  __shared__ uint32_t push_lds[kBlock / 64 + 1];
+  const uint32_t n = p.counters[C_ACTIVE];
+  for (uint32_t base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {
+    const uint32_t i = base + threadIdx.x;
+    bool want_next = false;
+    uint32_t slot = 0;
+    int prim = -1;
+    V3<R> nx_o, nx_lo, nx_d;
+    V4 nx_rec = mk4<R>(R(0), R(0), R(0), R(0));
+    if (i < n) {
+      slot = p.q_active[i].slot;
+      const V4 h = p.hit[i];
+      prim = (int)real_to_bits(h.y);
+      bool work = prim >= 0;
+      if (work && level0) { const int mt = s.materials[aov_hit_material(s, prim)].type; work = mt == 3 || mt == 5; }
+      if (work) {
+        const V4 ro = p.ray_o[i], rd = p.ray_d[i];
+        const V3<R> d(rd.x, rd.y, rd.z);
+        SurfExt<R> ext;
+        const Surf<R> si = build_surface(s, prim, V3<R>(ro.x, ro.y, ro.z), d, h.x, h.z, h.w, TEX ? &ext : nullptr);
+        if (!si.ok) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_SHADING_NORMAL);   // primitives.rs:66, as the frame reports it
+        TexCtx<R> tc;
+        if (TEX) {   // dpdx = dpdy = 0, dudx .. dvdy = 0 (TexCtx's defaults)
+          tc.p = si.p; tc.u = ext.u; tc.v = ext.v;
+          tc.pd = V3<double>((double)si.p.x + (double)si.p_lo.x, (double)si.p.y + (double)si.p_lo.y, (double)si.p.z + (double)si.p_lo.z);
+        }
+        const Material<R>& m0 = s.materials[si.material];
+        const Rgb<R> rho = aov_rho<R, TEX>(s, m0, tc);
+        const V4 st = level0 ? mk4<R>(R(1), R(1), R(1), R(0)) : p.path[i];
+        if (!level0) {
+          const V3<R> nn = vnormalize(si.n);
+          const V4 rec = aov_follow_scale<R>(st, rho, h.x);   // {thr * rho, T + t}
+          rec_a[slot] = mk4u<R>(rec.x, rec.y, rec.z, 1u);
+          rec_b[slot] = mk4<R>(nn.x, nn.y, nn.z, rec.w);
+        }
+        if (may_follow && (m0.type == 3 || m0.type == 5)) {
+          Rgb<R> tint;
+          if (m0.type == 3) want_next = aov_follow_dir(m0, rho, d, si.sn, &nx_d, &tint);   // a Mirror's rho is its clamped Kr at this hit: not evaluated twice
+          else if (TEX) {
+            const Material<R> m = resolve_material(s, m0, tc);
+            want_next = aov_follow_dir(m, rgb_clamp0(Rgb<R>(m.kr)), d, si.sn, &nx_d, &tint);
+          }
+          else want_next = aov_follow_dir(m0, rgb_clamp0(Rgb<R>(m0.kr)), d, si.sn, &nx_d, &tint);
+          if (want_next) {
+            nx_o = si.p; nx_lo = si.p_lo;   // spawn_ray applies no offset (Q8)
+            nx_rec = aov_follow_scale<R>(st, tint, h.x);   // {thr * tint, T + t}
+          }
+        }
+        if (TEX) { if (tc.err) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_MIPMAP); }
+      }
+    }
+    const uint32_t qn = block_push(&p.counters[C_NEXT], want_next, push_lds);
+    if (want_next) {
+      p.q_next[qn] = QEnt{slot, 0u, 0u, 0u};
+      p.npath[qn] = nx_rec;
+      store_ray<R>(p.nray_o, p.nray_d, qn, nx_o, nx_lo, nx_d, Const<R>::inf, self_prim<R>(prim));
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Sample-variance plane beside the film (rrt_render_moments, include/rrt.h): per film pixel {S1 = sum fw y, S2 = sum fw y^2, S0 = sum fw,
 // S3 = sum fw^2} over every sample whose footprint covers the pixel, y = the luminance of L w after the film's own clamps. Kernels of their
 // own, not a template flag on k_film_box / k_film_wide: the kernels a plain frame launches stay the code they are. The film sums go through

@@ -116,6 +116,17 @@ int rrt_render_aov(rrt_handle* h, const int32_t rect[4], int rank, int world, ui
   return guarded([&]() { h->impl->render_aov(rect, rank, world, max_samples, out); });
 }
 
+int rrt_render_aov_follow(rrt_handle* h, const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, rrt_aov* out) {
+  // rrt_render_aov's checks in its order, then the chain's own bound: all before any device work
+  if (!out) { rrt::set_last_error("rrt_render_aov_follow: null output description (rrt_aov)"); return RRT_EINVAL; }
+  if (!out->albedo && !out->normal && !out->depth) { rrt::set_last_error("rrt_render_aov_follow: no plane requested (albedo, normal and depth are all NULL)"); return RRT_EINVAL; }
+  if (out->mem != RRT_MEM_HOST && out->mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_aov_follow: bad mem"); return RRT_EINVAL; }
+  if (!rect) { rrt::set_last_error("rrt_render_aov_follow: null rect"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_render_aov_follow: null handle"); return RRT_EINVAL; }
+  if (max_follow > 16u) { rrt::set_last_error("rrt_render_aov_follow: max_follow must be 0..16"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_aov_follow(rect, rank, world, max_samples, max_follow, out); });
+}
+
 void rrt_denoise_defaults(rrt_denoise_params* p) {
   if (!p) return;
   p->iterations = 5; p->demodulate = 1;

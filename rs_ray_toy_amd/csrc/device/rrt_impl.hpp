@@ -47,6 +47,7 @@ struct HandleBase {
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
   virtual void render_end(rrt_render_stats* stats) = 0;
   virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
+  virtual void render_aov_follow(const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) = 0;
   virtual void render_moments(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, rrt_render_stats* stats) = 0;
   virtual void render_frame_aov(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, uint64_t aov_max_samples, const rrt_aov* aov, rrt_render_stats* stats) = 0;   // moments may be NULL
   virtual void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film, void* moments, uint32_t* tile_samples, int mem, rrt_render_stats* stats) = 0;
@@ -855,6 +856,92 @@ class Handle : public HandleBase {
     aov_merge_out(out);   // into the caller's planes (+=)
     check_device_errors();
   }
+  // ---- feature buffers through mirrors and glass (rrt_render_aov_follow): render_aov's pass loop with a level loop in place of k_aov_shade ------------
+  // Per pass: camera kernels, closest hit over the camera queue (tile trees where a frame has built them), k_aov_shade for the first hits' records,
+  // then per level k_aov_follow, the queue rotation and a closest-hit launch over the device-side count of followed entries - no host read-back between levels, launches sized by the
+  // pass like the path loop's - and render_aov's own gather kernels. What launch_raygen sets per pass and the queue halves the levels swap are put back.
+  void render_aov_follow(const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) override {
+    if (pending_) throw std::invalid_argument("render_aov_follow: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (out->precision != precision()) throw std::invalid_argument("render_aov_follow: plane precision must match the handle");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_aov_follow: bad rank/world");
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    const rrt_film& f = desc_.film;
+    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
+    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_aov_follow: rect outside the film");
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30, n_ranks = (uint32_t)world;
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
+    const size_t W = (size_t)f.xres, H = (size_t)f.yres, plane_n = W * H * 4;
+    size_t rh = (size_t)(rect[3] - rect[1]);
+    if (n_ranks > 1) {   // rows of this rank's bands
+      size_t rows = 0;
+      for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == (uint32_t)rank) rows++;
+      rh = rows;
+    }
+    const size_t rw = (size_t)(rect[2] - rect[0]), rpix = rw * rh;
+    uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
+    if (max_samples != 0) s_total = std::min<uint64_t>(s_total, max_samples);
+    if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
+    if (!has_specular_) max_follow = 0;   // no surface of the scene is followed: every chain ends on its first hit, and no level is launched to find that out
+    using V4 = typename Vec4T<R>::type;
+    struct Restore {   // what launch_raygen sets for the pass it last ran for, and the queue halves as the call found them
+      Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6]; bool swapped;
+      ~Restore() {
+        h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k];
+        if (swapped) h->swap_queues();
+      }
+    } restore{this, tt_pass_ok_, film_runs_ok_, scene_.root_cull, {scene_.root_box[0], scene_.root_box[1], scene_.root_box[2], scene_.root_box[3], scene_.root_box[4], scene_.root_box[5]}, false};
+
+    if (aov_planes_.n != 3 * plane_n) aov_planes_.alloc(3 * plane_n);
+    HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
+    ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+    ensure_aov_recs();
+    const size_t group = std::min(rpix, cap_);                     // pixels per group
+    const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
+    for (size_t g0 = 0; g0 < rpix; g0 += group) {
+      const size_t npix = std::min(group, rpix - g0);
+      for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
+        const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
+        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
+        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, (uint32_t)rank, tiled};
+        const size_t nslots = npix * (size_t)ns;
+        const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+        launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
+        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
+        const dim3 sg(std::min(grid, 16384u));
+        // level 0's records are k_aov_shade's own (see k_aov_follow)
+        if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
+        else hipLaunchKernelGGL((k_aov_shade<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
+        for (uint32_t k = 0; k <= max_follow; k++) {
+          const int level0 = k == 0 ? 1 : 0, may_follow = k < max_follow ? 1 : 0;
+          if (level0 && !may_follow) break;   // max_follow = 0: the first hits are the planes
+          if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_follow<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
+          else hipLaunchKernelGGL((k_aov_follow<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
+          if (!may_follow) break;
+          swap_queues(); restore.swapped = !restore.swapped;
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);   // active <- next
+          launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/false);
+        }
+        if (!wide_filter) hipLaunchKernelGGL((k_aov_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p);
+        else {
+          // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as render_impl)
+          const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+          const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+          const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+          const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
+          hipLaunchKernelGGL((k_aov_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p,
+                             ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+        }
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    aov_merge_out(out);   // into the caller's planes (+=)
+    check_device_errors();
+  }
   // ---- rrt_denoise (device/dfilter.hpp): prepare, initial variance, one a-trous launch per iteration, finish ---------------------------------------------
   // Only the handle's stream and its own work buffers are used: nothing of the frame's state is read or written.
   template <int S>
@@ -977,6 +1064,7 @@ class Handle : public HandleBase {
   bool tile_order_ = true;  // option "tile_order": pixels of a pass enumerated tile by tile (PassDesc::tiled)
   bool raygen_lean_ = true;   // option "raygen_lean"
   bool has_transmissive_ = false, has_translucent_ = false;
+  bool has_specular_ = false;   // a Mirror or Glass primitive exists (render_aov_follow runs no level beyond the first hits otherwise)
   bool area_lights_ = true;   // some light is a DiffuseAreaLight (else the Lambert shading kernel drops the area-light code)
   uint32_t shade_kinds_scene_ = kAllKinds, shade_kinds_ = kAllKinds;   // lobe-kind set of the scene's materials / of the shading kernel in use (option "shade_spec")
   int trav_mode_ = 3;   // 1 = LDS-treelet grid-stride kernel, 2 = persistent-thread kernel, 3 = by queue size
@@ -1104,6 +1192,11 @@ class Handle : public HandleBase {
 #endif
     FlatScene<R> fs = flatten_scene<R>(d, slab_pad);
     has_transmissive_ = fs.used.has_transmissive; has_translucent_ = fs.used.has_translucent; area_lights_ = fs.used.area_lights;
+    has_specular_ = false;   // some primitive's material is a Mirror or a Glass: the only surfaces render_aov_follow can follow
+    for (size_t i = 0; i < d->n_prims; i++) {
+      const int mt = d->materials[d->prims[i].material].type;
+      if (mt == RRT_MAT_MIRROR || mt == RRT_MAT_GLASS) has_specular_ = true;
+    }
     shade_kinds_scene_ = fs.used.shade == ShadeClass::Lambert ? kKindsLambert : (fs.used.shade == ShadeClass::Glossy ? kKindsGlossy : kAllKinds);
     shade_kinds_ = shade_kinds_scene_;
     if (!fs.used.warning.empty()) warnings.push_back(fs.used.warning);
