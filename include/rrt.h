@@ -548,6 +548,54 @@ void rrt_adaptive_defaults(rrt_adaptive_params*);   /* min_samples 16, batch 16,
 int rrt_render_adaptive(rrt_handle*, const int32_t rect[4], const rrt_adaptive_params* params /* NULL = defaults */, void* film_xyzw, void* moments,
                         uint32_t* tile_samples /* may be NULL */, int mem, rrt_render_stats* stats /* may be NULL */);
 
+/* Light-group and bounce passes beside the film (no counterpart in the reference, whose PathIntegrator::li returns one sum): the frame of
+ * rrt_render_rect (rank / world = 0 / 1) or of the rect's interleaved bands, partitioned as rrt_render_moments partitions them, and per pass a
+ * film of the part of every sample's radiance that the pass selects. Path integrator only.
+ *   vertex b:  the value of `bounces` in PathIntegrator::li (path.rs:51-226) when uniform_sample_one_light runs: 0 is the camera ray's hit.
+ *              Specular vertices count and have no next-event term.
+ *   light ln:  the light uniform_sample_one_light picked (integrator/mod.rs:359-401); its group is light_group[ln], or min(ln, 31) for a NULL
+ *              light_group.
+ *   pass k:    per sample the sum, in vertex order, of the terms beta * Ld / light_pdf that the frame adds to L (estimate_direct's unoccluded
+ *              terms; emission is 0, Q18) with bit light_group[ln] set in passes[k].groups and bounce_lo <= b < bounce_hi (bounce_hi <= 0: no
+ *              upper end). A term may count for several passes or for none.
+ * The pass radiance goes through the film exactly as L does: the NaN / negative / infinity handling of integrator/mod.rs:105-122, the camera
+ * weight, the pixel filter, dead samples adding filter weight (Q2), the weight tripled (Q3). So every pass film carries the frame's own weight
+ * channel, and rrt_resolve_rgba8, rrt_denoise and rrt_film_gather take a pass film as they take a frame. passes[k].film_xyzw is a full-frame
+ * W*H*4 film of the handle's precision in `mem`, added to (+=); rect, rank / world and += are rrt_render_moments'. film_xyzw, when not NULL,
+ * is added to with the very bits rrt_render_rect / rrt_render_bands add, and the statistics hold the same camera_samples, camera_rays,
+ * closest_queries, any_queries, root_culled and sky_culled: no ray is traced twice, and tile trees, lens cull, root and horizon cull and
+ * shadow lists stay on. A pass with groups = ~0u and no bounce limits holds the frame's bits; passes that partition the (group, vertex) pairs
+ * sum to the frame up to the rounding of the sums. A passes frame renders as with the option film_records 0 (per-slot radiance layout, as a
+ * moments frame), which changes no bit of the film. The handle is left as it was; the radiance planes (16 bytes per pass and pool slot) are
+ * allocated by the first call and bound the size of a pool pass.
+ * Errors, each with its own message: RRT_EINVAL before any device work for a NULL handle, rect or passes, n_passes outside 1 .. RRT_MAX_PASSES,
+ * a NULL pass film, a bad mem, bounce_lo < 0 and a light_group entry >= 32; RRT_EINVAL for a rect outside the film, bad rank / world, a frame in
+ * flight; RRT_EUNSUP, the reason named, for every integrator but Path and for a finite Film.max_sample_luminance (its clamp depends on the
+ * whole sample's luminance, so the passes would no longer add up); otherwise what rrt_render_rect gives for the scene.
+ * Not provided: a _begin / _end form, an adaptive form, moments per pass. */
+#define RRT_MAX_PASSES 16
+typedef struct rrt_pass {
+  uint32_t groups;               /* bit g set: NEE terms of lights in group g count */
+  int32_t  bounce_lo, bounce_hi; /* ... at path vertices lo <= b < hi; hi <= 0 means no upper end */
+  void*    film_xyzw;            /* full-frame W*H*4, handle precision, added to (+=) */
+} rrt_pass;
+int rrt_render_passes(rrt_handle*, const int32_t rect[4], int rank, int world,
+                      const uint8_t* light_group /* n_lights entries, each < 32; NULL: light i is in group min(i, 31) */,
+                      const rrt_pass* passes, int n_passes,
+                      void* film_xyzw /* may be NULL */, int mem, rrt_render_stats* stats /* may be NULL */);
+
+/* Relighting from pass films (no counterpart in the reference). films[k] are n full-frame W*H*4 films of the handle's precision in `mem`, as
+ * rrt_render_passes leaves them; gains_rgb holds n RGB triples. Per pixel
+ *     film_out[:3] = sum_k rgb_to_xyz(gains[k] * xyz_to_rgb(films[k][:3])),
+ *     film_out[3]  = films[0][3],
+ * rgb_to_xyz the table a film's RGB sums were merged with (spectrum.rs:2084-2090) and xyz_to_rgb its inverse, taken in double. That inverse
+ * agrees with the six-digit xyz_to_rgb table of spectrum.rs:2075-2082 (rrt_resolve_rgba8's) to 1.4e-6, which is how far the two tables are from
+ * being inverses of each other; with the inverse, unit gains return the sum of the films and gains g the frame of the scene whose lights' spectra
+ * are scaled by g, to the rounding of the arithmetic (through the six-digit table: to 5e-7 of the frame's largest value). Computed in double in both precision modes, on the device for both memory kinds (host films are staged). film_out is overwritten, not added
+ * to, and may be one of the inputs. The handle is left as it was. Errors: RRT_EINVAL, each with its own message, for a NULL handle, films,
+ * films[k], gains_rgb or film_out, n outside 1 .. RRT_MAX_PASSES and a bad mem, all before any device work. */
+int rrt_combine_passes(rrt_handle*, const void* const* films, const double* gains_rgb /* n x 3 */, int n, void* film_out, int mem);
+
 /* ---- multi-GPU film reassembly: RCCL over xGMI, one collective per frame ----
  * The reference has one address space: its rayon tiles merge under a lock (Film::merge_film_tile film.rs:248-263, driven from
  * integrator/mod.rs:64-74,133). Across GPUs every rank renders its bands (rrt_render_bands / _begin) into its own device

@@ -167,6 +167,13 @@ class AdaptiveParams(C.Structure):
     _fields_ = [("min_samples", C.c_uint32), ("batch", C.c_uint32), ("max_samples", C.c_uint32), ("threshold", C.c_double)]
 
 
+RRT_MAX_PASSES = 16
+
+
+class Pass(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("bounce_lo", C.c_int32), ("bounce_hi", C.c_int32), ("film_xyzw", C.c_void_p)]
+
+
 # every symbol include/rrt.h declares (tests/test_abi.py checks the library exports all of them)
 PROTOTYPES = {
     "rrt_scene_load": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -204,6 +211,8 @@ PROTOTYPES = {
     "rrt_tile_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
     "rrt_adaptive_defaults": (None, [C.POINTER(AdaptiveParams)]),
     "rrt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
+    "rrt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.POINTER(Pass), C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
+    "rrt_combine_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int]),
     "rrt_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "rrt_comm_id": (C.c_int, [C.c_void_p]),
     "rrt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

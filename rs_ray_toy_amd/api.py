@@ -7,6 +7,7 @@ as `RrtUnsupported`. There is no CPU fallback: every compute call goes to the HI
 import ctypes as C
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -245,6 +246,78 @@ class Renderer:
         _check(A.lib().rrt_render_moments(self._h, r, rank, world, film_ptr, moments_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
         return st
 
+    # rrt_render_passes: the frame of render() / render_bands() and, beside it, one film per pass of the Path integrator's next-event terms
+    @staticmethod
+    def _pass_table(passes, film_ptrs):
+        tab = (A.Pass * max(1, len(passes)))()
+        for k, (p, ptr) in enumerate(zip(passes, film_ptrs)):
+            groups, lo, hi = p
+            tab[k] = A.Pass(int(groups) & 0xFFFFFFFF, int(lo), int(hi), ptr)
+        return tab
+
+    @staticmethod
+    def _light_groups(light_group):
+        if light_group is None:
+            return None, None
+        lg = np.ascontiguousarray(light_group, np.uint8)
+        return lg, lg.ctypes.data
+
+    def render_passes(self, passes, light_group=None, rect=None, rank=0, world=1, film=True, stats=False):
+        """passes: a list of (groups, bounce_lo, bounce_hi) - a bit mask of light groups and the path vertices lo <= b < hi (hi <= 0: no upper end);
+        light_group: one group (< 32) per light, None = light i is in group min(i, 31). film: True = a new frame film, None / False = none, or an
+        (H, W, 4) array added to (+=). -> (film or None, [pass films][, stats]): (H, W, 4) host arrays of the handle's precision."""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        if film is True:
+            film = np.zeros((H, W, 4), self.dtype)
+        elif film is False:
+            film = None
+        if film is not None and (film.dtype != self.dtype or film.shape != (H, W, 4) or not film.flags.c_contiguous):
+            raise ValueError("render_passes: film is a C-contiguous (H, W, 4) array of the handle's precision")
+        films = [np.zeros((H, W, 4), self.dtype) for _ in passes]
+        tab = self._pass_table(passes, [f.ctypes.data for f in films])
+        lg, lg_ptr = self._light_groups(light_group)
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_passes(self._h, r, rank, world, lg_ptr, tab, len(passes), film.ctypes.data if film is not None else None, A.RRT_MEM_HOST,
+                                         C.byref(st) if stats else None))
+        return (film, films, st) if stats else (film, films)
+
+    def render_passes_device(self, rect, passes, film_ptrs, light_group=None, film_ptr=None, rank=0, world=1, stats=True):
+        """render_passes into device films: film_ptrs[k] is pass k's film (+=), film_ptr the frame's or None."""
+        tab = self._pass_table(passes, film_ptrs)
+        lg, lg_ptr = self._light_groups(light_group)
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_passes(self._h, r, rank, world, lg_ptr, tab, len(passes), film_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
+        return st
+
+    @staticmethod
+    def _gains(gains, n):
+        """(n, 3) doubles from one number for all films, one number per film, or one RGB triple per film."""
+        g = np.asarray(gains, np.float64)
+        if g.ndim == 1: g = g[:, None]
+        return np.ascontiguousarray(np.broadcast_to(g, (n, 3)))
+
+    # rrt_combine_passes: relighting - sum_k rgb_to_xyz(gains[k] * xyz_to_rgb(films[k])), the weight channel films[0]'s
+    def combine_passes(self, films, gains, out=None):
+        """films: (H, W, 4) host arrays as render_passes returns them; gains: one RGB triple (or one number) per film. -> the combined film."""
+        W, H = self.scene.resolution
+        for f in films:
+            if f.dtype != self.dtype or f.shape != (H, W, 4) or not f.flags.c_contiguous:
+                raise ValueError("combine_passes: films are C-contiguous (H, W, 4) arrays of the handle's precision")
+        if out is None:
+            out = np.empty((H, W, 4), self.dtype)
+        g = self._gains(gains, len(films))
+        ptrs = (C.c_void_p * max(1, len(films)))(*[f.ctypes.data for f in films])
+        _check(A.lib().rrt_combine_passes(self._h, ptrs, g.ctypes.data_as(C.POINTER(C.c_double)), len(films), out.ctypes.data, A.RRT_MEM_HOST))
+        return out
+
+    def combine_passes_device(self, film_ptrs, gains, out_ptr):
+        g = self._gains(gains, len(film_ptrs))
+        ptrs = (C.c_void_p * max(1, len(film_ptrs)))(*film_ptrs)
+        _check(A.lib().rrt_combine_passes(self._h, ptrs, g.ctypes.data_as(C.POINTER(C.c_double)), len(film_ptrs), out_ptr, A.RRT_MEM_DEVICE))
+
     # rrt_render_frame_aov: the frame of render_moments() and the planes of render_aov() from one camera pass - every input of denoise(..., moments=)
     def render_frame_aov(self, rect=None, rank=0, world=1, max_samples=0, film=None, moments=True, planes=("albedo", "normal", "depth"), stats=False):
         """-> (film, moments_or_None, aov_dict[, stats]): film and moments as render_moments gives them (moments: True = a new plane, False / None =
@@ -474,6 +547,19 @@ def write_aov_pngs(prefix, aov):
         write_png(f"{prefix}_{name}.png", rgba)
 
 
+def write_pass_pngs(prefix, renderer, n_lights, scale=1.0):
+    """<prefix>_direct.png (path vertex 0), <prefix>_indirect.png (vertices >= 1) and <prefix>_light<i>.png for the first 14 lights, from one
+    Renderer.render_passes call - what rrt_render writes under RRT_PASSES=<prefix>."""
+    shown = min(int(n_lights), A.RRT_MAX_PASSES - 2)
+    if n_lights > shown:
+        print(f"RRT_PASSES writes the passes of the first {shown} of the scene's {n_lights} lights", file=sys.stderr, flush=True)
+    names = ["direct", "indirect"] + [f"light{i}" for i in range(shown)]
+    passes = [(0xFFFFFFFF, 0, 1), (0xFFFFFFFF, 1, 0)] + [(1 << i, 0, 0) for i in range(shown)]
+    _, films = renderer.render_passes(passes, light_group=[min(i, 31) for i in range(n_lights)], film=None)
+    for name, f in zip(names, films):
+        write_png(f"{prefix}_{name}.png", resolve_rgba8(f, scale))
+
+
 def write_png(path, rgba):
     rgba = np.ascontiguousarray(rgba, np.uint8)
     H, W, _ = rgba.shape
@@ -519,6 +605,8 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     write_png(save_to, rgba)
     if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
         write_aov_pngs(os.environ["RRT_AOV"], r.render_aov(follow=follow))
+    if os.environ.get("RRT_PASSES"):   # as rrt_render: direct, indirect and one PNG per light (the first 14) after the frame
+        write_pass_pngs(os.environ["RRT_PASSES"], r, scene.desc.n_lights, scene.desc.film.scale)
     if os.environ.get("RRT_DENOISE"):   # as rrt_render: the filtered frame, guided by the planes of at most 32 samples per pixel
         write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, aov if aov is not None else r.render_aov(max_samples=32, follow=follow), moments=moments), scene.desc.film.scale))
     r.close()

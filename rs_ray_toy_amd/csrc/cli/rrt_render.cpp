@@ -17,6 +17,8 @@
 // its first 32 samples come from one call, rrt_render_frame_aov: the same bits as rrt_render_moments followed by rrt_render_aov, one camera pass less.
 // RRT_AOV_FOLLOW = <n> (1..16) makes RRT_AOV and RRT_DENOISE take their planes from rrt_render_aov_follow(max_follow = n): the feature buffers of the
 // first non-specular surface behind mirrors and smooth glass. With RRT_DENOISE_MOMENTS that is rrt_render_moments followed by that call.
+// RRT_PASSES = <prefix> writes light-group and bounce passes after the frame (rrt_render_passes, on device 0 alone): <prefix>_direct.png (path vertex 0),
+// <prefix>_indirect.png (vertices >= 1) and <prefix>_light<i>.png for the first 14 lights, each light its own group; Path integrator only.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -62,6 +64,31 @@ int write_aov(rrt_handle* h, int precision, int W, int H, uint32_t follow, const
   }
   const char* names[3] = {"_albedo.png", "_normal.png", "_depth.png"};
   for (int k = 0; k < 3 && rc == RRT_OK; k++) rc = rrt_write_png((prefix + names[k]).c_str(), img[k].data(), W, H);
+  return rc;
+}
+
+// the pass films of rrt_render_passes -> 8-bit images: direct, indirect, and one per light for the first 14 lights (RRT_MAX_PASSES - 2)
+template <typename R>
+int write_passes(rrt_handle* h, int precision, int W, int H, double scale, size_t n_lights, const std::string& prefix) {
+  const size_t npx = (size_t)W * (size_t)H;
+  const size_t shown = std::min<size_t>(n_lights, RRT_MAX_PASSES - 2);
+  if (n_lights > shown) std::fprintf(stderr, "rrt_render: RRT_PASSES writes the passes of the first %zu of the scene's %zu lights\n", shown, n_lights);
+  std::vector<std::vector<R>> films(2 + shown, std::vector<R>(4 * npx, R(0)));
+  std::vector<std::string> names = {"_direct.png", "_indirect.png"};
+  std::vector<rrt_pass> passes = {{~0u, 0, 1, films[0].data()}, {~0u, 1, 0, films[1].data()}};
+  std::vector<uint8_t> group(n_lights);
+  for (size_t i = 0; i < n_lights; i++) group[i] = (uint8_t)std::min<size_t>(i, 31);   // (lights past the 31st share a group no pass here asks for alone)
+  for (size_t i = 0; i < shown; i++) {
+    passes.push_back({1u << i, 0, 0, films[2 + i].data()});
+    names.push_back("_light" + std::to_string(i) + ".png");
+  }
+  const int32_t rect[4] = {0, 0, W, H};
+  int rc = rrt_render_passes(h, rect, 0, 1, group.data(), passes.data(), (int)passes.size(), nullptr, RRT_MEM_HOST, nullptr);
+  std::vector<uint8_t> rgba(4 * npx);
+  for (size_t k = 0; k < passes.size() && rc == RRT_OK; k++) {
+    rc = rrt_resolve_rgba8(films[k].data(), precision, W, H, scale, rgba.data());
+    if (rc == RRT_OK) rc = rrt_write_png((prefix + names[k]).c_str(), rgba.data(), W, H);
+  }
   return rc;
 }
 
@@ -245,6 +272,12 @@ int main(int argc, char** argv) {
     if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_AOV runs on one GPU: the feature buffers are rendered on device 0 alone\n");
     rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, follow, env_aov) : write_aov<double>(handles[0], precision, W, H, follow, env_aov);
     if (rc != RRT_OK) { const int e = fail("rrt_render_aov", rc); cleanup(); return e; }
+  }
+  if (const char* env_ps = std::getenv("RRT_PASSES"); env_ps && *env_ps) {
+    if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_PASSES runs on one GPU: the passes are rendered on device 0 alone\n");
+    rc = precision == RRT_F32 ? write_passes<float>(handles[0], precision, W, H, film_scale, desc->n_lights, env_ps)
+                              : write_passes<double>(handles[0], precision, W, H, film_scale, desc->n_lights, env_ps);
+    if (rc != RRT_OK) { const int e = fail("rrt_render_passes", rc); cleanup(); return e; }
   }
   if (const char* env_dn = env_dn_path; env_dn && *env_dn) {
     std::vector<unsigned char> host_moments;

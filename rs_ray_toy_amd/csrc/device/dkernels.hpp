@@ -425,17 +425,29 @@ __global__ void __launch_bounds__(kBlock) k_closest(SceneDev<R> s, Pools<R> p, c
 }
 
 // unoccluded shadow ray: L += Ld (a path owns at most one shadow ray per launch, so the update needs no atomic)
-template <typename R> RRT_DEV void add_pending(const Pools<R>& p, uint32_t i) {
+// PASSES: the any-hit launch belongs to a frame of rrt_render_passes. A template flag of the four any-hit kernels, as k_shade_path's: the
+// instantiations every other frame launches are the code they were.
+template <typename R, bool PASSES = false> RRT_DEV void add_pending(const Pools<R>& p, uint32_t i) {
   const typename Vec4T<R>::type ld = p.sld[i];
   const uint32_t slot = real_to_bits(ld.w);
   typename Vec4T<R>::type L = p.L[slot];
   L.x += ld.x; L.y += ld.y; L.z += ld.z;
   p.L[slot] = L;
+  // rrt_render_passes: the same term into the plane of every pass it counts for. A plane receives a slot's terms in the order L does - one shadow
+  // ray per path and launch - so a pass that takes every term holds L's own bits.
+  if (PASSES) {
+    for (uint32_t m = p.smask[i]; m != 0u; m &= m - 1u) {
+      typename Vec4T<R>::type* const q = p.pass_L + (size_t)(__ffs((int)m) - 1) * p.pass_stride + slot;
+      typename Vec4T<R>::type a = *q;
+      a.x += ld.x; a.y += ld.y; a.z += ld.z;
+      *q = a;
+    }
+  }
 }
 
 // Any-hit kernel over the shadow queue: VisibilityTester::unoccluded (lights/mod.rs:60-66); unoccluded paths
 // add their pending contribution to L (estimate_direct integrator/mod.rs:459-481).
-template <typename R, bool DEEP, bool COUNT>
+template <typename R, bool DEEP, bool COUNT, bool PASSES = false>
 __global__ void __launch_bounds__(kBlock) k_shadow(SceneDev<R> s, Pools<R> p, const uint32_t* queue, const uint32_t* count,
                                                     uint32_t* deep_stack, uint32_t deep_stride, unsigned long long* totals) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -449,7 +461,7 @@ __global__ void __launch_bounds__(kBlock) k_shadow(SceneDev<R> s, Pools<R> p, co
   const int skip = (int)real_to_bits(rd.w);
   if (DEEP) { GlobStack st{deep_stack + i, deep_stride}; occ = traverse_any(s, r, st, skip, &nn, &np); }
   else { PrivStack st; occ = traverse_any(s, r, st, skip, &nn, &np); }
-  if (!occ) add_pending(p, i);
+  if (!occ) add_pending<R, PASSES>(p, i);
   if (COUNT && totals) { atomicAdd(&totals[0], (unsigned long long)nn); atomicAdd(&totals[1], (unsigned long long)np); }
 }
 
@@ -1021,7 +1033,10 @@ template <uint32_t KM> constexpr int shade_path_waves() { return KM == kKindsLam
 // `ray = isect.spawn_ray(wi).into()` drops them afterwards, path.rs:163).
 // KM: the lobe kinds the scene's materials can produce (dmath.hpp "Lobe-kind sets"); kAllKinds = the general kernel.
 // AREA = false: every light of the scene is a point or distant light (no area-light sampling code, no light sample dimensions drawn).
-template <typename R, int NL, bool TEX = false, uint32_t KM = kAllKinds, bool AREA = true>
+// PASSES: the launch belongs to a frame of rrt_render_passes - a shadow record's pass mask (Pools::pass_tab) rides in bits 8 .. 23 of sh_tab, which the
+// start-triangle word's `<< 24` drops, and is stored beside the record (Pools::smask). A template flag, not a pointer test: the instantiations every
+// other frame launches are the code they were, register for register.
+template <typename R, int NL, bool TEX = false, uint32_t KM = kAllKinds, bool AREA = true, bool PASSES = false>
 __global__ void __launch_bounds__((shade_path_block<R, KM>())) __attribute__((amdgpu_waves_per_eu(TEX ? 1 : shade_path_waves<KM>(), 8))) k_shade_path(SceneDev<R> s, Pools<R> p) {
   __shared__ uint32_t push_lds[shade_path_block<R, KM>() / 64 + 1];
   // [r4] Hit compaction (option "shade_compact"). More than half of a queue's rays MISS on an open scene (config 4: 104 M queued closest-hit rays, ~47 M hits per
@@ -1110,6 +1125,7 @@ __global__ void __launch_bounds__((shade_path_block<R, KM>())) __attribute__((am
             sh_ld = beta * (ld / s.light_pick_pdf);
             sh_o = so; sh_d = sd;
             sh_tab = s.use_shadow_tabs ? s.lights[ln].shadow_tab : 0u;
+            if (PASSES) sh_tab |= (p.pass_tab[ln] & p.pass_tab[s.n_lights + bounces]) << 8;   // `bounces` is still this vertex's number (path.rs:51-226)
             want_shadow = true;
           }
         }
@@ -1176,6 +1192,7 @@ __global__ void __launch_bounds__((shade_path_block<R, KM>())) __attribute__((am
   if (want_shadow) {
     store_ray<R>(p.sray_o, p.sray_d, qs, sh_o, o_lo, sh_d, R(1) - R(0.0001), self_prim<R>(prim) | (int)(sh_tab << 24));   // (sh_tab != 0 only in fp32, where prim >= 0 and < 2^19)
     p.sld[qs] = mk4u<R>(sh_ld.r, sh_ld.g, sh_ld.b, slot);
+    if (PASSES) p.smask[qs] = sh_tab >> 8;
   }
   const uint32_t qn = block_push(&p.counters[C_NEXT], want_next, push_lds);
   if (want_next) {
@@ -1635,6 +1652,50 @@ __global__ void k_film_add(const R* src, R* dst, size_t n) {
   px[1] += R(0.212671) * cr + R(0.715160) * cg + R(0.072169) * cb;
   px[2] += R(0.019334) * cr + R(0.119193) * cg + R(0.950227) * cb;
   px[3] += wsum; px[3] += wsum; px[3] += wsum;
+}
+
+// rrt_combine_passes: out = sum_k rgb_to_xyz(gain_k * xyz_to_rgb(film_k)) per pixel, the weight channel film_0's. One thread per pixel reads all its inputs
+// before it writes, so the output may be one of the inputs. The arithmetic is f64 in both precisions (xyz_to_rgb has coefficients of both signs: in fp32
+// its cancellation would cost the digits the gain then scales) - a few dozen flops per pixel beside n 16-byte loads.
+// xyz_to_rgb here is CombineArgs::to_rgb, the inverse in f64 of the rgb_to_xyz table a film was merged with (k_film_add), not the six-digit table of
+// spectrum.rs:2075-2082: the two tables are inverses of each other only to 1.4e-6, and a relit frame is the frame of the scaled lights only as far as the
+// way back to RGB undoes the way there (f64: 5.1e-7 of the frame's largest value with the six-digit table, 1e-15 with the inverse).
+constexpr int kMaxPasses = 16;   // RRT_MAX_PASSES
+struct CombineArgs {
+  const void* films[kMaxPasses];
+  double gains[kMaxPasses][3];
+  double to_rgb[3][3];
+  int n;
+};
+// the inverse of k_film_add's rgb_to_xyz (spectrum.rs:2084-2090) by cofactors, in f64
+inline void combine_to_rgb(double inv[3][3]) {
+  const double m[3][3] = {{0.412453, 0.357580, 0.180423}, {0.212671, 0.715160, 0.072169}, {0.019334, 0.119193, 0.950227}};
+  const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+  const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
+  inv[0][0] = c00 / det; inv[1][0] = c01 / det; inv[2][0] = c02 / det;
+  inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det; inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det; inv[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det;
+  inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det; inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det; inv[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+}
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_combine_passes(CombineArgs a, R* out, size_t npix) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npix) return;
+  using V4 = typename Vec4T<R>::type;
+  double x = 0.0, y = 0.0, z = 0.0;
+  R w0 = R(0);
+  for (int k = 0; k < a.n; k++) {
+    const V4 f = reinterpret_cast<const V4*>(a.films[k])[i];
+    if (k == 0) w0 = f.w;
+    const double fx = (double)f.x, fy = (double)f.y, fz = (double)f.z;
+    // back to RGB (to_rgb), the gain, rgb_to_xyz spectrum.rs:2084-2090
+    const double r = (a.to_rgb[0][0] * fx + a.to_rgb[0][1] * fy + a.to_rgb[0][2] * fz) * a.gains[k][0];
+    const double g = (a.to_rgb[1][0] * fx + a.to_rgb[1][1] * fy + a.to_rgb[1][2] * fz) * a.gains[k][1];
+    const double b = (a.to_rgb[2][0] * fx + a.to_rgb[2][1] * fy + a.to_rgb[2][2] * fz) * a.gains[k][2];
+    x += 0.412453 * r + 0.357580 * g + 0.180423 * b;
+    y += 0.212671 * r + 0.715160 * g + 0.072169 * b;
+    z += 0.019334 * r + 0.119193 * g + 0.950227 * b;
+  }
+  reinterpret_cast<V4*>(out)[i] = mk4<R>((R)x, (R)y, (R)z, w0);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -304,7 +304,7 @@ RRT_DEV bool leaf_step_f32(const TravScene& ts, uint32_t word, LaneRay& r, int* 
 //              are the pool's closest-ray arrays and the verdict is written to occluded[i] (public rrt_trace_any).
 // Grid-stride form for small queues: the wave alternates between "every lane walks interior nodes until it holds a leaf" and "every lane
 // tests its leaf" (while-while); the BFS top of the tree is read from LDS.
-template <bool ANY, bool MIXED = false>
+template <bool ANY, bool MIXED = false, bool PASSES = false>
 __global__ void __launch_bounds__(kTravBlock) k_trace_pairs_f32(TravScene ts, Pools<float> p, const uint32_t* queue, const uint32_t* count,
                                                                  uint32_t n_fixed, uint8_t* occluded, uint32_t n_lo, uint32_t n_hi) {
   {  // queue-size regime of this kernel (the other traversal kernel is launched next to it for the other regime)
@@ -374,7 +374,7 @@ __global__ void __launch_bounds__(kTravBlock) k_trace_pairs_f32(TravScene ts, Po
     }
     if (ANY) {
       if (occluded) occluded[gid] = found ? 1 : 0;
-      else if (!found) add_pending(p, gid);
+      else if (!found) add_pending<float, PASSES>(p, gid);
     } else {
       p.hit[gid] = make_float4(r.tmax, __uint_as_float((uint32_t)hit), hu, hv);
     }
@@ -478,7 +478,7 @@ __device__ unsigned long long g_pt_stats[2][16];
 #else
 #define RRT_PT_ATTR
 #endif
-template <bool ANY, bool MIXED = false, bool QUAD = false>
+template <bool ANY, bool MIXED = false, bool QUAD = false, bool PASSES = false>
 __global__ void __launch_bounds__(kPtBlock) RRT_PT_ATTR k_trace_pt_f32(TravScene ts, Pools<float> p, const uint32_t* queue, const uint32_t* count,
                                                             uint32_t n_fixed, uint32_t* work, uint8_t* occluded, uint32_t n_lo, uint32_t n_hi) {
   static_assert(!QUAD || (!ANY && !MIXED), "quad nodes: closest-hit rays of plain triangle scenes only");
@@ -528,7 +528,7 @@ __global__ void __launch_bounds__(kPtBlock) RRT_PT_ATTR k_trace_pt_f32(TravScene
   auto finish = [&](bool found) {
     if (ANY) {
       if (occluded) occluded[qidx] = found ? 1 : 0;
-      else if (!found) add_pending(p, qidx);
+      else if (!found) add_pending<float, PASSES>(p, qidx);
     } else {
       p.hit[qidx] = make_float4(r.tmax, __uint_as_float((uint32_t)hit), hu, hv);
     }
@@ -990,6 +990,7 @@ RRT_DEV bool walk_any_private_f32(const TravScene& ts, LaneRay& r) {
 #define RRT_SL_SORT 0   // measured and off: see the kernel
 #endif
 constexpr int kSlBlock = RRT_SL_BLOCK;
+template <bool PASSES = false>
 static __global__ void __launch_bounds__(kSlBlock) k_shadow_lists_f32(TravScene ts, ShadowLists sl, Pools<float> p, const uint32_t* count) {
   const uint32_t n = *count;
 #if RRT_SL_SORT
@@ -1099,7 +1100,7 @@ static __global__ void __launch_bounds__(kSlBlock) k_shadow_lists_f32(TravScene 
 #endif
       }
     }
-    if (!found) add_pending(p, i);
+    if (!found) add_pending<float, PASSES>(p, i);
   }
 }
 

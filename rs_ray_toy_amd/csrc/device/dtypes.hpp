@@ -129,6 +129,13 @@ struct Pools {
   V4 *rdx_o, *rdx_d, *rdy_o, *rdy_d;
   uint32_t* counters;    // [0] active, [1] next, [2] shadow, [3] camera rays, [4..] stats
   uint32_t* shadow_count;  // the shadow queue's counter (the path integrator alternates two shadow queues, see render_impl)
+  // rrt_render_passes (all null / 0 in every other frame; kept last, so that no other member moves in the kernels' argument blocks)
+  uint32_t* smask;         // beside sld, per shadow queue: bit k set = the pending contribution also counts for pass k
+  V4* pass_L;              // one radiance plane per pass, each pass_stride slots: plane k of slot s at pass_L[k * pass_stride + s]
+  size_t pass_stride;
+  // the call's pass table folded per light and per path vertex on the host: the mask of light ln at vertex b is pass_tab[ln] & pass_tab[n_lights + b]
+  // (n_lights + max_depth words; bit k of a light's word: its group is in pass k's groups, of a vertex's word: bounce_lo <= b < bounce_hi of pass k)
+  const uint32_t* pass_tab;
 };
 
 }  // namespace rrtd

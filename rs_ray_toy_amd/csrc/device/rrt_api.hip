@@ -230,6 +230,34 @@ int rrt_render_adaptive(rrt_handle* h, const int32_t rect[4], const rrt_adaptive
   return guarded([&]() { h->impl->render_adaptive(rect, &p, film_xyzw, moments, tile_samples, mem, stats); });
 }
 
+int rrt_render_passes(rrt_handle* h, const int32_t rect[4], int rank, int world, const uint8_t* light_group, const rrt_pass* passes, int n_passes, void* film_xyzw, int mem,
+                      rrt_render_stats* stats) {
+  // the caller's own arguments first (wrong whichever handle they come with), each with its own message; the light_group entries, whose number is the
+  // handle's, are the first thing the handle checks - also before any device work
+  static_assert(RRT_MAX_PASSES == rrtd::kMaxPasses && RRT_MAX_PASSES <= 16, "a pass mask rides in 16 bits of a shadow record's table word");
+  if (!rect) { rrt::set_last_error("rrt_render_passes: null rect"); return RRT_EINVAL; }
+  if (!passes) { rrt::set_last_error("rrt_render_passes: null passes"); return RRT_EINVAL; }
+  if (n_passes < 1 || n_passes > RRT_MAX_PASSES) { rrt::set_last_error("rrt_render_passes: n_passes must be 1 .. 16 (RRT_MAX_PASSES)"); return RRT_EINVAL; }
+  for (int k = 0; k < n_passes; k++) {
+    if (!passes[k].film_xyzw) { rrt::set_last_error("rrt_render_passes: null pass film (passes[" + std::to_string(k) + "].film_xyzw)"); return RRT_EINVAL; }
+    if (passes[k].bounce_lo < 0) { rrt::set_last_error("rrt_render_passes: passes[" + std::to_string(k) + "].bounce_lo must be >= 0"); return RRT_EINVAL; }
+  }
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_passes: bad mem"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_render_passes: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_passes(rect, rank, world, light_group, passes, n_passes, film_xyzw, mem, stats); });
+}
+
+int rrt_combine_passes(rrt_handle* h, const void* const* films, const double* gains_rgb, int n, void* film_out, int mem) {
+  if (!films) { rrt::set_last_error("rrt_combine_passes: null films"); return RRT_EINVAL; }
+  if (!gains_rgb) { rrt::set_last_error("rrt_combine_passes: null gains"); return RRT_EINVAL; }
+  if (!film_out) { rrt::set_last_error("rrt_combine_passes: null output film"); return RRT_EINVAL; }
+  if (n < 1 || n > RRT_MAX_PASSES) { rrt::set_last_error("rrt_combine_passes: n must be 1 .. 16 (RRT_MAX_PASSES)"); return RRT_EINVAL; }
+  for (int k = 0; k < n; k++) if (!films[k]) { rrt::set_last_error("rrt_combine_passes: null film (films[" + std::to_string(k) + "])"); return RRT_EINVAL; }
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_combine_passes: bad mem"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_combine_passes: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->combine_passes(films, gains_rgb, n, film_out, mem); });
+}
+
 int rrt_set_option(rrt_handle* h, const char* key, double value) {
   if (!h || !key) { rrt::set_last_error("rrt_set_option: null argument"); return RRT_EINVAL; }
   return guarded([&]() { h->impl->set_option(key, value); });

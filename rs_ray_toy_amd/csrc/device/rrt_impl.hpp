@@ -52,6 +52,8 @@ struct HandleBase {
   virtual void render_frame_aov(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, uint64_t aov_max_samples, const rrt_aov* aov, rrt_render_stats* stats) = 0;   // moments may be NULL
   virtual void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film, void* moments, uint32_t* tile_samples, int mem, rrt_render_stats* stats) = 0;
   virtual void tile_error(const void* moments, int mem, const int32_t rect[4], double* tile_error) = 0;
+  virtual void render_passes(const int32_t rect[4], int rank, int world, const uint8_t* light_group, const rrt_pass* passes, int n_passes, void* film, int mem, rrt_render_stats* stats) = 0;   // film may be NULL
+  virtual void combine_passes(const void* const* films, const double* gains_rgb, int n, void* film_out, int mem) = 0;
   virtual void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) = 0;   // moments may be NULL (rrt_denoise)
   virtual void set_option(const std::string& key, double v) = 0;
   // rrt_film_gather (rrt_comm.hip): events on the handle's stream around the frame's collective, so that the frame's statistics can tell
@@ -344,13 +346,70 @@ class Handle : public HandleBase {
     render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user, &fa);
     if (!queued) render_aov(rect, rank, world, aov_max_samples, aov);
   }
+  // ---- rrt_render_passes: the frame, and beside it the films of its next-event terms split by light group and path vertex --------------------------------
+  // render_impl in its passes mode: the passes of a frame with film_records off (per-slot layout, as a moments frame), the PASSES instantiations of
+  // k_shade_path, which store a pass mask beside every shadow record (Pools::smask, from the table folded here), add_pending adding an unoccluded record
+  // to the radiance plane of every pass in its mask, and the frame's own film kernel run once more per plane into that pass's internal film.
+  void render_passes(const int32_t rect[4], int rank, int world, const uint8_t* light_group, const rrt_pass* passes, int n_passes, void* film_user, int mem, rrt_render_stats* stats) override {
+    const uint32_t nl = (uint32_t)desc_.n_lights;
+    if (light_group) for (uint32_t i = 0; i < nl; i++)
+      if (light_group[i] >= 32) throw std::invalid_argument("render_passes: light_group[" + std::to_string(i) + "] = " + std::to_string((int)light_group[i]) + ": a group is 0 .. 31");
+    if (pending_) throw std::invalid_argument("render_passes: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_passes: bad rank/world");
+    const rrt_film& f = desc_.film;
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_passes: rect outside the film");
+    if (desc_.integrator.type != RRT_INT_PATH)
+      throw UnsupportedError("render_passes: the passes are the Path integrator's next-event terms; DirectLighting, AO and Debug frames have no passes");
+    if (!std::isinf(f.max_sample_luminance))
+      throw UnsupportedError("render_passes: a finite Film.max_sample_luminance clamps by the whole sample's luminance, so the passes would no longer add up to the frame");
+    // the call's table folded per light and per vertex (Pools::pass_tab)
+    const int depth = std::max(0, desc_.integrator.max_depth);
+    pass_tab_host_.assign((size_t)nl + (size_t)depth, 0u);
+    for (int k = 0; k < n_passes; k++) {
+      for (uint32_t i = 0; i < nl; i++) {
+        const uint32_t g = light_group ? light_group[i] : std::min(i, 31u);
+        if ((passes[k].groups >> g) & 1u) pass_tab_host_[i] |= 1u << k;
+      }
+      for (int b = 0; b < depth; b++)
+        if (b >= passes[k].bounce_lo && (passes[k].bounce_hi <= 0 || b < passes[k].bounce_hi)) pass_tab_host_[nl + (size_t)b] |= 1u << k;
+    }
+    const PassesReq pq{passes, n_passes};
+    render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, nullptr, nullptr, &pq);
+  }
+  struct PassesReq { const rrt_pass* passes; int n; };
+  // rrt_combine_passes: one kernel over the pixels; films in host memory are staged
+  void combine_passes(const void* const* films, const double* gains_rgb, int n, void* film_out, int mem) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    using V4 = typename Vec4T<R>::type;
+    const size_t npix = (size_t)desc_.film.xres * (size_t)desc_.film.yres;
+    CombineArgs a{};
+    a.n = n;
+    combine_to_rgb(a.to_rgb);
+    for (int k = 0; k < n; k++) for (int c = 0; c < 3; c++) a.gains[k][c] = gains_rgb[3 * k + c];
+    DevBuf<V4> stage;
+    R* out = (R*)film_out;
+    if (mem == RRT_MEM_DEVICE) for (int k = 0; k < n; k++) a.films[k] = films[k];
+    else {
+      stage.alloc((size_t)(n + 1) * npix);
+      for (int k = 0; k < n; k++) {
+        HIP_CHECK(hipMemcpyAsync(stage.p + (size_t)k * npix, films[k], npix * sizeof(V4), hipMemcpyHostToDevice, st_));
+        a.films[k] = stage.p + (size_t)k * npix;
+      }
+      out = (R*)(stage.p + (size_t)n * npix);
+    }
+    hipLaunchKernelGGL((k_combine_passes<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, a, out, npix);
+    HIP_CHECK(hipGetLastError());
+    if (mem != RRT_MEM_DEVICE) HIP_CHECK(hipMemcpyAsync(film_out, out, npix * sizeof(V4), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+  }
   // the feature buffers a frame was asked for: the caller's planes, and the leading samples that run_pass shades and gathers (0: none - the frame is
   // only held to its moments mode)
   struct FrameAov { const rrt_aov* out; uint64_t prefix; };
   // moments_user: the caller's sample-variance plane (same memory kind as the film) = the frame's moments mode; NULL = a plain frame, unless `fa` asks
   // for a moments-mode frame whose plane is not handed out
   void render_impl(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, void* film_user, int film_mem, rrt_render_stats* stats, void* moments_user = nullptr,
-                   const FrameAov* fa = nullptr) {
+                   const FrameAov* fa = nullptr, const PassesReq* pq = nullptr) {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
     const rrt_film& f = desc_.film;
@@ -369,6 +428,9 @@ class Handle : public HandleBase {
     if (rpix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }   // a rank that owns no band (world > yres / 16): nothing to add to the caller's film
 
     const bool with_moments = moments_user != nullptr || fa != nullptr;
+    // run_pass, rect_passes and frame_setup work for a passes frame while passes_n_ > 0; the pools' passes members are null in every other frame
+    struct PassesOff { Handle* h; ~PassesOff() { h->passes_n_ = 0; h->pool_.smask = nullptr; h->pool_.pass_L = nullptr; h->pool_.pass_stride = 0; h->pool_.pass_tab = nullptr; } } passes_off{this};
+    passes_n_ = pq ? (uint32_t)pq->n : 0u;
     frame_setup(with_moments, rpix * (size_t)std::max<uint64_t>(s_total, 1));
     struct AovOff { Handle* h; ~AovOff() { h->aov_prefix_ = 0; } } aov_off{this};   // run_pass shades first hits for this frame only
     aov_prefix_ = fa ? fa->prefix : 0;
@@ -385,8 +447,13 @@ class Handle : public HandleBase {
     rect_passes(rect, band_h, n_ranks, rank, rw, rh, 0, s_total, with_moments, *fr);
     if (timing) HIP_CHECK(hipEventRecord(fr->ev_end, st_));
     // merge into the caller's film (+=)
-    const bool wait = !(film_mem == RRT_MEM_DEVICE && defer_);
-    merge_out(film_user, moments_user, film_mem, wait);
+    const bool wait = !(film_mem == RRT_MEM_DEVICE && defer_) || pq != nullptr;
+    if (pq) {   // each pass's internal film into its caller's film, as the frame's own below
+      const size_t nfilm = (size_t)f.xres * (size_t)f.yres * 4;
+      for (int k = 0; k < pq->n; k++) merge_film(pass_films_.p + (size_t)k * nfilm, pq->passes[k].film_xyzw, film_mem);
+    }
+    if (film_user || !pq) merge_out(film_user, moments_user, film_mem, wait);
+    else HIP_CHECK(hipStreamSynchronize(st_));
     if (!wait) { frame_ = std::move(fr); return; }   // render_end() synchronises, checks the error flags and reads the statistics
     if (aov_prefix_ > 0) aov_merge_out(fa->out);
     check_device_errors();
@@ -415,6 +482,7 @@ class Handle : public HandleBase {
       P = std::max<size_t>(64, std::min(P, (free_b / 4) / per_slot));
     }
     ensure_pools(P);
+    if (passes_n_ > 0) passes_setup(P);
     if constexpr (std::is_same<R, float>::value) {
       if (tt_state_ == 0 && tile_trees_on_) {
         build_tile_trees();
@@ -422,11 +490,35 @@ class Handle : public HandleBase {
       }
     }
   }
+  // rrt_render_passes: the passes' internal films (zeroed), the table, one radiance plane per pass and a mask array per shadow queue. The planes come
+  // after the pools: a pool pass of such a frame holds at most pass_cap_ slots - what the pools hold, or what half of the memory still free lets the
+  // planes hold.
+  void passes_setup(size_t want) {
+    using V4 = typename Vec4T<R>::type;
+    const size_t nfilm = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
+    if (pass_films_.n < passes_n_ * nfilm) pass_films_.alloc(passes_n_ * nfilm);
+    HIP_CHECK(hipMemsetAsync(pass_films_.p, 0, passes_n_ * nfilm * sizeof(R), st_));
+    if (pass_tab_.n < pass_tab_host_.size()) { HIP_CHECK(hipStreamSynchronize(st_)); pass_tab_.alloc(pass_tab_host_.size()); }
+    if (!pass_tab_host_.empty()) HIP_CHECK(hipMemcpyAsync(pass_tab_.p, pass_tab_host_.data(), pass_tab_host_.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+    size_t P = std::min(cap_, std::max<size_t>(want, 64));
+    if (pass_planes_.n < passes_n_ * P || pass_smask_[0].n < P) {
+      HIP_CHECK(hipStreamSynchronize(st_));
+      pass_planes_.release(); pass_smask_[0].release(); pass_smask_[1].release();
+      size_t free_b = 0, total_b = 0;
+      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+      P = std::max<size_t>(64, std::min(P, (free_b / 2) / (passes_n_ * sizeof(V4) + 2 * sizeof(uint32_t))));
+      pass_planes_.alloc(passes_n_ * P);
+      pass_smask_[0].alloc(P); pass_smask_[1].alloc(P);
+    }
+    pass_cap_ = P;
+    pool_.pass_L = pass_planes_.p; pool_.pass_stride = P; pool_.pass_tab = pass_tab_.p; pool_.smask = pass_smask_[0].p;
+  }
   // the passes of sample numbers 1 + s_lo .. s_hi of a rect's (or its bands') rw x rh pixels: pixel groups and sample chunks from what the pools hold
   void rect_passes(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_lo, uint64_t s_hi, bool with_moments, FrameRec& fr) {
     const size_t rpix = rw * rh;
-    const size_t group = std::min(rpix, cap_);                           // pixels per group
-    const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);         // samples per pass
+    const size_t cap = passes_n_ > 0 ? pass_cap_ : cap_;
+    const size_t group = std::min(rpix, cap);                            // pixels per group
+    const uint64_t s_chunk = std::max<uint64_t>(1, cap / group);          // samples per pass
     for (size_t g0 = 0; g0 < rpix && s_hi > s_lo; g0 += group) {
       const size_t npix = std::min(group, rpix - g0);
       for (uint64_t sb = s_lo; sb < s_hi; sb += s_chunk) {
@@ -470,7 +562,9 @@ class Handle : public HandleBase {
     const uint32_t aov_ns = (!list && aov_prefix_ > s_off) ? (uint32_t)std::min<uint64_t>(ns, aov_prefix_ - s_off) : 0u;
     hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
     size_t e = tick(0);
-    launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments, list);
+    launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments && passes_n_ == 0, list);
+    // rrt_render_passes: this pool pass's slots of every plane start at 0, as raygen starts L (on the main stream: the shadow stream waits for shading)
+    for (uint32_t k = 0; k < passes_n_; k++) HIP_CHECK(hipMemsetAsync(pool_.pass_L + (size_t)k * pool_.pass_stride, 0, nslots * sizeof(typename Vec4T<R>::type), st_));
     tock(e);
     hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
     if (integ == RRT_INT_PATH) {
@@ -479,6 +573,7 @@ class Handle : public HandleBase {
       auto use_shadow_queue = [&](int k) {
         pool_.sray_o = shadow_buf_[k][0]; pool_.sray_d = shadow_buf_[k][1]; pool_.sld = shadow_buf_[k][2];
         pool_.shadow_count = counters_.p + (k ? C_SHADOW2 : C_SHADOW);
+        if (passes_n_ > 0) pool_.smask = pass_smask_[k].p;
       };
       for (int b = 0; b < max_depth; b++) {
         hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
@@ -494,19 +589,7 @@ class Handle : public HandleBase {
         scene_.use_shadow_tabs = use_shadow_lists() ? 1u : 0u;
         scene_.horizon = (horizon_on_ && horizon_.n) ? horizon_.p : nullptr; scene_.hz_tau = horizon_tau_.p; scene_.hz_axis = hz_axis_;   // (counting frames too: the cull is geometry, not a kernel's arithmetic - their node counters then hold the rays that are traced)
         e = tick(3);
-        if (tex_depth_ > 0) hipLaunchKernelGGL((k_shade_path<R, 4, true>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
-        else if (has_translucent_) hipLaunchKernelGGL((k_shade_path<R, 4>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
-        else if (shade_kinds_ == kKindsLambert) {
-          constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsLambert>();
-          const dim3 g(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u));
-          if (area_lights_ || shade_kinds_ == kAllKinds) hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, true>), g, dim3(kB), 0, st_, scene_, pool_);
-          else hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, false>), g, dim3(kB), 0, st_, scene_, pool_);
-        }
-        else if (shade_kinds_ == kKindsGlossy) {
-          constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsGlossy>();
-          hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsGlossy>), dim3(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u)), dim3(kB), 0, st_, scene_, pool_);
-        }
-        else hipLaunchKernelGGL((k_shade_path<R, 2>), dim3(std::min(sgrid, 16384u)), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_);
+        if (passes_n_ > 0) launch_shade_path<true>(nslots, sgrid); else launch_shade_path<false>(nslots, sgrid);
         tock(e);
         if (scene_.horizon) hipLaunchKernelGGL(k_accumulate_sky, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
         if (overlap) {
@@ -579,29 +662,54 @@ class Handle : public HandleBase {
       }
     }
     e = tick(4);
-    if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
-      if constexpr (std::is_same<R, float>::value)
-        hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_.p, film_runs_.p, (uint32_t)(ns / 8));
+    // rrt_render_passes: after the frame's own film (k = -1) the same kernel once per pass, with L pointing at the pass's radiance plane, into the
+    // pass's internal film
+    typename Vec4T<R>::type* const frame_L = pool_.L;
+    for (int k = -1; k < (int)passes_n_; k++) {
+      R* const film_dst = k < 0 ? film_.p : pass_films_.p + (size_t)k * ((size_t)f.xres * (size_t)f.yres * 4);
+      if (k >= 0) pool_.L = pool_.pass_L + (size_t)k * pool_.pass_stride;
+      if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
+        if constexpr (std::is_same<R, float>::value)
+          hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_dst, film_runs_.p, (uint32_t)(ns / 8));
+      }
+      else if (!wide_filter) {
+        const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
+        if (list) hipLaunchKernelGGL((k_film_box_moments_list<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_dst, moments_.p);
+        else if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p);
+        else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst);
+      }
+      else {
+        // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
+        const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+        const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+        const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+        const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
+        const dim3 fg((uint32_t)((en + kBlock - 1) / kBlock));
+        if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+        else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+      }
     }
-    else if (!wide_filter) {
-      const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
-      if (list) hipLaunchKernelGGL((k_film_box_moments_list<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_.p, moments_.p);
-      else if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p);
-      else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p);
-    }
-    else {
-      // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
-      const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-      const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-      const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-      const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-      const dim3 fg((uint32_t)((en + kBlock - 1) / kBlock));
-      if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, moments_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-      else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-    }
+    pool_.L = frame_L;
     tock(e);
     if (aov_ns > 0) launch_aov_gather_frame(pd, aov_ns, rect, wide_filter);
     HIP_CHECK(hipGetLastError());
+  }
+  // the path shading kernel the scene's materials select (shade_kinds_); PS: its rrt_render_passes instantiation
+  template <bool PS>
+  void launch_shade_path(size_t nslots, uint32_t sgrid) {
+    if (tex_depth_ > 0) hipLaunchKernelGGL((k_shade_path<R, 4, true, kAllKinds, true, PS>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
+    else if (has_translucent_) hipLaunchKernelGGL((k_shade_path<R, 4, false, kAllKinds, true, PS>), dim3(std::min((uint32_t)((nslots + 255) / 256), 16384u)), dim3(256), 0, st_, scene_, pool_);
+    else if (shade_kinds_ == kKindsLambert) {
+      constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsLambert>();
+      const dim3 g(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u));
+      if (area_lights_ || shade_kinds_ == kAllKinds) hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, true, PS>), g, dim3(kB), 0, st_, scene_, pool_);
+      else hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsLambert, false, PS>), g, dim3(kB), 0, st_, scene_, pool_);
+    }
+    else if (shade_kinds_ == kKindsGlossy) {
+      constexpr uint32_t kB = (uint32_t)shade_path_block<R, kKindsGlossy>();
+      hipLaunchKernelGGL((k_shade_path<R, 2, false, kKindsGlossy, true, PS>), dim3(std::min((uint32_t)((nslots + kB - 1) / kB), 16384u)), dim3(kB), 0, st_, scene_, pool_);
+    }
+    else hipLaunchKernelGGL((k_shade_path<R, 2, false, kAllKinds, true, PS>), dim3(std::min(sgrid, 16384u)), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_);
   }
   // rrt_render_frame_aov, first half of a pass: the first hits of the queue the bounce-0 closest-hit launch has just answered, under a stamp that no
   // earlier pass has written into the record buffers. It reads the queue and writes its own records: the shadow stream is not involved.
@@ -661,29 +769,38 @@ class Handle : public HandleBase {
       }
     }
   }
+  // one internal film (RGB sums + weight sum), converted to XYZ, added to a caller's film (+=): enqueued for device memory, done on return for host memory
+  void merge_film(const R* src, void* film_user, int film_mem) {
+    const size_t npx = (size_t)desc_.film.xres * (size_t)desc_.film.yres, nfilm = npx * 4;
+    if (film_mem == RRT_MEM_DEVICE) {
+      hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, src, (R*)film_user, npx);
+      return;
+    }
+    if (film_xyz_.n != nfilm) film_xyz_.alloc(nfilm);
+    HIP_CHECK(hipMemsetAsync(film_xyz_.p, 0, nfilm * sizeof(R), st_));
+    hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, src, film_xyz_.p, npx);
+    HIP_CHECK(hipGetLastError());
+    std::vector<R> tmp(nfilm);
+    HIP_CHECK(hipMemcpyAsync(tmp.data(), film_xyz_.p, nfilm * sizeof(R), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    R* dst = (R*)film_user;
+    for (size_t i = 0; i < nfilm; i++) dst[i] += tmp[i];
+  }
   // the internal film, converted to XYZ, and the internal moments buffer (where moments_user is given) added to the caller's buffers (+=); wait = 0
   // (device memory only): enqueued, not waited for
   void merge_out(void* film_user, void* moments_user, int film_mem, bool wait) {
     const size_t W = (size_t)desc_.film.xres, H = (size_t)desc_.film.yres;
     const bool with_moments = moments_user != nullptr;
-    const size_t nfilm = W * H * 4, npx = W * H;
+    const size_t nfilm = W * H * 4;
+    merge_film(film_.p, film_user, film_mem);
     if (film_mem == RRT_MEM_DEVICE) {
-      hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)film_.p, (R*)film_user, npx);
       if (with_moments) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((nfilm + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)moments_.p, (R*)moments_user, nfilm);
       HIP_CHECK(hipGetLastError());
       if (!wait) return;
       HIP_CHECK(hipStreamSynchronize(st_));
     } else {
-      if (film_xyz_.n != nfilm) film_xyz_.alloc(nfilm);
-      HIP_CHECK(hipMemsetAsync(film_xyz_.p, 0, nfilm * sizeof(R), st_));
-      hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)film_.p, film_xyz_.p, npx);
-      HIP_CHECK(hipGetLastError());
-      std::vector<R> tmp(nfilm);
-      HIP_CHECK(hipMemcpyAsync(tmp.data(), film_xyz_.p, nfilm * sizeof(R), hipMemcpyDeviceToHost, st_));
-      HIP_CHECK(hipStreamSynchronize(st_));
-      R* dst = (R*)film_user;
-      for (size_t i = 0; i < nfilm; i++) dst[i] += tmp[i];
       if (with_moments) {
+        std::vector<R> tmp(nfilm);
         HIP_CHECK(hipMemcpyAsync(tmp.data(), moments_.p, nfilm * sizeof(R), hipMemcpyDeviceToHost, st_));
         HIP_CHECK(hipStreamSynchronize(st_));
         R* dm = (R*)moments_user;
@@ -1151,6 +1268,14 @@ class Handle : public HandleBase {
   DevBuf<typename Vec4T<R>::type> dn_stage_m_;   // denoise with a moments plane in host memory: its staging
   bool dn_lds_ = true;       // option "dn_lds"
   DevBuf<typename Vec4T<R>::type> aov_rec_a_, aov_rec_b_;   // k_aov_shade's per-slot records {rho.rgb, hit flag}, {n.xyz, t}: sized like pool.L
+  // render_passes (all allocated by the first call): the passes' internal films, the folded pass table (Pools::pass_tab) and its host copy, the radiance
+  // planes, the mask arrays of the two shadow queues; passes_n_ = the passes of the frame being rendered, 0 outside such a frame
+  DevBuf<R> pass_films_;
+  DevBuf<uint32_t> pass_tab_, pass_smask_[2];
+  std::vector<uint32_t> pass_tab_host_;
+  DevBuf<typename Vec4T<R>::type> pass_planes_;
+  size_t pass_cap_ = 0;
+  uint32_t passes_n_ = 0;
   uint64_t aov_prefix_ = 0;   // render_frame_aov: the leading samples whose first hits run_pass shades and gathers; 0 outside such a frame
   uint32_t aov_serial_ = 0;   // k_aov_shade_frame's stamp of the pass last shaded: counted up per pass over the handle's life, never 0 in a record
 
@@ -1514,6 +1639,7 @@ class Handle : public HandleBase {
       // cost — the latency chain of the longest ray — is lower). trav_mode_: 1 = grid-stride only, 2 = persistent
       // only, 3 = both by regime.
       const uint32_t split = any ? pt_split_any_ : pt_split_closest_;
+      const bool ps = passes_n_ > 0 && occluded == nullptr;   // the shadow launch of a passes frame: add_pending<float, true> (rrt_trace_any hands in `occluded`)
       const uint32_t lo_pt = trav_mode_ == 2 ? 0u : (trav_mode_ == 1 ? 0xffffffffu : split);
       const uint32_t hi_gs = trav_mode_ == 1 ? 0xffffffffu : (trav_mode_ == 2 ? 0u : split);
       // The grid-stride kernel goes FIRST. Both kernels are launched for every queue and the one whose regime it is not returns at once - but
@@ -1524,10 +1650,12 @@ class Handle : public HandleBase {
       if (trav_mode_ != 2) {
         if (trav_mode_ == 3) grid = std::max(1u, std::min(grid, (split + kTravBlock - 1) / kTravBlock));
         if (mixed_) {
-          if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          else if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
           else hipLaunchKernelGGL((k_trace_pairs_f32<false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
         } else {
-          if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          else if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
           else hipLaunchKernelGGL((k_trace_pairs_f32<false, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
         }
       }
@@ -1573,10 +1701,12 @@ class Handle : public HandleBase {
           const uint32_t gq = std::max(1u, std::min(grid_in, pt_grid_quad_));
           hipLaunchKernelGGL((k_trace_pt_f32<false, false, true>), dim3(gq), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
         } else if (mixed_) {
-          if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, true, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          else if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
           else hipLaunchKernelGGL((k_trace_pt_f32<false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
         } else {
-          if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          else if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
           else hipLaunchKernelGGL((k_trace_pt_f32<false, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
         }
       }
@@ -1667,7 +1797,8 @@ class Handle : public HandleBase {
     if constexpr (std::is_same<R, float>::value) {
       if (use_shadow_lists()) {   // (the shading kernel stored the light table with the ray's start triangle: scene_.use_shadow_tabs)
         const uint32_t g = std::max(1u, std::min((uint32_t)(((size_t)grid * kBlock + kSlBlock - 1) / kSlBlock), (uint32_t)sl_grid_cap_));
-        hipLaunchKernelGGL(k_shadow_lists_f32, dim3(g), dim3(kSlBlock), 0, stream, trav_, sl_dev_, pool_, pool_.shadow_count);
+        if (passes_n_ > 0) hipLaunchKernelGGL((k_shadow_lists_f32<true>), dim3(g), dim3(kSlBlock), 0, stream, trav_, sl_dev_, pool_, pool_.shadow_count);
+        else hipLaunchKernelGGL((k_shadow_lists_f32<false>), dim3(g), dim3(kSlBlock), 0, stream, trav_, sl_dev_, pool_, pool_.shadow_count);
         HIP_CHECK(hipGetLastError());
         return;
       }
@@ -1677,10 +1808,14 @@ class Handle : public HandleBase {
     const uint32_t stride = deep_ ? (uint32_t)cap_ : 0u;
     unsigned long long* tot = count_traversal_ ? totals_.p + 5 : nullptr;
     if (deep_) {
-      if (count_traversal_) hipLaunchKernelGGL((k_shadow<R, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
+      if (count_traversal_ && passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, true, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
+      else if (count_traversal_) hipLaunchKernelGGL((k_shadow<R, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
+      else if (passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, true, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
       else hipLaunchKernelGGL((k_shadow<R, true, false>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
     } else {
-      if (count_traversal_) hipLaunchKernelGGL((k_shadow<R, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
+      if (count_traversal_ && passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, false, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
+      else if (count_traversal_) hipLaunchKernelGGL((k_shadow<R, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
+      else if (passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, false, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
       else hipLaunchKernelGGL((k_shadow<R, false, false>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
     }
     HIP_CHECK(hipGetLastError());
