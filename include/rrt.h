@@ -596,6 +596,54 @@ int rrt_render_passes(rrt_handle*, const int32_t rect[4], int rank, int world,
  * films[k], gains_rgb or film_out, n outside 1 .. RRT_MAX_PASSES and a bad mem, all before any device work. */
 int rrt_combine_passes(rrt_handle*, const void* const* films, const double* gains_rgb /* n x 3 */, int n, void* film_out, int mem);
 
+/* ID mattes beside the film (no counterpart in the reference): which object each pixel shows - per pixel a table of K (id, coverage) slots, the
+ * filtered coverage of the ids its camera samples hit first, ranked (the information a Cryptomatte layer carries), and a weight record to
+ * normalise it. The call takes exactly the camera samples rrt_render_aov(h, rect, rank, world, max_samples, ...) takes; live samples, fw and the
+ * first hit (what rrt_trace_closest reports for the camera ray) are rrt_render_aov's. ids, coverage and weight are full-frame buffers in `mem`.
+ *   id of a hit sample: prim_id[prim_order[hit.prim]] - the caller's value for the primitive that was hit, any uint32_t; with prim_id == NULL,
+ *                prims[prim_order[hit.prim]].material + 1.
+ *   table rule:  a pixel's table is its K slots in stored order; a slot is empty when its coverage is 0. The call reads the caller's table,
+ *                continues it and writes it back (zeroed buffers are an empty table). For every live sample with fw != 0 that covers the pixel, in
+ *                arrival order: weight[0] += fw; if it hit something, weight[1] += fw, and then a non-empty slot holding its id takes += fw,
+ *                otherwise the first empty slot takes (id, fw), otherwise weight[2] += fw (overflow). Nothing is ever evicted: every coverage
+ *                stored by a call on zeroed buffers is its id's complete sum, sum of slots + weight[2] == weight[1] up to rounding (exactly for
+ *                the box filter of radius 0.5, whose weights are integers), and a pixel with weight[2] == 0 holds the complete list.
+ *   arrival order: box filter of radius 0.5: sample-number order, so the table does not depend on how the frame is cut into pool passes. Every
+ *                other filter: the implementation's order - where a pixel meets more than K ids, which K are kept is not specified, only the
+ *                identities above are.
+ *   on the way out: every pixel's slots are sorted by coverage descending, ties by ascending id; empty slots come last, as (0, 0).
+ * Rects and bands of a box-filtered frame touch disjoint pixels, so several calls into one set of buffers give the whole frame's table; a wide
+ * filter's splats across a border continue the neighbour's table, which is exact where nothing overflows. Every call reads, ranks and writes
+ * the whole W*H*K table whatever the rect (pixels it does not touch are only re-ranked; a host table is staged in and out in full), so a frame
+ * cut into n calls pays n times the film's table on top of its samples: prefer few, large calls. The handle is left as it was (a frame
+ * rendered before and after is the same frame).
+ * Errors, each with its own message: RRT_EINVAL before any device work for a NULL out, ids, coverage, weight, rect or handle, n_slots outside
+ * 1 .. RRT_MAX_MATTE_SLOTS and a bad mem; RRT_EINVAL for n_prim_id != n_prims when prim_id is not NULL, a precision that is not the handle's, a
+ * rect outside the film, bad rank / world, a frame in flight; otherwise what rrt_render_aov gives for the scene.
+ * Not provided: ids through mirrors and glass (a _follow form), a fused form inside rrt_render_frame_aov, _begin / _end, an adaptive form. */
+#define RRT_MAX_MATTE_SLOTS 16
+typedef struct rrt_mattes {
+  int32_t mem;        /* RRT_MEM_* of the three arrays                          */
+  int32_t precision;  /* must equal the handle's                                */
+  int32_t n_slots;    /* K, 1 .. RRT_MAX_MATTE_SLOTS                            */
+  int32_t pad;
+  uint32_t* ids;      /* W*H*K  : [pixel][slot]                                 */
+  void* coverage;     /* W*H*K  : [pixel][slot], handle precision               */
+  void* weight;       /* W*H*4  : sum fw over live samples | over hit samples | overflow | 0 */
+} rrt_mattes;
+int rrt_render_mattes(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples,
+                      const uint32_t* prim_id /* n_prim_id entries, indexed like rrt_scene_desc.prims; NULL: material index + 1 */,
+                      size_t n_prim_id, rrt_mattes* out);
+
+/* One matte from a table (no counterpart in the reference): alpha[p] = (sum of coverage[p][k] over the slots whose id is in ids[]) / weight[p][0],
+ * and 0 where weight[p][0] == 0 - the share of the pixel's live filter weight that the listed ids cover. ids may name absent ids and repeat ids.
+ * The arithmetic is in double, rounded once to the handle's precision; it runs on the device for both memory kinds (host arrays are staged).
+ * alpha is W*H values of the handle's precision in m->mem, overwritten. On a table without overflow the alphas of a partition of the ids and
+ * the miss share 1 - weight[1] / weight[0] sum to 1. The handle is left as it was. Errors, each with its own message: RRT_EINVAL before any
+ * device work for a NULL m, ids, coverage, weight, id list, alpha or handle, n_slots outside 1 .. RRT_MAX_MATTE_SLOTS, a bad mem and n_ids
+ * outside 1 .. 256; RRT_EINVAL for a precision that is not the handle's or a frame in flight. */
+int rrt_matte_extract(rrt_handle*, const rrt_mattes* m, const uint32_t* ids, int n_ids /* 1 .. 256 */, void* alpha /* W*H, handle precision, in m->mem */);
+
 /* ---- multi-GPU film reassembly: RCCL over xGMI, one collective per frame ----
  * The reference has one address space: its rayon tiles merge under a lock (Film::merge_film_tile film.rs:248-263, driven from
  * integrator/mod.rs:64-74,133). Across GPUs every rank renders its bands (rrt_render_bands / _begin) into its own device

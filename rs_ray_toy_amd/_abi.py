@@ -174,6 +174,14 @@ class Pass(C.Structure):
     _fields_ = [("groups", C.c_uint32), ("bounce_lo", C.c_int32), ("bounce_hi", C.c_int32), ("film_xyzw", C.c_void_p)]
 
 
+RRT_MAX_MATTE_SLOTS = 16
+
+
+class Mattes(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32), ("n_slots", C.c_int32), ("pad", C.c_int32), ("ids", C.c_void_p),
+                ("coverage", C.c_void_p), ("weight", C.c_void_p)]
+
+
 # every symbol include/rrt.h declares (tests/test_abi.py checks the library exports all of them)
 PROTOTYPES = {
     "rrt_scene_load": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -213,6 +221,8 @@ PROTOTYPES = {
     "rrt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.POINTER(Pass), C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_combine_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int]),
+    "rrt_render_mattes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(Mattes)]),
+    "rrt_matte_extract": (C.c_int, [C.c_void_p, C.POINTER(Mattes), C.c_void_p, C.c_int, C.c_void_p]),
     "rrt_band_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "rrt_comm_id": (C.c_int, [C.c_void_p]),
     "rrt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

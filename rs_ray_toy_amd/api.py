@@ -72,6 +72,29 @@ class Scene:
     def resolution(self):
         return self.desc.film.xres, self.desc.film.yres
 
+    def prim_ids(self, by="object"):
+        """One uint32 id per entry of rrt_scene_desc.prims, for Renderer.render_mattes: "material" = material index + 1; "instance" =
+        rrt_prim.instance + 2 (uninstanced primitives get 1); "object" = 1 + the dense index of the distinct (instance, material) pairs in
+        ascending order; "prim" = index + 1."""
+        d = self.desc
+        n = int(d.n_prims)
+        if n == 0:
+            return np.zeros(0, np.uint32)
+        prims = np.frombuffer((A.Prim * n).from_address(C.addressof(d.prims.contents)), dtype=np.dtype(A.Prim))     # a view of the scene's own records
+        inst, mat = prims["instance"].astype(np.int64), prims["material"].astype(np.int64)
+        if by == "material":
+            ids = mat + 1
+        elif by == "instance":
+            ids = inst + 2
+        elif by == "object":
+            _, dense = np.unique(np.stack([inst, mat], -1), axis=0, return_inverse=True)
+            ids = dense.reshape(-1) + 1
+        elif by == "prim":
+            ids = np.arange(n, dtype=np.int64) + 1
+        else:
+            raise ValueError(f'prim_ids: by is "material", "instance", "object" or "prim", not {by!r}')
+        return np.ascontiguousarray(ids, np.uint32)
+
     def __del__(self):
         try:
             if self._h:
@@ -318,6 +341,62 @@ class Renderer:
         ptrs = (C.c_void_p * max(1, len(film_ptrs)))(*film_ptrs)
         _check(A.lib().rrt_combine_passes(self._h, ptrs, g.ctypes.data_as(C.POINTER(C.c_double)), len(film_ptrs), out_ptr, A.RRT_MEM_DEVICE))
 
+    # rrt_render_mattes: per pixel the K best-covered ids of the camera rays' first hits; resolve_mattes() divides the coverages out
+    def _prim_id_arg(self, ids):
+        """None (material index + 1), a Scene.prim_ids key, or one id per entry of rrt_scene_desc.prims -> (array kept alive, pointer, count)"""
+        if ids is None:
+            return None, None, 0
+        arr = self.scene.prim_ids(ids) if isinstance(ids, str) else np.ascontiguousarray(ids, np.uint32)
+        return arr, arr.ctypes.data, arr.size
+
+    def render_mattes(self, ids=None, slots=6, rect=None, rank=0, world=1, max_samples=0, mattes=None):
+        """-> dict(ids (H, W, K) uint32, coverage (H, W, K), weight (H, W, 4)): host arrays, the table ranked by coverage. mattes: such a dict,
+        continued in place (its K is the table's)."""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        if mattes is None:
+            mattes = dict(ids=np.zeros((H, W, slots), np.uint32), coverage=np.zeros((H, W, slots), self.dtype), weight=np.zeros((H, W, 4), self.dtype))
+        m = self._mattes_struct(mattes, "render_mattes")
+        arr, ptr, n = self._prim_id_arg(ids)
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_mattes(self._h, r, rank, world, max_samples, ptr, n, C.byref(m)))
+        return mattes
+
+    def _mattes_struct(self, mattes, who):
+        W, H = self.scene.resolution
+        i, c, w = mattes["ids"], mattes["coverage"], mattes["weight"]
+        K = i.shape[-1] if i.ndim == 3 else 0
+        ok = (i.dtype == np.uint32 and i.shape == (H, W, K) and c.dtype == self.dtype and c.shape == (H, W, K) and w.dtype == self.dtype and w.shape == (H, W, 4)
+              and i.flags.c_contiguous and c.flags.c_contiguous and w.flags.c_contiguous)
+        if not ok:
+            raise ValueError(f"{who}: ids (H, W, K) uint32, coverage (H, W, K) and weight (H, W, 4) of the handle's precision, all C-contiguous")
+        return A.Mattes(A.RRT_MEM_HOST, self.precision, K, 0, i.ctypes.data, c.ctypes.data, w.ctypes.data)
+
+    def render_mattes_device(self, rect, ids_ptr, coverage_ptr, weight_ptr, slots, ids=None, rank=0, world=1, max_samples=0):
+        """The same on device buffers (raw pointers of the W*H*slots ids, W*H*slots coverages and W*H*4 weights), continued in place."""
+        m = A.Mattes(A.RRT_MEM_DEVICE, self.precision, slots, 0, ids_ptr, coverage_ptr, weight_ptr)
+        arr, ptr, n = self._prim_id_arg(ids)
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_mattes(self._h, r, rank, world, max_samples, ptr, n, C.byref(m)))
+
+    # rrt_matte_extract: alpha = the coverage of the listed ids / the live weight
+    def matte_extract(self, mattes, ids, out=None):
+        """mattes: the dict of render_mattes; ids: 1 .. 256 ids -> (H, W) alpha of the handle's precision"""
+        W, H = self.scene.resolution
+        m = self._mattes_struct(mattes, "matte_extract")
+        lst = np.ascontiguousarray(np.atleast_1d(ids), np.uint32)
+        if out is None:
+            out = np.empty((H, W), self.dtype)
+        if out.dtype != self.dtype or out.shape != (H, W) or not out.flags.c_contiguous:
+            raise ValueError("matte_extract: out is a C-contiguous (H, W) array of the handle's precision")
+        _check(A.lib().rrt_matte_extract(self._h, C.byref(m), lst.ctypes.data, lst.size, out.ctypes.data))
+        return out
+
+    def matte_extract_device(self, ids_ptr, coverage_ptr, weight_ptr, slots, ids, out_ptr):
+        m = A.Mattes(A.RRT_MEM_DEVICE, self.precision, slots, 0, ids_ptr, coverage_ptr, weight_ptr)
+        lst = np.ascontiguousarray(np.atleast_1d(ids), np.uint32)
+        _check(A.lib().rrt_matte_extract(self._h, C.byref(m), lst.ctypes.data, lst.size, out_ptr))
+
     # rrt_render_frame_aov: the frame of render_moments() and the planes of render_aov() from one camera pass - every input of denoise(..., moments=)
     def render_frame_aov(self, rect=None, rank=0, world=1, max_samples=0, film=None, moments=True, planes=("albedo", "normal", "depth"), stats=False):
         """-> (film, moments_or_None, aov_dict[, stats]): film and moments as render_moments gives them (moments: True = a new plane, False / None =
@@ -547,6 +626,33 @@ def write_aov_pngs(prefix, aov):
         write_png(f"{prefix}_{name}.png", rgba)
 
 
+def resolve_mattes(m):
+    """The table of Renderer.render_mattes -> (H, W, K) float64 shares coverage / weight[..., 0] (0 where no live sample covers the pixel)."""
+    cov, w0 = np.asarray(m["coverage"], np.float64), np.asarray(m["weight"], np.float64)[..., 0]
+    live = w0 != 0
+    return np.where(live[..., None], cov / np.where(live, w0, 1.0)[..., None], 0.0)
+
+
+def matte_colour(ids):
+    """(..., 3) float64: the three low bytes of id * 2654435761 (mod 2^32), each / 255 - the preview colour of an id"""
+    h = (np.asarray(ids).astype(np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    return np.stack([(h >> np.uint64(s)) & np.uint64(0xFF) for s in (0, 8, 16)], -1).astype(np.float64) / 255.0
+
+
+def write_matte_png(path, m):
+    """One preview image of a matte table: per pixel sum_k colour(id_k) * coverage_k / weight[0], the slots added in stored order, quantised as
+    write_aov_pngs quantises - what rrt_render writes under RRT_MATTES=<path.png>."""
+    share = resolve_mattes(m)
+    col = matte_colour(m["ids"])
+    rgb = np.zeros(share.shape[:2] + (3,))
+    for k in range(share.shape[2]):
+        rgb += col[:, :, k, :] * share[:, :, k, None]
+    rgba = np.empty(rgb.shape[:2] + (4,), np.uint8)
+    rgba[..., :3] = np.clip(np.nan_to_num(rgb) * 255.0 + 0.5, 0.0, 255.0).astype(np.uint8)
+    rgba[..., 3] = 255
+    write_png(path, rgba)
+
+
 def write_pass_pngs(prefix, renderer, n_lights, scale=1.0):
     """<prefix>_direct.png (path vertex 0), <prefix>_indirect.png (vertices >= 1) and <prefix>_light<i>.png for the first 14 lights, from one
     Renderer.render_passes call - what rrt_render writes under RRT_PASSES=<prefix>."""
@@ -607,6 +713,11 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
         write_aov_pngs(os.environ["RRT_AOV"], r.render_aov(follow=follow))
     if os.environ.get("RRT_PASSES"):   # as rrt_render: direct, indirect and one PNG per light (the first 14) after the frame
         write_pass_pngs(os.environ["RRT_PASSES"], r, scene.desc.n_lights, scene.desc.film.scale)
+    if os.environ.get("RRT_MATTES"):   # as rrt_render: one preview image of the ID mattes after the frame
+        by = os.environ.get("RRT_MATTE_BY") or "object"
+        if by not in ("material", "instance", "object"):
+            raise ValueError("RRT_MATTE_BY must be material, instance or object")
+        write_matte_png(os.environ["RRT_MATTES"], r.render_mattes(ids=by, slots=int(os.environ.get("RRT_MATTE_SLOTS") or 6)))
     if os.environ.get("RRT_DENOISE"):   # as rrt_render: the filtered frame, guided by the planes of at most 32 samples per pixel
         write_png(os.environ["RRT_DENOISE"], resolve_rgba8(r.denoise(film, aov if aov is not None else r.render_aov(max_samples=32, follow=follow), moments=moments), scene.desc.film.scale))
     r.close()

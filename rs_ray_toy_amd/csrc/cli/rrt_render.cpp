@@ -19,6 +19,9 @@
 // first non-specular surface behind mirrors and smooth glass. With RRT_DENOISE_MOMENTS that is rrt_render_moments followed by that call.
 // RRT_PASSES = <prefix> writes light-group and bounce passes after the frame (rrt_render_passes, on device 0 alone): <prefix>_direct.png (path vertex 0),
 // <prefix>_indirect.png (vertices >= 1) and <prefix>_light<i>.png for the first 14 lights, each light its own group; Path integrator only.
+// RRT_MATTES = <path.png> writes one preview image of the ID mattes after the frame (rrt_render_mattes, on device 0 alone): per pixel the ids' hash
+// colours weighted by their coverage shares; RRT_MATTE_BY = material | instance | object (default) chooses the ids, RRT_MATTE_SLOTS (default 6) the
+// slots per pixel.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -90,6 +93,52 @@ int write_passes(rrt_handle* h, int precision, int W, int H, double scale, size_
     if (rc == RRT_OK) rc = rrt_write_png((prefix + names[k]).c_str(), rgba.data(), W, H);
   }
   return rc;
+}
+
+// one id per primitive, as Scene.prim_ids of the Python layer numbers them: "material" = material + 1, "instance" = instance + 2, "object" = 1 + the
+// dense index of the distinct (instance, material) pairs in ascending order. False = an unknown key.
+bool matte_prim_ids(const rrt_scene_desc* d, const std::string& by, std::vector<uint32_t>& ids) {
+  ids.resize(d->n_prims);
+  if (by == "material") { for (size_t i = 0; i < d->n_prims; i++) ids[i] = d->prims[i].material + 1u; return true; }
+  if (by == "instance") { for (size_t i = 0; i < d->n_prims; i++) ids[i] = (uint32_t)(d->prims[i].instance + 2); return true; }
+  if (by != "object") return false;
+  std::vector<std::pair<int64_t, int64_t>> pairs(d->n_prims);
+  for (size_t i = 0; i < d->n_prims; i++) pairs[i] = {(int64_t)d->prims[i].instance, (int64_t)d->prims[i].material};
+  std::vector<std::pair<int64_t, int64_t>> uniq(pairs);
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  for (size_t i = 0; i < d->n_prims; i++) ids[i] = 1u + (uint32_t)(std::lower_bound(uniq.begin(), uniq.end(), pairs[i]) - uniq.begin());
+  return true;
+}
+
+// the table of rrt_render_mattes -> one 8-bit preview: per pixel sum_k colour(id_k) * coverage_k / weight[0], the slots added in stored order;
+// colour(id) = the three low bytes of id * 2654435761 (mod 2^32), each / 255 (write_matte_png of the Python layer, operation by operation)
+template <typename R>
+int write_mattes(rrt_handle* h, int precision, int W, int H, const std::vector<uint32_t>& prim_id, int slots, const char* path) {
+  const size_t npx = (size_t)W * (size_t)H, K = (size_t)slots;
+  std::vector<uint32_t> ids(npx * K, 0u);
+  std::vector<R> cov(npx * K, R(0)), wgt(4 * npx, R(0));
+  rrt_mattes m{RRT_MEM_HOST, precision, slots, 0, ids.data(), cov.data(), wgt.data()};
+  const int32_t rect[4] = {0, 0, W, H};
+  int rc = rrt_render_mattes(h, rect, 0, 1, 0, prim_id.data(), prim_id.size(), &m);
+  if (rc != RRT_OK) return rc;
+  auto q = [](double v) { return (uint8_t)std::min(255.0, std::max(0.0, (v == v ? v : 0.0) * 255.0 + 0.5)); };
+  std::vector<uint8_t> img(4 * npx, 255);
+  for (size_t i = 0; i < npx; i++) {
+    const double w0 = (double)wgt[4 * i];
+    double rgb[3] = {0.0, 0.0, 0.0};
+    for (size_t k = 0; k < K; k++) {
+      const double share = w0 != 0.0 ? (double)cov[i * K + k] / w0 : 0.0;
+      const uint32_t hash = ids[i * K + k] * 2654435761u;
+      for (int c = 0; c < 3; c++) {
+        const double colour = (double)((hash >> (8 * c)) & 0xffu) / 255.0;
+        const double term = colour * share;   // (a statement of its own: a product that is rounded before it is added, as numpy rounds it)
+        rgb[c] += term;
+      }
+    }
+    for (int c = 0; c < 3; c++) img[4 * i + c] = q(rgb[c]);
+  }
+  return rrt_write_png(path, img.data(), W, H);
 }
 
 // the gathered film, filtered by rrt_denoise under the planes of at most 32 samples per pixel -> one 8-bit image. planes_dev: the three planes as
@@ -278,6 +327,22 @@ int main(int argc, char** argv) {
     rc = precision == RRT_F32 ? write_passes<float>(handles[0], precision, W, H, film_scale, desc->n_lights, env_ps)
                               : write_passes<double>(handles[0], precision, W, H, film_scale, desc->n_lights, env_ps);
     if (rc != RRT_OK) { const int e = fail("rrt_render_passes", rc); cleanup(); return e; }
+  }
+  if (const char* env_mt = std::getenv("RRT_MATTES"); env_mt && *env_mt) {
+    if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_MATTES runs on one GPU: the ID mattes are rendered on device 0 alone\n");
+    const char* env_by = std::getenv("RRT_MATTE_BY");
+    const char* env_slots = std::getenv("RRT_MATTE_SLOTS");
+    std::vector<uint32_t> prim_id;
+    char* end = nullptr;
+    const long slots = (env_slots && *env_slots) ? std::strtol(env_slots, &end, 10) : 6;
+    if (!matte_prim_ids(desc, (env_by && *env_by) ? env_by : "object", prim_id) || (end && *end != '\0') || slots < 1 || slots > RRT_MAX_MATTE_SLOTS) {
+      std::fprintf(stderr, "rrt_render: RRT_MATTE_BY must be material, instance or object, RRT_MATTE_SLOTS a number (1..16)\n");
+      cleanup();
+      return 2;
+    }
+    const int k = (int)slots;
+    rc = precision == RRT_F32 ? write_mattes<float>(handles[0], precision, W, H, prim_id, k, env_mt) : write_mattes<double>(handles[0], precision, W, H, prim_id, k, env_mt);
+    if (rc != RRT_OK) { const int e = fail("rrt_render_mattes", rc); cleanup(); return e; }
   }
   if (const char* env_dn = env_dn_path; env_dn && *env_dn) {
     std::vector<unsigned char> host_moments;

@@ -2224,4 +2224,191 @@ static __global__ void __launch_bounds__(kSelBlock) k_tile_select(const uint32_t
   if (tid == 0u) *count_out = base;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// ID mattes (rrt_render_mattes / rrt_matte_extract, include/rrt.h): per pixel a table of K (id, coverage) slots and a weight record. A pass of
+// its own beside the k_aov_* family - camera kernels, closest-hit launch, k_matte_ids, k_matte_box / k_matte_wide - around an internal table that
+// lives across the pool passes of a call: k_matte_load copies the caller's table in before the first pass, k_matte_rank sorts it out after the last.
+// The internal table is slot-major (ids[k * npix + pix], cov[k * npix + pix]: a wave's loads of one slot are consecutive); the caller's is
+// [pixel][slot]. Nothing is ever evicted: a stored coverage is then the id's complete sum, and the overflow channel says how much is missing.
+// ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kMaxMatteSlots = 16;   // RRT_MAX_MATTE_SLOTS
+template <typename R>
+struct MatteTab {
+  uint32_t* ids;                        // [slot][film pixel]
+  R* cov;                               // [slot][film pixel]; 0 = the slot is empty
+  typename Vec4T<R>::type* weight;      // [film pixel]: sum fw over live samples | over hit samples | overflow | 0
+  uint32_t K;
+  size_t npix;                          // W x H
+};
+
+// One thread per entry of the camera queue, as k_aov_shade reads it, but only the primitive index of the hit record is looked at: no surface, no
+// texture. An 8-byte record per slot: {hit flag, id}. Every live sample of the pass is in the queue (no root cull), so every live slot gets a record.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_matte_ids(Pools<R> p, const uint32_t* id_dev, uint32_t n_ids, uint2* rec) {
+  const uint32_t n = p.counters[C_ACTIVE];
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t slot = p.q_active[i].slot;
+    const int prim = (int)real_to_bits(p.hit[i].y);
+    rec[slot] = prim < 0 ? make_uint2(0u, 0u) : make_uint2(1u, (uint32_t)prim < n_ids ? id_dev[prim] : 0u);
+  }
+}
+
+// A thread's K slots in LDS, slot-major over the workgroup (word k * kBlock + tid: consecutive lanes in consecutive banks): a per-thread array
+// indexed by a runtime slot number would live in scratch. K * kBlock ids, then K * kBlock coverages; a thread touches its own column only.
+template <typename R>
+struct MatteLds { uint32_t* id; R* cov; };
+template <typename R>
+RRT_DEV MatteLds<R> matte_lds(uint32_t K) {
+  extern __shared__ uint32_t matte_smem[];
+  return {matte_smem + threadIdx.x, reinterpret_cast<R*>(matte_smem + K * kBlock) + threadIdx.x};
+}
+inline size_t matte_lds_bytes(uint32_t K, size_t real_bytes) { return (size_t)K * kBlock * (sizeof(uint32_t) + real_bytes); }
+template <typename R>
+RRT_DEV void matte_lds_load(const MatteTab<R>& tab, const MatteLds<R>& t, size_t pix) {
+  for (uint32_t k = 0; k < tab.K; k++) { t.id[k * kBlock] = tab.ids[k * tab.npix + pix]; t.cov[k * kBlock] = tab.cov[k * tab.npix + pix]; }
+}
+template <typename R>
+RRT_DEV void matte_lds_store(const MatteTab<R>& tab, const MatteLds<R>& t, size_t pix) {
+  for (uint32_t k = 0; k < tab.K; k++) { tab.ids[k * tab.npix + pix] = t.id[k * kBlock]; tab.cov[k * tab.npix + pix] = t.cov[k * kBlock]; }
+}
+// The table rule of rrt.h for one live sample with filter weight fw. `last`: the slot the previous hit sample went to, tried first (consecutive
+// samples of a pixel mostly share an id); it finds what the search would find, since a table holds an id once.
+template <typename R>
+RRT_DEV void matte_add(const MatteLds<R>& t, uint32_t K, uint32_t& last, typename Vec4T<R>::type& w, R fw, uint2 rec) {
+  if (fw == R(0)) return;
+  w.x += fw;
+  if (rec.x == 0u) return;   // a live sample that misses the scene
+  w.y += fw;
+  const uint32_t id = rec.y;
+  if (t.id[last * kBlock] == id && t.cov[last * kBlock] != R(0)) { t.cov[last * kBlock] += fw; return; }
+  uint32_t found = K, empty = K;
+  for (uint32_t k = 0; k < K; k++) {
+    if (t.cov[k * kBlock] != R(0)) { if (t.id[k * kBlock] == id) { found = k; break; } }
+    else if (empty == K) empty = k;
+  }
+  if (found < K) { t.cov[found * kBlock] += fw; last = found; }
+  else if (empty < K) { t.id[empty * kBlock] = id; t.cov[empty * kBlock] = fw; last = empty; }
+  else w.z += fw;   // overflow: K other ids hold the slots
+}
+
+// Gather form, as k_aov_box: one thread per pixel of the pass, its samples in sample order - the arrival order of the box filter.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_matte_box(SceneDev<R> s, Pools<R> p, PassDesc pd, MatteTab<R> tab, const uint2* rec) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  const size_t pix = (size_t)py_ * (size_t)s.xres + px_;
+  const MatteLds<R> t = matte_lds<R>(tab.K);
+  matte_lds_load(tab, t, pix);
+  typename Vec4T<R>::type w = tab.weight[pix];
+  uint32_t last = 0;
+  for (uint32_t sl = 0; sl < pd.ns; sl++) {
+    const uint32_t slot = sl * pd.npix + pl;
+    if (!(p.weight[slot] > R(0))) continue;   // dead sample
+    matte_add(t, tab.K, last, w, R(1), rec[slot]);   // box filter table weight 1
+  }
+  matte_lds_store(tab, t, pix);
+  tab.weight[pix] = w;
+}
+
+// Gather form, as k_aov_wide: one thread per film pixel within reach of the pass, the samples of every pass pixel within reach, the film's own
+// footprint test and table look-up (film_wide_weight).
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_matte_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, MatteTab<R> tab, const uint2* rec,
+                                                        int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+  const uint32_t tt = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tt >= (uint32_t)ew * (uint32_t)eh) return;
+  const int x = ex0 + (int)(tt % (uint32_t)ew), y = ey0 + (int)(tt / (uint32_t)ew);
+  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x;
+  const MatteLds<R> t = matte_lds<R>(tab.K);
+  matte_lds_load(tab, t, pix);
+  typename Vec4T<R>::type w = tab.weight[pix];
+  uint32_t last = 0;
+  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
+    if (sy < 0 || sy >= ymax) continue;
+    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+      uint32_t pl;
+      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
+      for (uint32_t sl = 0; sl < pd.ns; sl++) {
+        const uint32_t slot = sl * pd.npix + pl;
+        if (!(p.weight[slot] > R(0))) continue;
+        const typename Vec4T<R>::type cs = p.samp[slot];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
+        matte_add(t, tab.K, last, w, fw, rec[slot]);
+      }
+    }
+  }
+  matte_lds_store(tab, t, pix);
+  tab.weight[pix] = w;
+}
+
+// the caller's [pixel][slot] table into the internal slot-major one: one thread per (pixel, slot), reads consecutive
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_matte_load(const uint32_t* ids, const R* cov, MatteTab<R> tab) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= tab.npix * tab.K) return;
+  const size_t pix = e / tab.K, k = e % tab.K;
+  tab.ids[k * tab.npix + pix] = ids[e];
+  tab.cov[k * tab.npix + pix] = cov[e];
+}
+
+// Rank on the way out: one thread per pixel sorts its K slots (insertion sort in its LDS column, K <= 16) by coverage descending, ties by
+// ascending id, empty slots last as (0, 0), and writes them in the caller's [pixel][slot] layout.
+template <typename R>
+RRT_DEV bool matte_before(uint32_t ia, R ca, uint32_t ib, R cb) {
+  if (ca == R(0)) return false;
+  if (cb == R(0)) return true;
+  return ca > cb || (ca == cb && ia < ib);
+}
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_matte_rank(MatteTab<R> tab, uint32_t* ids, R* cov) {
+  const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= tab.npix) return;
+  const MatteLds<R> t = matte_lds<R>(tab.K);
+  matte_lds_load(tab, t, pix);
+  for (uint32_t i = 1; i < tab.K; i++) {
+    const uint32_t ci = t.id[i * kBlock];
+    const R cc = t.cov[i * kBlock];
+    uint32_t j = i;
+    while (j > 0 && matte_before<R>(ci, cc, t.id[(j - 1) * kBlock], t.cov[(j - 1) * kBlock])) {
+      t.id[j * kBlock] = t.id[(j - 1) * kBlock]; t.cov[j * kBlock] = t.cov[(j - 1) * kBlock];
+      j--;
+    }
+    t.id[j * kBlock] = ci; t.cov[j * kBlock] = cc;
+  }
+  for (uint32_t k = 0; k < tab.K; k++) {
+    const R c = t.cov[k * kBlock];
+    ids[pix * tab.K + k] = c != R(0) ? t.id[k * kBlock] : 0u;
+    cov[pix * tab.K + k] = c;
+  }
+}
+
+// rrt_matte_extract: one thread per pixel over a table in the caller's layout; `list` is the wanted ids, sorted and without duplicates (binary
+// search). The sum and the division are in double, rounded once.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_matte_extract(const uint32_t* ids, const R* cov, const typename Vec4T<R>::type* weight, uint32_t K,
+                                                           const uint32_t* list, int n_list, R* alpha, size_t npix) {
+  const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= npix) return;
+  const double w0 = (double)weight[pix].x;
+  double sum = 0.0;
+  for (uint32_t k = 0; k < K; k++) {
+    const R c = cov[pix * K + k];
+    if (c == R(0)) continue;
+    const uint32_t id = ids[pix * K + k];
+    int lo = 0, hi = n_list - 1;
+    bool in = false;
+    while (lo <= hi) {
+      const int mid = (lo + hi) >> 1;
+      const uint32_t v = list[mid];
+      if (v == id) { in = true; break; }
+      if (v < id) lo = mid + 1; else hi = mid - 1;
+    }
+    if (in) sum += (double)c;
+  }
+  alpha[pix] = w0 != 0.0 ? (R)(sum / w0) : R(0);
+}
+
 }  // namespace rrtd

@@ -258,6 +258,37 @@ int rrt_combine_passes(rrt_handle* h, const void* const* films, const double* ga
   return guarded([&]() { h->impl->combine_passes(films, gains_rgb, n, film_out, mem); });
 }
 
+namespace {
+// the caller's own table description, wrong whichever handle it comes with: every check before any device work, each with its own message
+int mattes_desc_check(const std::string& name, const rrt_mattes* m) {
+  auto bad = [&](const char* what) { rrt::set_last_error(name + ": " + what); return (int)RRT_EINVAL; };
+  static_assert(RRT_MAX_MATTE_SLOTS == rrtd::kMaxMatteSlots, "the slot tile of the matte kernels is sized for RRT_MAX_MATTE_SLOTS");
+  if (!m) return bad("null table description (rrt_mattes)");
+  if (!m->ids) return bad("null ids array");
+  if (!m->coverage) return bad("null coverage array");
+  if (!m->weight) return bad("null weight array");
+  if (m->n_slots < 1 || m->n_slots > RRT_MAX_MATTE_SLOTS) return bad("n_slots must be 1 .. 16 (RRT_MAX_MATTE_SLOTS)");
+  if (m->mem != RRT_MEM_HOST && m->mem != RRT_MEM_DEVICE) return bad("bad mem");
+  return RRT_OK;
+}
+}  // namespace
+
+int rrt_render_mattes(rrt_handle* h, const int32_t rect[4], int rank, int world, uint64_t max_samples, const uint32_t* prim_id, size_t n_prim_id, rrt_mattes* out) {
+  if (const int rc = mattes_desc_check("rrt_render_mattes", out); rc != RRT_OK) return rc;
+  if (!rect) { rrt::set_last_error("rrt_render_mattes: null rect"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_render_mattes: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_mattes(rect, rank, world, max_samples, prim_id, n_prim_id, out); });
+}
+
+int rrt_matte_extract(rrt_handle* h, const rrt_mattes* m, const uint32_t* ids, int n_ids, void* alpha) {
+  if (const int rc = mattes_desc_check("rrt_matte_extract", m); rc != RRT_OK) return rc;
+  if (!ids) { rrt::set_last_error("rrt_matte_extract: null id list"); return RRT_EINVAL; }
+  if (n_ids < 1 || n_ids > 256) { rrt::set_last_error("rrt_matte_extract: n_ids must be 1 .. 256"); return RRT_EINVAL; }
+  if (!alpha) { rrt::set_last_error("rrt_matte_extract: null alpha"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_matte_extract: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->matte_extract(m, ids, n_ids, alpha); });
+}
+
 int rrt_set_option(rrt_handle* h, const char* key, double value) {
   if (!h || !key) { rrt::set_last_error("rrt_set_option: null argument"); return RRT_EINVAL; }
   return guarded([&]() { h->impl->set_option(key, value); });

@@ -55,6 +55,8 @@ struct HandleBase {
   virtual void render_passes(const int32_t rect[4], int rank, int world, const uint8_t* light_group, const rrt_pass* passes, int n_passes, void* film, int mem, rrt_render_stats* stats) = 0;   // film may be NULL
   virtual void combine_passes(const void* const* films, const double* gains_rgb, int n, void* film_out, int mem) = 0;
   virtual void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) = 0;   // moments may be NULL (rrt_denoise)
+  virtual void render_mattes(const int32_t rect[4], int rank, int world, uint64_t max_samples, const uint32_t* prim_id, size_t n_prim_id, const rrt_mattes* out) = 0;   // prim_id may be NULL
+  virtual void matte_extract(const rrt_mattes* m, const uint32_t* ids, int n_ids, void* alpha) = 0;
   virtual void set_option(const std::string& key, double v) = 0;
   // rrt_film_gather (rrt_comm.hip): events on the handle's stream around the frame's collective, so that the frame's statistics can tell
   // the collective (rrt_render_stats::ms_gather) from the render (ms_total) - what a multi-GPU scaling run needs to separate imbalance from xGMI time
@@ -973,6 +975,149 @@ class Handle : public HandleBase {
     aov_merge_out(out);   // into the caller's planes (+=)
     check_device_errors();
   }
+  // ---- ID mattes (rrt_render_mattes): render_aov's pass loop with k_matte_ids in k_aov_shade's place and a (id, coverage) table in the planes' ----------
+  // Per call: the ids of the entries of prim_order are built on the host and uploaded (they are the caller's, not the scene's: nothing of the scene
+  // preparation knows them), the caller's table is copied into the internal slot-major one (k_matte_load; a host table is staged), the passes insert
+  // into it (k_matte_box / k_matte_wide), k_matte_rank sorts it out. What render_aov puts back per pass is put back here. Load, rank and the
+  // staging of a host table run over the whole W x H x K table whatever the rect: a frame cut into n calls moves the table n times.
+  void render_mattes(const int32_t rect[4], int rank, int world, uint64_t max_samples, const uint32_t* prim_id, size_t n_prim_id, const rrt_mattes* out) override {
+    if (pending_) throw std::invalid_argument("render_mattes: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (prim_id && n_prim_id != desc_.n_prims)
+      throw std::invalid_argument("render_mattes: n_prim_id = " + std::to_string(n_prim_id) + ", the scene has " + std::to_string(desc_.n_prims) + " primitives (one id per entry of rrt_scene_desc.prims)");
+    if (out->precision != precision()) throw std::invalid_argument("render_mattes: table precision must match the handle");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_mattes: bad rank/world");
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    const rrt_film& f = desc_.film;
+    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
+    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
+      throw std::invalid_argument("render_mattes: rect outside the film");
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30, n_ranks = (uint32_t)world;
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
+    const size_t W = (size_t)f.xres, H = (size_t)f.yres, NP = W * H;
+    const uint32_t K = (uint32_t)out->n_slots;
+    size_t rh = (size_t)(rect[3] - rect[1]);
+    if (n_ranks > 1) {   // rows of this rank's bands
+      size_t rows = 0;
+      for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == (uint32_t)rank) rows++;
+      rh = rows;
+    }
+    const size_t rw = (size_t)(rect[2] - rect[0]), rpix = rw * rh;
+    uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
+    if (max_samples != 0) s_total = std::min<uint64_t>(s_total, max_samples);
+    using V4 = typename Vec4T<R>::type;
+    struct Restore {   // what launch_raygen sets for the pass it last ran for
+      Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6];
+      ~Restore() { h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k]; }
+    } restore{this, tt_pass_ok_, film_runs_ok_, scene_.root_cull, {scene_.root_box[0], scene_.root_box[1], scene_.root_box[2], scene_.root_box[3], scene_.root_box[4], scene_.root_box[5]}};
+
+    // the id of every entry of prim_order
+    const size_t n_ord = matte_order_.size();
+    const std::vector<uint32_t>* id_host = &matte_mat_;
+    if (prim_id) {
+      matte_id_host_.resize(n_ord);
+      for (size_t i = 0; i < n_ord; i++) matte_id_host_[i] = prim_id[matte_order_[i]];
+      id_host = &matte_id_host_;
+    }
+    if (matte_id_dev_.n != n_ord) matte_id_dev_.alloc(n_ord);
+    if (n_ord) HIP_CHECK(hipMemcpyAsync(matte_id_dev_.p, id_host->data(), n_ord * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+    // the caller's table in
+    if (matte_ids_.n != NP * K) { matte_ids_.alloc(NP * K); matte_cov_.alloc(NP * K); }
+    if (matte_w_.n != NP) matte_w_.alloc(NP);
+    const MatteTab<R> tab{matte_ids_.p, matte_cov_.p, matte_w_.p, K, NP};
+    const bool host = out->mem == RRT_MEM_HOST;
+    const uint32_t* user_ids = out->ids;
+    const R* user_cov = (const R*)out->coverage;
+    if (host) {
+      if (matte_stage_ids_.n != NP * K) { matte_stage_ids_.alloc(NP * K); matte_stage_cov_.alloc(NP * K); }
+      HIP_CHECK(hipMemcpyAsync(matte_stage_ids_.p, out->ids, NP * K * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+      HIP_CHECK(hipMemcpyAsync(matte_stage_cov_.p, out->coverage, NP * K * sizeof(R), hipMemcpyHostToDevice, st_));
+      user_ids = matte_stage_ids_.p; user_cov = matte_stage_cov_.p;
+    }
+    HIP_CHECK(hipMemcpyAsync(matte_w_.p, out->weight, NP * sizeof(V4), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st_));
+    const uint32_t tab_grid = (uint32_t)((NP * K + kBlock - 1) / kBlock), pix_grid = (uint32_t)((NP + kBlock - 1) / kBlock);
+    const size_t lds = matte_lds_bytes(K, sizeof(R));
+    hipLaunchKernelGGL((k_matte_load<R>), dim3(tab_grid), dim3(kBlock), 0, st_, user_ids, user_cov, tab);
+    HIP_CHECK(hipGetLastError());
+
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));   // also where no pass runs: check_device_errors below reads them
+    if (rpix > 0 && s_total > 0) {
+      ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+      if (matte_rec_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); matte_rec_.alloc(cap_); }
+      const size_t group = std::min(rpix, cap_);                     // pixels per group
+      const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
+      for (size_t g0 = 0; g0 < rpix; g0 += group) {
+        const size_t npix = std::min(group, rpix - g0);
+        for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
+          const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
+          const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
+          PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, (uint32_t)rank, tiled};
+          const size_t nslots = npix * (size_t)ns;
+          const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+          launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
+          launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
+          const dim3 sg(std::min(grid, 16384u));
+          hipLaunchKernelGGL((k_matte_ids<R>), sg, dim3(kBlock), 0, st_, pool_, (const uint32_t*)matte_id_dev_.p, (uint32_t)n_ord, matte_rec_.p);
+          if (!wide_filter) hipLaunchKernelGGL((k_matte_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p);
+          else {
+            // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as render_aov)
+            const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+            const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+            const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+            const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
+            hipLaunchKernelGGL((k_matte_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p,
+                               ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+          }
+          HIP_CHECK(hipGetLastError());
+        }
+      }
+    }
+    // ranked, into the caller's table
+    hipLaunchKernelGGL((k_matte_rank<R>), dim3(pix_grid), dim3(kBlock), lds, st_, tab, host ? matte_stage_ids_.p : out->ids, host ? matte_stage_cov_.p : (R*)out->coverage);
+    HIP_CHECK(hipGetLastError());
+    if (host) {
+      HIP_CHECK(hipMemcpyAsync(out->ids, matte_stage_ids_.p, NP * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipMemcpyAsync(out->coverage, matte_stage_cov_.p, NP * K * sizeof(R), hipMemcpyDeviceToHost, st_));
+    }
+    HIP_CHECK(hipMemcpyAsync(out->weight, matte_w_.p, NP * sizeof(V4), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    check_device_errors();
+  }
+  // rrt_matte_extract: one kernel over the pixels; a table in host memory is staged through the buffers render_mattes stages through
+  void matte_extract(const rrt_mattes* m, const uint32_t* ids, int n_ids, void* alpha) override {
+    if (pending_) throw std::invalid_argument("matte_extract: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (m->precision != precision()) throw std::invalid_argument("matte_extract: table precision must match the handle");
+    HIP_CHECK(hipSetDevice(dev_));
+    using V4 = typename Vec4T<R>::type;
+    const size_t NP = (size_t)desc_.film.xres * (size_t)desc_.film.yres;
+    const uint32_t K = (uint32_t)m->n_slots;
+    if (NP == 0) return;
+    std::vector<uint32_t> list(ids, ids + n_ids);
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    if (matte_list_.n < list.size()) matte_list_.alloc(256);
+    HIP_CHECK(hipMemcpyAsync(matte_list_.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+    const bool host = m->mem == RRT_MEM_HOST;
+    const uint32_t* t_ids = m->ids;
+    const R* t_cov = (const R*)m->coverage;
+    const V4* t_w = (const V4*)m->weight;
+    R* out = (R*)alpha;
+    if (host) {
+      if (matte_stage_ids_.n != NP * K) { matte_stage_ids_.alloc(NP * K); matte_stage_cov_.alloc(NP * K); }
+      if (matte_w_.n != NP) matte_w_.alloc(NP);
+      if (matte_alpha_.n != NP) matte_alpha_.alloc(NP);
+      HIP_CHECK(hipMemcpyAsync(matte_stage_ids_.p, m->ids, NP * K * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+      HIP_CHECK(hipMemcpyAsync(matte_stage_cov_.p, m->coverage, NP * K * sizeof(R), hipMemcpyHostToDevice, st_));
+      HIP_CHECK(hipMemcpyAsync(matte_w_.p, m->weight, NP * sizeof(V4), hipMemcpyHostToDevice, st_));
+      t_ids = matte_stage_ids_.p; t_cov = matte_stage_cov_.p; t_w = matte_w_.p; out = matte_alpha_.p;
+    }
+    hipLaunchKernelGGL((k_matte_extract<R>), dim3((uint32_t)((NP + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, t_ids, t_cov, t_w, K, (const uint32_t*)matte_list_.p, (int)list.size(), out, NP);
+    HIP_CHECK(hipGetLastError());
+    if (host) HIP_CHECK(hipMemcpyAsync(alpha, matte_alpha_.p, NP * sizeof(R), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+  }
   // ---- feature buffers through mirrors and glass (rrt_render_aov_follow): render_aov's pass loop with a level loop in place of k_aov_shade ------------
   // Per pass: camera kernels, closest hit over the camera queue (tile trees where a frame has built them), k_aov_shade for the first hits' records,
   // then per level k_aov_follow, the queue rotation and a closest-hit launch over the device-side count of followed entries - no host read-back between levels, launches sized by the
@@ -1277,6 +1422,13 @@ class Handle : public HandleBase {
   size_t pass_cap_ = 0;
   uint32_t passes_n_ = 0;
   uint64_t aov_prefix_ = 0;   // render_frame_aov: the leading samples whose first hits run_pass shades and gathers; 0 outside such a frame
+  // render_mattes (all allocated by the first call): the internal slot-major table and weight records, k_matte_ids' per-slot records (sized like
+  // pool.L), the per-call id of every entry of prim_order, the staging of a host-memory table, matte_extract's sorted id list and staged output
+  DevBuf<uint32_t> matte_ids_, matte_id_dev_, matte_stage_ids_, matte_list_;
+  DevBuf<R> matte_cov_, matte_stage_cov_, matte_alpha_;
+  DevBuf<typename Vec4T<R>::type> matte_w_;
+  DevBuf<uint2> matte_rec_;
+  std::vector<uint32_t> matte_order_, matte_mat_, matte_id_host_;
   uint32_t aov_serial_ = 0;   // k_aov_shade_frame's stamp of the pass last shaded: counted up per pass over the handle's life, never 0 in a record
 
   void check_renderable() {
@@ -1322,6 +1474,10 @@ class Handle : public HandleBase {
       const int mt = d->materials[d->prims[i].material].type;
       if (mt == RRT_MAT_MIRROR || mt == RRT_MAT_GLASS) has_specular_ = true;
     }
+    // render_mattes: the primitive behind each entry of prim_order and its material index + 1 (the ids of a NULL prim_id), kept on the host
+    matte_order_.assign(d->prim_order, d->prim_order + d->n_prim_order);
+    matte_mat_.resize(d->n_prim_order);
+    for (size_t i = 0; i < d->n_prim_order; i++) matte_mat_[i] = d->prims[d->prim_order[i]].material + 1u;
     shade_kinds_scene_ = fs.used.shade == ShadeClass::Lambert ? kKindsLambert : (fs.used.shade == ShadeClass::Glossy ? kKindsGlossy : kAllKinds);
     shade_kinds_ = shade_kinds_scene_;
     if (!fs.used.warning.empty()) warnings.push_back(fs.used.warning);
