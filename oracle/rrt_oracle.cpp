@@ -928,6 +928,17 @@ enum : uint8_t { BXDF_REFLECTION = 1, BXDF_TRANSMISSION = 2, BXDF_DIFFUSE = 4, B
 enum LobeKind { LAMBERT, OREN_NAYAR, MICROFACET, SPEC_REFL, DEBUG_DIFFUSE, DEBUG_SPECULAR, SPEC_TRANS, FRESNEL_SPEC, LAMBERT_TRANS, MICROFACET_TRANS };
 enum FresnelKind { FR_NOOP, FR_DIELECTRIC, FR_CONDUCTOR };
 
+// BSDF branch census (oracle_bsdf_census): which branch of the material and BxDF code below every call took, so that a test frame can be shown to
+// reach the branch it is for (tests/material_shapes.py). Relaxed atomic counters: they count and nothing else.
+enum BsdfCensus { BC_BUILT_0, BC_BUILT_1, BC_BUILT_2, BC_BUILT_4,
+                  BC_LOBE_FIRST, BC_LOBE_LAST = BC_LOBE_FIRST + MICROFACET_TRANS,   // one per LobeKind added, in LobeKind order
+                  BC_SAMPLE_NO_MATCH, BC_SAMPLE_COMP0, BC_SAMPLE_COMP1, BC_SAMPLE_COMP2, BC_SAMPLE_COMP3, BC_SAMPLE_PDF0, BC_SAMPLE_OTHER_PDFS,
+                  BC_REFRACT_FAIL_SPECULAR, BC_REFRACT_FAIL_MICROFACET, BC_FRESNEL_SPEC_REFLECT, BC_FRESNEL_SPEC_TRANSMIT, BC_FR_SWAP, BC_FR_TIR,
+                  BC_TR11_NORMAL, BC_TR11_CLAMP, BC_MICRO_REJECT_BACK, BC_MICRO_REJECT_HEMI,
+                  BC_ALPHA_CLAMP, BC_OREN_MAX_COS, BC_OREN_SKIP, BC_F_LEAK, BC_DIRECT_F_BLACK, BC_PATH_LAST_QUERY, BC_COUNT };
+std::atomic<uint64_t> g_bsdf_census[BC_COUNT];
+inline void bsdf_count(int k) { g_bsdf_census[k].fetch_add(1, std::memory_order_relaxed); }
+
 inline double cos_theta(V3 w) { return w.z; }
 inline double cos2_theta(V3 w) { return w.z * w.z; }
 inline double abs_cos_theta(V3 w) { return std::fabs(w.z); }
@@ -945,10 +956,10 @@ inline V3 reflect(V3 wo, V3 n) { return -wo + n * 2.0 * dot(wo, n); }  // reflec
 double fr_dielectric(double cos_i, double eta_i, double eta_t) {  // reflection.rs:145-168
   cos_i = clampd(cos_i, -1.0, 1.0);
   bool entering = cos_i > 0.0;
-  if (!entering) { std::swap(eta_i, eta_t); cos_i = std::fabs(cos_i); }
+  if (!entering) { bsdf_count(BC_FR_SWAP); std::swap(eta_i, eta_t); cos_i = std::fabs(cos_i); }
   double sin_i = std::sqrt(rmax(0.0, 1.0 - cos_i * cos_i));
   double sin_t = eta_i / eta_t * sin_i;
-  if (sin_t >= 1.0) return 1.0;
+  if (sin_t >= 1.0) { bsdf_count(BC_FR_TIR); return 1.0; }
   double cos_t = std::sqrt(rmax(0.0, 1.0 - sin_t * sin_t));
   double r_parl = ((eta_t * cos_i) - (eta_i * cos_t)) / ((eta_t * cos_i) + (eta_i * cos_t));
   double r_perp = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
@@ -1012,6 +1023,7 @@ double tr_g(const Lobe& l, V3 wo, V3 wi) { return 1.0 / (1.0 + tr_lambda(l, wo) 
 double tr_pdf(const Lobe& l, V3 wo, V3 wh) { return tr_d(l, wh) * tr_g1(l, wo) * absdot(wo, wh) / abs_cos_theta(wo); }  // microfacet.rs:30-36
 void tr_sample_11(double cos_t, double u1, double u2, double* slope_x, double* slope_y) {  // :268-323
   if (cos_t > 0.9999) {
+    bsdf_count(BC_TR11_NORMAL);
     double r = std::sqrt(u1 / (1.0 - u1));
     double phi = 6.28318530718 * u2;
     *slope_x = r * std::cos(phi);
@@ -1024,7 +1036,7 @@ void tr_sample_11(double cos_t, double u1, double u2, double* slope_x, double* s
   double g1 = 2.0 / (1.0 + std::sqrt(1.0 + 1.0 / (a * a)));
   a = 2.0 * u1 / g1 - 1.0;
   double tmp = 1.0 / (a * a - 1.0);
-  if (tmp > 1e10) tmp = 1e10;
+  if (tmp > 1e10) { bsdf_count(BC_TR11_CLAMP); tmp = 1e10; }
   double b = tan_t;
   double d = std::sqrt(rmax(b * b * tmp * tmp - (a * a - b * b) * tmp, 0.0));
   double sx1 = b * tmp - d, sx2 = b * tmp + d;
@@ -1063,9 +1075,10 @@ Rgb lobe_f(const Lobe& l, V3 wo, V3 wi) {
     case OREN_NAYAR: {              // :917-941
       double sin_i = sin_theta(wi), sin_o = sin_theta(wo), max_cos = 0.0;
       if (sin_i > 1e-4 && sin_o > 1e-4) {
+        bsdf_count(BC_OREN_MAX_COS);
         double d_cos = cos_phi(wi) * cos_phi(wo) + sin_phi(wi) * sin_phi(wo);
         max_cos = rmax(d_cos, 0.0);
-      }
+      } else bsdf_count(BC_OREN_SKIP);
       double sin_alpha, tan_beta;
       if (abs_cos_theta(wi) > abs_cos_theta(wo)) { sin_alpha = sin_o; tan_beta = sin_i / abs_cos_theta(wi); }
       else { sin_alpha = sin_i; tan_beta = sin_o / abs_cos_theta(wo); }
@@ -1125,6 +1138,7 @@ Rgb lobe_sample_f(const Lobe& l, V3 wo, V3* wi, double u0, double u1, double* pd
     if (l.kind == FRESNEL_SPEC) {
       fr = fr_dielectric(cos_theta(wo), l.eta_a, l.eta_b);
       if (u0 < fr) {
+        bsdf_count(BC_FRESNEL_SPEC_REFLECT);
         *wi = V3(-wo.x, -wo.y, wo.z);
         if (sampled_type) *sampled_type = BXDF_SPECULAR | BXDF_REFLECTION;
         *pdf = fr;
@@ -1133,9 +1147,9 @@ Rgb lobe_sample_f(const Lobe& l, V3 wo, V3* wi, double u0, double u1, double* pd
     }
     bool entering = cos_theta(wo) > 0.0;
     double eta_i = entering ? l.eta_a : l.eta_b, eta_t = entering ? l.eta_b : l.eta_a;
-    if (!bsdf_refract(wo, faceforward(V3(0.0, 0.0, 1.0), wo), eta_i / eta_t, wi)) return Rgb();
+    if (!bsdf_refract(wo, faceforward(V3(0.0, 0.0, 1.0), wo), eta_i / eta_t, wi)) { bsdf_count(BC_REFRACT_FAIL_SPECULAR); return Rgb(); }
     Rgb ft;
-    if (l.kind == FRESNEL_SPEC) { ft = l.t * (1.0 - fr); *pdf = 1.0 - fr; if (sampled_type) *sampled_type = BXDF_SPECULAR | BXDF_TRANSMISSION; }
+    if (l.kind == FRESNEL_SPEC) { bsdf_count(BC_FRESNEL_SPEC_TRANSMIT); ft = l.t * (1.0 - fr); *pdf = 1.0 - fr; if (sampled_type) *sampled_type = BXDF_SPECULAR | BXDF_TRANSMISSION; }
     else { ft = l.t * (Rgb(1.0) - Rgb(fr_dielectric(cos_theta(*wi), l.eta_a, l.eta_b))); *pdf = 1.0; }
     ft = ft * ((eta_i * eta_i) / (eta_t * eta_t));
     return ft / abs_cos_theta(*wi);
@@ -1149,18 +1163,18 @@ Rgb lobe_sample_f(const Lobe& l, V3 wo, V3* wi, double u0, double u1, double* pd
   if (l.kind == MICROFACET_TRANS) {  // :1098-1123
     if (wo.z == 0.0) return Rgb();
     V3 wh = tr_sample_wh(l, wo, u0, u1);
-    if (dot(wo, wh) < 0.0) return Rgb();
+    if (dot(wo, wh) < 0.0) { bsdf_count(BC_MICRO_REJECT_BACK); return Rgb(); }
     double eta = cos_theta(wo) > 0.0 ? l.eta_a / l.eta_b : l.eta_b / l.eta_a;
-    if (!bsdf_refract(wo, wh, eta, wi)) return Rgb();
+    if (!bsdf_refract(wo, wh, eta, wi)) { bsdf_count(BC_REFRACT_FAIL_MICROFACET); return Rgb(); }
     *pdf = lobe_pdf(l, wo, *wi);
     return lobe_f(l, wo, *wi);
   }
   if (l.kind == MICROFACET) {  // :993-1018
     if (wo.z == 0.0) return Rgb();
     V3 wh = tr_sample_wh(l, wo, u0, u1);
-    if (dot(wo, wh) < 0.0) return Rgb();
+    if (dot(wo, wh) < 0.0) { bsdf_count(BC_MICRO_REJECT_BACK); return Rgb(); }
     *wi = reflect(wo, wh);
-    if (!same_hemisphere(wo, *wi)) return Rgb();
+    if (!same_hemisphere(wo, *wi)) { bsdf_count(BC_MICRO_REJECT_HEMI); return Rgb(); }
     *pdf = tr_pdf(l, wo, wh) / (4.0 * dot(wo, wh));
     return lobe_f(l, wo, *wi);
   }
@@ -1177,6 +1191,7 @@ Rgb lobe_sample_f(const Lobe& l, V3 wo, V3* wi, double u0, double u1, double* pd
 }
 
 double roughness_to_alpha(double roughness) {  // microfacet.rs:12-20
+  if (!(roughness > 1e-3)) bsdf_count(BC_ALPHA_CLAMP);
   roughness = rmax(roughness, 1e-3);
   double x = std::log(roughness);
   return 1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x;
@@ -1192,7 +1207,7 @@ struct Bsdf {  // reflection.rs:205-405
   void init(const SI& si) {  // Bsdf::new :215-226
     ns = si.sn; ss = vnormalize(si.sdpdu); ng = si.n; ts = cross(ns, ss); n = 0; present = true;
   }
-  void add(const Lobe& l) { if (n >= 8) throw OraclePanic{"reflection.rs:228 assert!(self.bxdfs.len() < MAX_BXDFS)"}; lobes[n++] = l; }
+  void add(const Lobe& l) { if (n >= 8) throw OraclePanic{"reflection.rs:228 assert!(self.bxdfs.len() < MAX_BXDFS)"}; bsdf_count(BC_LOBE_FIRST + (int)l.kind); lobes[n++] = l; }
   static bool match(const Lobe& l, uint8_t flags) { return (l.type & flags) == l.type; }
   int num_components(uint8_t flags) const { int c = 0; for (int i = 0; i < n; i++) if (match(lobes[i], flags)) c++; return c; }
   V3 to_local(V3 v) const { return {dot(v, ss), dot(v, ts), dot(v, ns)}; }
@@ -1201,6 +1216,7 @@ struct Bsdf {  // reflection.rs:205-405
     V3 wi = to_local(wi_w), wo = to_local(wo_w);
     if (wo.z == 0.0) return Rgb();
     bool refl = dot(wi_w, ng) * dot(wo_w, ng) > 0.0;
+    if ((wo.z * wi.z > 0.0) != refl) bsdf_count(BC_F_LEAK);   // the shading frame and the geometric normal disagree on the side
     Rgb r;
     for (int i = 0; i < n; i++) {
       const Lobe& l = lobes[i];
@@ -1220,7 +1236,7 @@ struct Bsdf {  // reflection.rs:205-405
   // sample_f :302-381 (returns only the chosen lobe's f; other pdfs added only for non-reflective lobes: Q21)
   Rgb sample_f(V3 wo_w, V3* wi_w, double u0, double u1, double* pdf_out, uint8_t flags, uint8_t* sampled) const {
     int matching = num_components(flags);
-    if (matching == 0) { *pdf_out = 0.0; *sampled = BXDF_NONE; return Rgb(); }
+    if (matching == 0) { bsdf_count(BC_SAMPLE_NO_MATCH); *pdf_out = 0.0; *sampled = BXDF_NONE; return Rgb(); }
     double fl = std::floor(u0 * (double)matching);
     size_t comp = (fl != fl || fl <= 0.0) ? 0 : (size_t)fl;
     comp = std::min(comp, (size_t)matching);
@@ -1228,6 +1244,7 @@ struct Bsdf {  // reflection.rs:205-405
     for (int i = 0; i < n; i++)
       if (match(lobes[i], flags)) { if (count == 0) { chosen = i; break; } count--; }
     if (chosen < 0) throw OraclePanic{"reflection.rs:337 Did not Choose Any BxDF"};
+    bsdf_count(BC_SAMPLE_COMP0 + (int)std::min(comp, (size_t)3));
     const Lobe& bx = lobes[chosen];
     double ur0 = rmin(u0 * (double)matching - (double)comp, ONE_MINUS_EPSILON), ur1 = u1;
     V3 wi, wo = to_local(wo_w);
@@ -1235,8 +1252,9 @@ struct Bsdf {  // reflection.rs:205-405
     *pdf_out = 0.0;
     *sampled = bx.type;
     Rgb f = lobe_sample_f(bx, wo, &wi, ur0, ur1, pdf_out, sampled);
-    if (*pdf_out == 0.0) { *sampled = BXDF_NONE; return Rgb(); }
+    if (*pdf_out == 0.0) { bsdf_count(BC_SAMPLE_PDF0); *sampled = BXDF_NONE; return Rgb(); }
     *wi_w = to_world(wi);
+    if (!(bx.type & BXDF_REFLECTION) && matching > 1) bsdf_count(BC_SAMPLE_OTHER_PDFS);
     if (!(bx.type & BXDF_REFLECTION) && matching > 1)
       for (int i = 0; i < n; i++) if (i != chosen && match(lobes[i], flags)) *pdf_out += lobe_pdf(lobes[i], wo, wi);
     if (matching > 1) *pdf_out /= (double)matching;
@@ -1701,6 +1719,8 @@ void compute_scattering(const Scene& sc, SI& si, const RayDiff& rd, Bsdf* bsdf, 
     }
     default: throw OraclePanic{"unknown material type in scene desc"};
   }
+  if (bsdf->n == 0) bsdf_count(BC_BUILT_0); else if (bsdf->n == 1) bsdf_count(BC_BUILT_1); else if (bsdf->n == 2) bsdf_count(BC_BUILT_2);
+  else if (bsdf->n == 4) bsdf_count(BC_BUILT_4);
 }
 
 // ---- lights (lights/point.rs, lights/diffuse.rs, shape/mod.rs sample_ref/pdf_ref) ----------------------
@@ -1815,6 +1835,7 @@ Rgb estimate_direct(const Scene& sc, const SI& si, const Bsdf& bsdf, double us0,
       f = bsdf.f(si.wo, wi, flags) * absdot(wi, si.sn);
       scattering_pdf = bsdf.pdf(si.wo, wi, flags);
     }
+    if (f.is_black()) bsdf_count(BC_DIRECT_F_BLACK);
     if (!f.is_black()) {
       if (!unoccluded(sc, si.p, si.n, ls.p1, ls.n1, cnt)) li = Rgb();
       if (!li.is_black()) {
@@ -1923,6 +1944,7 @@ struct Integ {
     while (true) {
       SI isect;
       bool found = scene_intersect(sc, &ray, &isect, nullptr, cnt);
+      if (bounces >= (long)in.max_depth) bsdf_count(BC_PATH_LAST_QUERY);   // the query whose hit only emission would read (path.rs:77,91)
       // isect.le() is 0 (no area-light primitives, Q18); infinite_lights is empty on supported scenes
       (void)specular_bounce;
       if (!found || bounces >= (long)in.max_depth) break;
@@ -2230,6 +2252,11 @@ int oracle_texture_eval(const rrt_scene_desc* d, int32_t tex, const double* si15
 void oracle_mip_census(uint64_t* out, int reset) {
   for (int k = 0; k < MC_COUNT; k++)
     out[k] = reset ? g_mip_census[k].exchange(0, std::memory_order_relaxed) : g_mip_census[k].load(std::memory_order_relaxed);
+}
+// The BSDF branch census since the last reset (process-wide; BsdfCensus order, tests/oracle_lib.py BSDF_CENSUS names the counters)
+void oracle_bsdf_census(uint64_t* out, int reset) {
+  for (int k = 0; k < BC_COUNT; k++)
+    out[k] = reset ? g_bsdf_census[k].exchange(0, std::memory_order_relaxed) : g_bsdf_census[k].load(std::memory_order_relaxed);
 }
 // SurfaceInteraction::compute_differentials: in24 = {n, p, dpdu, dpdv, rx_origin, rx_direction, ry_origin, ry_direction},
 // out10 = {dpdx.xyz, dpdy.xyz, dudx, dvdx, dudy, dvdy}

@@ -621,7 +621,11 @@ template <typename R> RRT_DEV Rgb<R> fr_conductor(R cos_i_in, Rgb<R> eta_i, Rgb<
   Rgb<R> t0 = eta2 - eta_k2 - Rgb<R>(sin2);
   Rgb<R> a2_plus_b2 = rgb_sqrt(t0 * t0 + eta2 * eta_k2 * Rgb<R>(R(4)));
   Rgb<R> t1 = a2_plus_b2 + Rgb<R>(cos2);
-  Rgb<R> a = rgb_sqrt((a2_plus_b2 + t0) * R(0.5));
+  // reflection.rs:185-187: a2_plus_b2 = sqrt(t0^2 + ...) >= |t0|, so the radicand below is >= 0 - and exactly 0 where k = 0 and eta^2 < sin^2 (total reflection,
+  // F = 1), which IEEE's sqrt(t0 * t0) == |t0| delivers. The fp32 product's sqrt is not correctly rounded and its t0 * t0 + ... contracts to an fma: a
+  // square root one ulp short made the radicand negative, a and F NaN, and path.rs:146 asserted on beta (tests/material_shapes.py metal_k0). Clamped: 0
+  // stays 0, every other value keeps its bits.
+  Rgb<R> a = rgb_sqrt(rgb_clamp0((a2_plus_b2 + t0) * R(0.5)));
   Rgb<R> t2 = a * R(2) * cos_i;
   Rgb<R> rs = (t1 - t2) / (t1 + t2);
   Rgb<R> t3 = a2_plus_b2 * cos2 + Rgb<R>(sin2 * sin2);

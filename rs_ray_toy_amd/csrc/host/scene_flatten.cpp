@@ -260,13 +260,14 @@ MaterialScan scan_materials(const rrt_scene_desc* d, bool fp32) {
     else kinds = kAll;
     if (d->prims[i].type == RRT_PRIM_SPHERE && (m.type == RRT_MAT_GLASS || m.type == RRT_MAT_TRANSLUCENT)) transmissive_sphere = true;
     auto black = [](const double* c) { return !(c[0] > 0.0) && !(c[1] > 0.0) && !(c[2] > 0.0); };
+    // (a textured colour is evaluated per hit - glass.rs:66-70, translucent.rs:63-66 - and the kernels raise ERR_NULL_BSDF there; its constant slot says nothing)
     if (m.type == RRT_MAT_GLASS) {
       out.has_transmissive = true;
-      if (black(m.kr) && black(m.kt)) throw PanicError("glass.rs:70 null BSDF: path.rs:103 `bounces -= 1` underflows at the first bounce");
+      if (m.tex[RRT_P_KR] < 0 && m.tex[RRT_P_KT] < 0 && black(m.kr) && black(m.kt)) throw PanicError("glass.rs:70 null BSDF: path.rs:103 `bounces -= 1` underflows at the first bounce");
     }
     if (m.type == RRT_MAT_TRANSLUCENT) {
       out.has_transmissive = out.has_translucent = true;
-      if (black(m.reflect) && black(m.transmit)) throw PanicError("translucent.rs:66 null BSDF: path.rs:103 `bounces -= 1` underflows at the first bounce");
+      if (m.tex[RRT_P_REFLECT] < 0 && m.tex[RRT_P_TRANSMIT] < 0 && black(m.reflect) && black(m.transmit)) throw PanicError("translucent.rs:66 null BSDF: path.rs:103 `bounces -= 1` underflows at the first bounce");
     }
   }
   // sphere.rs has no epsilon: a ray spawned on a sphere re-hits it at t ~ 0 on a last-bit coin, and every refraction through a

@@ -35,6 +35,8 @@ def lib():
         L.oracle_render_rect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.oracle_mip_census.restype = None
         L.oracle_mip_census.argtypes = [C.c_void_p, C.c_int]
+        L.oracle_bsdf_census.restype = None
+        L.oracle_bsdf_census.argtypes = [C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -165,6 +167,30 @@ def mip_census(reset=True):
     out = (C.c_uint64 * len(MIP_CENSUS))()
     lib().oracle_mip_census(out, 1 if reset else 0)
     return dict(zip(MIP_CENSUS, (int(v) for v in out)))
+
+
+BSDF_CENSUS = ("built_0", "built_1", "built_2", "built_4",
+               "lobe_lambert", "lobe_oren_nayar", "lobe_microfacet", "lobe_spec_refl", "lobe_debug_diffuse", "lobe_debug_specular", "lobe_spec_trans",
+               "lobe_fresnel_spec", "lobe_lambert_trans", "lobe_microfacet_trans",
+               "sample_no_match", "sample_comp0", "sample_comp1", "sample_comp2", "sample_comp3", "sample_pdf0", "sample_other_pdfs",
+               "refract_fail_specular", "refract_fail_microfacet", "fresnel_spec_reflect", "fresnel_spec_transmit", "fr_swap", "fr_tir",
+               "tr11_normal", "tr11_clamp", "micro_reject_back", "micro_reject_hemi",
+               "alpha_clamp", "oren_max_cos", "oren_skip", "f_leak", "direct_f_black", "path_last_query")
+
+
+def bsdf_census(reset=True):
+    """What the oracle's material and BxDF code did since the last reset (BsdfCensus in rrt_oracle.cpp), process-wide: BSDFs built with 0 / 1 / 2 / 4
+    lobes and the lobes added per kind; Bsdf::sample_f calls with no matching lobe, by the index of the chosen component, that returned pdf 0 and
+    that added the other lobes' pdfs (a non-reflective lobe chosen among several); refract() failures in SpecularTransmission / FresnelSpecular
+    and in MicrofacetTransmission; FresnelSpecular's two branches; fr_dielectric calls that swapped the indices (cos_i <= 0) and that met total
+    internal reflection; tr_sample_11's cos_t > 0.9999 branch and its 1e10 clamp; microfacet samples rejected by dot(wo, wh) < 0 and by
+    !same_hemisphere; roughness_to_alpha calls at or below its 1e-3 clamp; Oren-Nayar evaluations with max_cos computed and skipped; Bsdf::f calls
+    where the shading frame and the geometric normal disagree on reflection against transmission; estimate_direct returns on a black f; closest-hit queries the path integrator
+    issued at bounces == max_depth (the device leaves them out: DESIGN.md section 3, dead work 2). Call it
+    once to reset, render, call it again to read."""
+    out = (C.c_uint64 * len(BSDF_CENSUS))()
+    lib().oracle_bsdf_census(out, 1 if reset else 0)
+    return dict(zip(BSDF_CENSUS, (int(v) for v in out)))
 
 
 def surface_differentials(n, p, dpdu, dpdv, rxo, rxd, ryo, ryd):

@@ -70,3 +70,27 @@ def boxes_on_a_plane(workdir, seed, n_boxes=7):
     with open(os.path.join(workdir, "heightfield.obj"), "w") as f:
         np.savetxt(f, np.array(V), fmt="v %.9g %.9g %.9g"); np.savetxt(f, np.array(F), fmt="f %d %d %d")
     return cfg, root
+
+
+def write_patch(workdir, half=7.0, bend=0.02):
+    """A curved 6 x 6 patch with smooth vertex normals and vt (non-zero dndu / dndv, real uv): the cube's normals are per-face."""
+    n = 6
+    lines = []
+    xs = [-half + 2.0 * half * i / n for i in range(n + 1)]
+    for z in xs:
+        for x in xs:
+            lines.append(f"v {x:.6f} {bend * (x * x + 0.5 * z * z):.6f} {z:.6f}")
+    for j in range(n + 1):
+        for i in range(n + 1):
+            lines.append(f"vt {i / n:.6f} {j / n:.6f}")
+    for z in xs:
+        for x in xs:
+            g = np.array([-2.0 * bend * x, 1.0, -bend * z]); g /= np.linalg.norm(g)
+            lines.append(f"vn {g[0]:.6f} {g[1]:.6f} {g[2]:.6f}")
+    for j in range(n):
+        for i in range(n):
+            a, b, c, d = j * (n + 1) + i + 1, j * (n + 1) + i + 2, (j + 1) * (n + 1) + i + 2, (j + 1) * (n + 1) + i + 1
+            lines.append(f"f {a}/{a}/{a} {d}/{d}/{d} {c}/{c}/{c}")
+            lines.append(f"f {a}/{a}/{a} {c}/{c}/{c} {b}/{b}/{b}")
+    with open(os.path.join(workdir, "patch.obj"), "w") as f:
+        f.write("\n".join(lines) + "\n")

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from scene_util import boxes_on_a_plane, rough_terrain
+from scene_util import boxes_on_a_plane, rough_terrain, write_patch as _write_patch
 from rs_ray_toy_amd import (RRT_F32, RRT_F64, RRT_FIXED_BVH, RRT_INSTANCES_FLATTEN, RRT_INSTANCES_KEEP, Renderer, RrtPanic, RrtUnsupported,
                             Scene, scenes)
 
@@ -1602,30 +1602,6 @@ def test_unsupported_and_panics(workdir):
 
 
 # ---- textures: texture graph + ray differentials on the device -----------------------------
-def _write_patch(workdir, half=7.0, bend=0.02):
-    """A curved 6 x 6 patch with smooth vertex normals and vt (non-zero dndu / dndv, real uv): the cube's normals are per-face."""
-    n = 6
-    lines = []
-    xs = [-half + 2.0 * half * i / n for i in range(n + 1)]
-    for z in xs:
-        for x in xs:
-            lines.append(f"v {x:.6f} {bend * (x * x + 0.5 * z * z):.6f} {z:.6f}")
-    for j in range(n + 1):
-        for i in range(n + 1):
-            lines.append(f"vt {i / n:.6f} {j / n:.6f}")
-    for z in xs:
-        for x in xs:
-            g = np.array([-2.0 * bend * x, 1.0, -bend * z]); g /= np.linalg.norm(g)
-            lines.append(f"vn {g[0]:.6f} {g[1]:.6f} {g[2]:.6f}")
-    for j in range(n):
-        for i in range(n):
-            a, b, c, d = j * (n + 1) + i + 1, j * (n + 1) + i + 2, (j + 1) * (n + 1) + i + 2, (j + 1) * (n + 1) + i + 1
-            lines.append(f"f {a}/{a}/{a} {d}/{d}/{d} {c}/{c}/{c}")
-            lines.append(f"f {a}/{a}/{a} {c}/{c}/{c} {b}/{b}/{b}")
-    with open(os.path.join(workdir, "patch.obj"), "w") as f:
-        f.write("\n".join(lines) + "\n")
-
-
 def _const_rgb(name, v):
     return {"texture_name": name, "texture_type": "BilerpTexture", "v00": {"values": v}, "v01": {"values": v}}
 

@@ -1,0 +1,328 @@
+"""The device's BSDF code (dmath.hpp: build_lobes, Bsdf::f / pdf / sample_f, lobe_f / lobe_pdf / lobe_sample_f, the Trowbridge-Reitz helpers, fr_dielectric,
+fr_conductor, roughness_to_alpha) on hand-built material tables (tests/material_shapes.py), against the f64 oracle.
+
+Every other GPU test shades materials with all their lobes present and mid-range parameters. The table of material_shapes.py walks the code through what that
+never reaches: lobe sets with gaps in the device's fixed slots, empty BSDFs (also in the Lambert and Glossy kernel instantiations), parameters on and beyond
+their clamps, alpha_x != alpha_y, alpha 0, glass at index 1 and below 1, a conductor with k = 0, and lobe sets that differ from hit to hit inside one wave.
+material_shapes.py says which case reaches what, and the oracle's BSDF census (oracle_lib.bsdf_census) proves per case that the frame does reach it: the
+proof is counted on the reference side.
+
+CPU tests (the host loader and the oracle alone):
+  test_case_loads_and_reaches_its_branches    the loaded rrt_material holds the table's constants, no texture bound (per-hit cases: the one slot); the
+                                              oracle's frame is finite and lit, or the recorded panic occurs; the census has what the case's tags ask; the
+                                              slab takes more than a third of the camera's first hits
+  test_lobe_subsets_give_different_frames     the oracle's frames of the ten Translucent lobe sets differ pairwise in more than a tenth of the pixels, and
+                                              so do glass with kr only / kt only / both: a device that dropped or misplaced a slot cannot pass
+  test_clamped_pairs_are_one_material         sigma 200 / 90, sigma -5 / 0, remapped roughness 0 / 1e-3: bit-equal oracle frames
+  test_closed_forms_at_the_edges              through oracle_lib.bsdf_eval: glass at index 1 passes straight through with f |cos| / pdf = kt, glass at index
+                                              0.75 reflects all beyond asin(0.75), the gap rule of the Translucent subsets, an empty Plastic, a black Metal
+GPU tests, a 64 x 64 film each:
+  test_f64_frame_matches_oracle               weights and the three counters equal, colour within 1e-9 of the brightest pixel; RrtPanic where the oracle
+                                              panics; where it drops samples the frame is finite and dark exactly where the oracle's is
+  test_fp32_frame_close_to_oracle             test_gpu_parity.py::test_transmissive_materials_path's fp32 bar; RrtPanic where the oracle panics
+  test_kernel_class_changes_nothing           the constant Matte / Plastic / Metal cases: the specialised shading kernel against the general one
+  test_shortcuts_change_no_bit                shade compaction and tile order off (and kernel specialisation, where the general kernel runs anyway): the fp32
+                                              frame keeps its bits
+  test_horizon_cull_below_the_surface         the Translucent cases on the terrain: the horizon tables answer transmitted bounce rays, the frame keeps its bits
+"""
+import numpy as np
+import pytest
+
+import material_shapes as MS
+import oracle_lib as O
+from rs_ray_toy_amd import RRT_F32, RRT_F64, RRT_SKIP_MIS_BSDF_RAY, Renderer, RrtPanic, Scene
+
+ALL = sorted(MS.CASES)
+FRAMES = [k for k in ALL if MS.CASES[k].oracle != "panic"]
+F64_ONLY = [k for k in ALL if MS.CASES[k].fp32.startswith("f64_only")]
+assert len(F64_ONLY) <= 3 and all(MS.CASES[k].material[0] == "MetalMaterial" for k in F64_ONLY)      # never a lobe-subset, empty-set or per-hit case
+# BxDFType bits (reflection.rs:28-36)
+REFLECTION, TRANSMISSION, DIFFUSE, GLOSSY, SPECULAR = 1, 2, 4, 8, 16
+SLOT_FLAGS = (DIFFUSE | REFLECTION, DIFFUSE | TRANSMISSION, GLOSSY | REFLECTION, GLOSSY | TRANSMISSION)
+
+_scenes, _refs = {}, {}
+
+
+def _scene(name, workdir):
+    if name not in _scenes:
+        # under an area light the oracle traces estimate_direct's BSDF-sampled ray, which can only add 0 and which the device leaves out (DESIGN.md section 3,
+        # dead work 1; tests/test_oracle.py shows the pixels identical): with the flag the oracle leaves it out too and the query counters compare
+        _scenes[name] = Scene.loads(*MS.scene(workdir, name), flags=RRT_SKIP_MIS_BSDF_RAY if MS.CASES[name].carrier == "area" else 0)
+    return _scenes[name]
+
+
+def _ref(name, workdir):
+    """(frame, (camera rays, closest queries the device issues, any queries), census) of the oracle for the case, rendered once and never written to; (None, panic message, census) where the oracle panics"""
+    if name not in _refs:
+        sc = _scene(name, workdir)
+        O.bsdf_census()
+        try:
+            film, st = O.render(sc, stats=True)
+            film.setflags(write=False)
+            census = O.bsdf_census()
+            # the device leaves out the path integrator's closest-hit query at bounces == max_depth, whose hit only emission would read (DESIGN.md section 3,
+            # dead work 2; test_gpu_parity.py compares no closest_queries under Path for that reason): the oracle counts those, so the expectation stays exact
+            _refs[name] = (film, (int(st.camera_rays), int(st.closest_queries) - census["path_last_query"], int(st.any_queries)), census)
+        except O.OracleError as e:
+            _refs[name] = (None, str(e), O.bsdf_census())
+    return _refs[name]
+
+
+def _lit(film):
+    return float((film[..., :3].max(-1) > 0).mean())
+
+
+def _material(sc):
+    return sc.desc.materials[sc.desc.n_materials - 1]
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ALL)
+def test_case_loads_and_reaches_its_branches(name, workdir):
+    c = MS.CASES[name]
+    sc = _scene(name, workdir)
+    m = _material(sc)
+    assert m.type == MS.MATERIAL_TYPE[c.material[0]] and (m.bump >= 0) == (c.carrier == "bump")
+    for field, want in MS.expected_constants(c).items():
+        got = getattr(m, field)
+        assert (list(got) if isinstance(want, list) else got) == want, (field, want)
+    bound = sorted(k for k in range(13) if m.tex[k] >= 0)
+    assert bound == sorted(MS.TEX_SLOT[k] for k in (c.per_hit or {})), bound
+    film, counters, census = _ref(name, workdir)
+    if c.oracle == "panic":
+        assert film is None and "path.rs:146 assert!(beta.y() > 0.0)" in counters, counters
+        return
+    assert film is not None, counters
+    print(f"{name}: lit {_lit(film):.4f}, brightest {film[..., :3].max():.4f}, counters {counters}, census { {k: v for k, v in census.items() if v} }")
+    assert np.all(np.isfinite(film)) and np.all(film[..., 3] > 0)
+    assert _lit(film) > 0.01
+    assert not MS.census_problems(c, census), (MS.census_problems(c, census), census)
+    if c.oracle == "drops":      # NaN samples dropped at the film (integrator/mod.rs:105): the slab is dark, and the frame without it is not
+        assert _lit(film) < 0.5 * _lit(_ref(f"rough_glass_v0_remap-{c.integrator}", workdir)[0])
+    if c.carrier in ("slab", "area"):
+        share, hits = MS.slab_coverage(sc, O)
+        assert hits > 4000 and share >= MS.SLAB_COVERAGE, (share, hits)
+
+
+SUBSET_GROUPS = {
+    "translucent-path": [f"translucent_{s}-path" for s in MS.TRANSLUCENT_SUBSETS],
+    "translucent-direct": [f"translucent_{s}-direct" for s in MS.TRANSLUCENT_SUBSETS],
+    "glass-path": ["glass_kr_only-path", "glass_kt_only-path", "glass_both-path"],
+    "glass-direct": ["glass_kr_only-direct", "glass_kt_only-direct", "glass_both-direct"],
+}
+
+
+@pytest.mark.parametrize("group", sorted(SUBSET_GROUPS))
+def test_lobe_subsets_give_different_frames(group, workdir):
+    names = SUBSET_GROUPS[group]
+    films = [_ref(n, workdir)[0][..., :3] for n in names]
+    pixels = films[0].shape[0] * films[0].shape[1]
+    for a in range(len(names)):
+        for b in range(a + 1, len(names)):
+            scale = max(films[a].max(), films[b].max())
+            differ = int((np.abs(films[a] - films[b]).max(-1) > 1e-6 * scale).sum())
+            print(f"{names[a]} against {names[b]}: {differ} of {pixels} pixels differ")
+            assert differ > pixels // 10, (names[a], names[b], differ)
+
+
+PAIRS = sorted((k, c.pair) for k, c in MS.CASES.items() if c.pair)
+
+
+@pytest.mark.parametrize("name,partner", PAIRS, ids=[a for a, _ in PAIRS])
+def test_clamped_pairs_are_one_material(name, partner, workdir):
+    (a, ca, _), (b, cb, _) = _ref(name, workdir), _ref(partner, workdir)
+    assert _material(_scene(name, workdir)).sigma != _material(_scene(partner, workdir)).sigma or \
+        _material(_scene(name, workdir)).roughness != _material(_scene(partner, workdir)).roughness      # two spellings ...
+    assert np.array_equal(a, b) and ca == cb                                                             # ... of one material
+
+
+def _unit(v):
+    v = np.asarray(v, np.float64)
+    return v / np.linalg.norm(v)
+
+
+def test_closed_forms_at_the_edges(workdir):
+    mat = lambda name: (_scene(name, workdir), _scene(name, workdir).desc.n_materials - 1)
+    # glass at index 1 under the path integrator (FresnelSpecular): F = 0 up to the rounding of cos_t = sqrt(1 - sin_i^2) against cos_i (3e-30 at the grazing wo below), so
+    # the reflect branch `u0 < F` is unreachable for any u0 a sampler draws but an exact 0; refraction is the identity and f |cos| / pdf = kt (eta_i^2 / eta_t^2 = 1)
+    for wo in (_unit([0.3, 0.2, 0.9]), _unit([0.9, -0.3, 0.1]), _unit([0.2, 0.5, -0.7])):
+        for u0 in (1e-20, 0.5, 0.999):
+            e = O.bsdf_eval(*mat("glass_index1-path"), wo, -wo, u0, 0.5)
+            assert e["n_lobes"] == 1 and e["s_flags"] == SPECULAR | TRANSMISSION and e["s_pdf"] == 1.0
+            assert np.allclose(e["s_wi"], -wo, rtol=0, atol=1e-15)
+            assert np.allclose(e["s_f"] * abs(e["s_wi"][2]) / e["s_pdf"], [0.8, 0.9, 1.0], rtol=1e-14, atol=0)
+    # glass at index 0.75, entering (wo on the normal's side) beyond asin(0.75): total internal reflection on the way IN, reflection with pdf 1
+    for sin_o in (0.76, 0.9, 0.999):
+        wo = np.array([sin_o, 0.0, np.sqrt(1.0 - sin_o * sin_o)])
+        for u0 in (0.0, 0.5, 0.999):
+            e = O.bsdf_eval(*mat("glass_index0.75-path"), wo, -wo, u0, 0.5)
+            assert e["s_flags"] == SPECULAR | REFLECTION and e["s_pdf"] == 1.0
+            assert np.array_equal(e["s_wi"], [-wo[0], -wo[1], wo[2]])
+    e = O.bsdf_eval(*mat("glass_index0.75-path"), np.array([0.5, 0.0, np.sqrt(0.75)]), [0.0, 0.0, -1.0], 0.9, 0.5)      # inside asin(0.75): refracts
+    assert e["s_flags"] == SPECULAR | TRANSMISSION
+    # the Translucent subsets: the count-th matching component skips the empty slots (reflection.rs:302-337)
+    wo = _unit([0.3, 0.2, 0.9])
+    for subset, slots in MS.SUBSET_SLOTS.items():
+        for integ, multi in (("path", True), ("direct", False)):
+            sc, mi = mat(f"translucent_{subset}-{integ}")
+            for u0 in (0.1, 0.6):
+                e = O.bsdf_eval(sc, mi, wo, _unit([0.1, -0.4, 0.8]), u0, 0.4, allow_multiple_lobes=multi)
+                assert e["n_lobes"] == len(slots) == e["n_nonspecular"], (subset, e)
+                want = SLOT_FLAGS[slots[int(u0 * len(slots))]] if slots else 0
+                assert e["s_flags"] == want and (e["s_pdf"] > 0) == bool(slots), (subset, u0, e, want)
+                assert (e["s_wi"][2] < 0) == bool(want & TRANSMISSION), (subset, u0, e)
+    # ... and the pdf of the Lambertian-only subsets integrates to 1 over the sphere (midpoint rule in cos theta, exact for |cos| / pi on each hemisphere)
+    mu = (np.arange(64) + 0.5) / 32.0 - 1.0
+    phi = (np.arange(16) + 0.5) * (2.0 * np.pi / 16)
+    for subset in ("s0", "s1", "s01"):
+        sc, mi = mat(f"translucent_{subset}-path")
+        total = 0.0
+        for m_ in mu:
+            for p_ in phi:
+                s_ = np.sqrt(1.0 - m_ * m_)
+                total += O.bsdf_eval(sc, mi, wo, [s_ * np.cos(p_), s_ * np.sin(p_), m_])["pdf"]
+        total *= (2.0 / 64) * (2.0 * np.pi / 16)
+        assert abs(total - 1.0) < 1e-12, (subset, total)
+    # Plastic with kd black: no lobe at all (the specular lobe is gated on kd, plastic.rs:42-73, quirk Q31)
+    e = O.bsdf_eval(*mat("plastic_kd_black-walls"), wo, _unit([0.1, -0.4, 0.8]))
+    assert e["n_lobes"] == 0 and e["s_pdf"] == 0 and e["s_flags"] == 0 and not e["f"].any() and e["pdf"] == 0
+    # Metal with eta = 1 and k = 0: F = 0. fr_conductor (reflection.rs:170-195) reaches it through sqrt(cos^4) and 2 |cos| |cos|, which round apart by a few
+    # ulp of cos^2: f is zero to 1e-15 of the D G / (4 cos cos) it multiplies, not always to the bit
+    for wi in (_unit([0.1, -0.4, 0.8]), _unit([-0.3, -0.2, 0.9]), _unit([0.9, 0.1, 0.2])):
+        e = O.bsdf_eval(*mat("metal_eta1_k0-walls"), wo, wi)
+        k0 = O.bsdf_eval(*mat("metal_k0-walls"), wo, wi)
+        assert k0["f"].min() > 0 and np.abs(e["f"]).max() <= 1e-15 * k0["f"].max(), (e["f"], k0["f"])
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------------
+
+def _counters(st):
+    return (st.camera_rays, st.closest_queries, st.any_queries)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ALL)
+def test_f64_frame_matches_oracle(name, workdir):
+    ref, counters, _ = _ref(name, workdir)
+    r = Renderer(_scene(name, workdir), 0, RRT_F64)
+    if MS.CASES[name].oracle == "panic":
+        with pytest.raises(RrtPanic, match="path.rs:146"):
+            r.render()
+        r.close()
+        return
+    film, st = r.render(stats=True)
+    r.close()
+    assert np.array_equal(film[..., 3], ref[..., 3])
+    assert _counters(st) == counters
+    if MS.CASES[name].oracle == "drops":
+        assert np.all(np.isfinite(film))
+        assert np.array_equal(film[..., :3].max(-1) > 0, ref[..., :3].max(-1) > 0)
+    scale = np.abs(ref[..., :3]).max()
+    if scale == 0:      # an empty BSDF on every surface: a black frame
+        assert not film[..., :3].any()
+        return
+    diff = np.abs(film[..., :3] - ref[..., :3]).max(-1) / scale
+    print(f"{name}: f64 max {diff.max():.3e}")
+    assert diff.max() < 1e-9, (diff.max(), int((diff > 1e-9).sum()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ALL)
+def test_fp32_frame_close_to_oracle(name, workdir):
+    """The cases the table marks f64-only (F64_ONLY; material_shapes.py argues each beside the case) keep everything here but the bar on the colour."""
+    ref, _, _ = _ref(name, workdir)
+    r = Renderer(_scene(name, workdir), 0, RRT_F32)
+    if MS.CASES[name].oracle == "panic":
+        assert MS.CASES[name].fp32 == "panic"
+        with pytest.raises(RrtPanic, match="path.rs:146"):
+            r.render()
+        r.close()
+        return
+    f32 = r.render().astype(np.float64)
+    r.close()
+    assert np.array_equal(f32[..., 3], ref[..., 3])
+    assert np.all(np.isfinite(f32))
+    scale = np.abs(ref[..., :3]).max()
+    if scale == 0:
+        assert not f32[..., :3].any()
+        return
+    d32 = np.abs(f32[..., :3] - ref[..., :3]).max(-1) / scale
+    print(f"{name}: f32 within 1e-4: {(d32 < 1e-4).mean():.4f}, median {np.median(d32):.3e}, max {d32.max():.3e}")
+    if name not in F64_ONLY:
+        assert (d32 < 1e-4).mean() > 0.99 and np.median(d32) < 1e-5, ((d32 < 1e-4).mean(), np.median(d32), d32.max())
+
+
+KERNEL_CLASS = [k for k in FRAMES if MS.CASES[k].carrier in ("walls", "field", "field_cube") and MS.CASES[k].per_hit is None and MS.CASES[k].integrator == MS.PATH and
+                MS.CASES[k].material[0] in ("MatteMaterial", "PlasticMaterial", "MetalMaterial")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", KERNEL_CLASS)
+def test_kernel_class_changes_nothing(name, workdir):
+    """test_gpu_parity.py::test_shading_kernel_specialisation on the table's constant opaque materials: the Lambert or Glossy instantiation of the path shading
+    kernel (host/scene_flatten.cpp scan_materials() restates build_lobes' conditions to choose it) against the general one. A lobe outside the chosen set would
+    raise DeviceError (ERR_KIND_SET) from render()."""
+    ref, _, _ = _ref(name, workdir)
+    scale = np.abs(ref[..., :3]).max()
+    r = Renderer(_scene(name, workdir), 0, RRT_F32)
+    spec, st_spec = r.render(stats=True)
+    r.set_option("shade_spec", 0)
+    gen, st_gen = r.render(stats=True)
+    r.close()
+    assert _counters(st_spec) == _counters(st_gen)
+    assert np.array_equal(spec[..., 3], gen[..., 3])
+    if scale == 0:
+        assert not spec[..., :3].any() and not gen[..., :3].any()
+        return
+    d = np.abs(spec[..., :3].astype(np.float64) - gen[..., :3]).max(-1) / scale
+    print(f"{name}: specialised against general: within 1e-6: {(d < 1e-6).mean():.4f}, median {np.median(d):.3e}, max {d.max():.3e}")
+    assert (d < 1e-6).mean() > 0.995 and np.median(d) < 1e-7, ((d < 1e-6).mean(), d.max())
+    for film in (spec, gen) if name not in F64_ONLY else ():      # (no fp32 statement against the oracle for those: material_shapes.py says why)
+        dd = np.abs(film[..., :3].astype(np.float64) - ref[..., :3]).max(-1) / scale
+        assert (dd < 1e-4).mean() > 0.99 and np.median(dd) < 1e-5, ((dd < 1e-4).mean(), dd.max())
+
+
+def _general_kernel_anyway(c):
+    return c.per_hit is not None or c.material[0] in ("GlassMaterial", "TranslucentMaterial", "MirrorMaterial")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FRAMES)
+def test_shortcuts_change_no_bit(name, workdir):
+    """The shading-side options reorder or specialise the work around the BSDF and must not touch it (test_gpu_parity.py: test_shade_compaction_changes_nothing,
+    test_tile_order_of_the_pixels_changes_nothing; test_shading_kernel_specialisation's cfg2_mixed for the scenes only the general kernel fits)."""
+    r = Renderer(_scene(name, workdir), 0, RRT_F32)
+    base, st0 = r.render(stats=True)
+    for opt in ("shade_compact", "tile_order") + (("shade_spec",) if _general_kernel_anyway(MS.CASES[name]) else ()):
+        r.set_option(opt, 0)
+        film, st = r.render(stats=True)
+        r.set_option(opt, 1)
+        assert np.array_equal(film, base), opt
+        assert _counters(st) == _counters(st0), opt
+    r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MS.find(carrier="field", mtype="TranslucentMaterial"))
+def test_horizon_cull_below_the_surface(name, workdir, monkeypatch):
+    """test_gpu_parity.py::test_horizon_cull_changes_nothing with a transmissive terrain: a bounce ray that leaves BELOW its start triangle is answered by the
+    u < 0 half of the horizon tables."""
+    monkeypatch.setenv("RRT_HZ_CHECK", "20000")
+    _, counters, census = _ref(name, workdir)
+    # the oracle's paths do continue below the surface: transmissive lobes are chosen (every chosen lobe of s13 is one)
+    assert census["lobe_lambert_trans"] > 1000 and census["lobe_microfacet_trans"] > 1000 and counters[1] > counters[0]
+    if name.startswith("translucent_s13"): assert census["lobe_lambert"] == 0 and census["lobe_microfacet"] == 0 and census["sample_comp0"] > 1000
+    else: assert census["sample_other_pdfs"] > 500
+    r = Renderer(_scene(name, workdir), 0, RRT_F32)
+    out = {}
+    for h in (1, 0):
+        r.set_option("horizon_cull", h)
+        out[h] = r.render(stats=True)
+    r.close()
+    assert out[1][0][..., :3].max() > 0
+    assert np.array_equal(out[1][0], out[0][0])
+    assert _counters(out[1][1]) == _counters(out[0][1])
+    assert out[0][1].sky_culled == 0
+    print(f"horizon cull, {name}: {out[1][1].sky_culled} of {out[1][1].closest_queries} closest-hit queries answered by the tables")
+    assert out[1][1].sky_culled > 0
