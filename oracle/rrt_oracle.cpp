@@ -266,6 +266,26 @@ bool tri_intersect_p(const Scene& sc, const rrt_tri& t, const Ray& r, const rrt_
   return true;
 }
 // intersect :226-391 (never compares t with ray.t_max: Q10)
+// Texture census (oracle_tex_census): which branch of the texture graph, the mappings, the noise, compute_differentials, Material::bump and the triangle's
+// uv set-up every call took, so that a test frame can be shown from the reference side to reach the branch it is named after. The counters only count
+// (relaxed: frames render on several threads); no result reads them. TC_DEPTH_MAX is a maximum, not a count. tests/oracle_lib.py TEX_CENSUS names them.
+enum TexCensus { TC_NODE_CONSTANT, TC_NODE_MIX, TC_NODE_BILERP, TC_NODE_CHECKER2D, TC_NODE_CHECKER3D, TC_NODE_SCALE, TC_NODE_WINDY, TC_NODE_WRINKLED, TC_NODE_UV,
+                 TC_NODE_IMAGE, TC_DEPTH_MAX,
+                 TC_FB_MIX_T1, TC_FB_MIX_T2, TC_FB_MIX_AMOUNT, TC_FB_SCALE_T1, TC_FB_SCALE_T2, TC_FB_CHECKER_T1, TC_FB_CHECKER_T2,
+                 TC_CHK_AA_NONE, TC_CHK_SAME_CELL, TC_CHK_FILTERED, TC_CHK_HALF, TC_CHK_NEGATIVE_SUM, TC_CHK_BUMP_INT_NEGATIVE, TC_CHK3_NEGATIVE_SUM,
+                 TC_ROUND_CALLS, TC_ROUND_PHI_WRAPPED, TC_FOLD_DX_HIGH, TC_FOLD_DX_LOW, TC_FOLD_DY_HIGH, TC_FOLD_DY_LOW, TC_ROUND_POLE,
+                 TC_NOISE_SUMS, TC_NOISE_N_INT_0, TC_NOISE_PARTIAL, TC_NOISE_ALL_OCTAVES, TC_NOISE_CALLS, TC_NOISE_NEGATIVE_LATTICE, TC_NOISE_SATURATED,
+                 TC_DIFF_CALLS, TC_DIFF_NO_AUX, TC_DIFF_NOT_FINITE, TC_DIFF_AXIS_YZ, TC_DIFF_AXIS_XZ, TC_DIFF_AXIS_XY, TC_DIFF_SOLVE_FAILED,
+                 TC_BUMP_CALLS, TC_BUMP_DU_FALLBACK, TC_BUMP_DV_FALLBACK, TC_BUMP_SLOPE, TC_BUMP_FALLBACK_SLOPE,
+                 TC_TRI_HITS, TC_TRI_DEGENERATE_UV, TC_TRI_NEGATIVE_DET, TC_TRI_COORD_DN,
+                 TC_MIX_AMOUNT_OUTSIDE, TC_MAT_NEGATIVE_VALUE, TC_COUNT };
+std::atomic<uint64_t> g_tex_census[TC_COUNT];
+inline void tex_count(int k) { g_tex_census[k].fetch_add(1, std::memory_order_relaxed); }
+inline void tex_count_max(int k, uint64_t v) {
+  uint64_t cur = g_tex_census[k].load(std::memory_order_relaxed);
+  while (cur < v && !g_tex_census[k].compare_exchange_weak(cur, v, std::memory_order_relaxed)) {}
+}
+
 bool tri_intersect(const Scene& sc, const rrt_tri& t, const Ray& r, double* thit, SI* ist, double* bu, double* bv, const rrt_xform* fx = nullptr, double* tri_margin = nullptr) {
   const TriGaps gap{tri_margin};
   V3 p0 = sc.P(t.v[0]), p1 = sc.P(t.v[1]), p2 = sc.P(t.v[2]);
@@ -297,6 +317,8 @@ bool tri_intersect(const Scene& sc, const rrt_tri& t, const Ray& r, double* thit
   V3 dp02 = p0 - p2, dp12 = p1 - p2;
   double determinant = duv02[0] * duv12[1] - duv02[1] * duv12[0];
   bool degenerate_uv = std::fabs(determinant) < 1e-8;
+  tex_count(TC_TRI_HITS);
+  if (degenerate_uv) tex_count(TC_TRI_DEGENERATE_UV); else if (determinant < 0.0) tex_count(TC_TRI_NEGATIVE_DET);
   V3 dpdu, dpdv;
   if (!degenerate_uv) {
     double i_det = 1.0 / determinant;
@@ -329,7 +351,7 @@ bool tri_intersect(const Scene& sc, const rrt_tri& t, const Ray& r, double* thit
       V3 dn1 = n0 - n2, dn2 = n1 - n2;
       if (degenerate_uv) {
         V3 dn = cross(n2 - n0, n1 - n0);
-        if (len2(dn) != 0.0) coordinate_system(dn, &dndu, &dndv);
+        if (len2(dn) != 0.0) { tex_count(TC_TRI_COORD_DN); coordinate_system(dn, &dndu, &dndv); }
       } else {
         double i_det = 1.0 / determinant;
         dndu = (dn1 * duv12[1] - dn2 * duv02[1]) * i_det;
@@ -340,6 +362,14 @@ bool tri_intersect(const Scene& sc, const rrt_tri& t, const Ray& r, double* thit
   }
   *bu = u; *bv = v;
   return true;
+}
+// flat mode: the device does not flatten a triangle with a degenerate uv (host/scene_flatten.cpp uv_degenerate: coordinate_system() of an object-space
+// vector does not commute with the instance's rotation)
+bool tri_uv_degenerate(const Scene& sc, const rrt_tri& t) {
+  if (!t.mesh_has_uv) return false;
+  double uv[3][2];
+  for (int k = 0; k < 3; k++) sc.UV(t.uv[k], &uv[k][0], &uv[k][1]);
+  return std::fabs((uv[0][0] - uv[2][0]) * (uv[1][1] - uv[2][1]) - (uv[0][1] - uv[2][1]) * (uv[1][0] - uv[2][0])) < 1e-8;
 }
 double tri_area(const Scene& sc, const rrt_tri& t) {  // :420-425
   V3 p0 = sc.P(t.v[0]), p1 = sc.P(t.v[1]), p2 = sc.P(t.v[2]);
@@ -803,7 +833,7 @@ bool prim_intersect(const Scene& sc, uint32_t pi, Ray* r, SI* si, double* bu, do
   };
   if (p.instance < 0) return geometric(r);
   const rrt_xform& x = sc.d->xforms[p.instance];
-  if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(x.m)) {
+  if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(x.m) && !tri_uv_degenerate(sc, sc.d->tris[p.shape])) {
     double t_hit = 0.0;
     if (!tri_intersect(sc, sc.d->tris[p.shape], *r, &t_hit, si, bu, bv, &x, tri_margin)) return false;
     si->prim = (int)pi; si->valid = true;
@@ -823,7 +853,7 @@ bool prim_intersect_p(const Scene& sc, uint32_t pi, const Ray& r, double* tri_ma
     return p.type == RRT_PRIM_TRIANGLE ? tri_intersect_p(sc, sc.d->tris[p.shape], rr, nullptr, tri_margin) : sphere_intersect_p(sphere_ref(sc, p.shape), rr);
   };
   if (p.instance < 0) return geometric(r);
-  if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(sc.d->xforms[p.instance].m)) return tri_intersect_p(sc, sc.d->tris[p.shape], r, &sc.d->xforms[p.instance], tri_margin);
+  if (sc.flat && p.type == RRT_PRIM_TRIANGLE && is_rigid(sc.d->xforms[p.instance].m) && !tri_uv_degenerate(sc, sc.d->tris[p.shape])) return tri_intersect_p(sc, sc.d->tris[p.shape], r, &sc.d->xforms[p.instance], tri_margin);
   return geometric(xf_ray(sc.d->xforms[p.instance].m_inv, r));
 }
 
@@ -1276,13 +1306,14 @@ inline double v3_at(V3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 void compute_differentials(SI* si, const RayDiff& rd) {
   si->dudx = si->dvdx = si->dudy = si->dvdy = 0.0;
   si->dpdx = si->dpdy = V3();
-  if (!rd.has) return;
+  tex_count(TC_DIFF_CALLS);
+  if (!rd.has) { tex_count(TC_DIFF_NO_AUX); return; }
   double d = dot(si->n, si->p);
   double tx = -(dot(si->n, rd.rxo) - d) / dot(si->n, rd.rxd);
-  if (std::isinf(tx) || std::isnan(tx)) return;
+  if (std::isinf(tx) || std::isnan(tx)) { tex_count(TC_DIFF_NOT_FINITE); return; }
   V3 px = rd.rxo + rd.rxd * tx;
   double ty = -(dot(si->n, rd.ryd) - d) / dot(si->n, rd.ryd);   // :234 reads ry_direction where pbrt reads ry_origin
-  if (std::isinf(ty) || std::isnan(ty)) return;
+  if (std::isinf(ty) || std::isnan(ty)) { tex_count(TC_DIFF_NOT_FINITE); return; }
   V3 py = rd.ryo + rd.ryd * ty;
   si->dpdx = px - si->p;
   si->dpdy = py - si->p;
@@ -1290,11 +1321,12 @@ void compute_differentials(SI* si, const RayDiff& rd) {
   if (std::fabs(si->n.x) > std::fabs(si->n.y) && std::fabs(si->n.x) > std::fabs(si->n.z)) { dim[0] = 1; dim[1] = 2; }
   else if (std::fabs(si->n.y) > std::fabs(si->n.z)) { dim[0] = 0; dim[1] = 2; }
   else { dim[0] = 0; dim[1] = 1; }
+  tex_count(dim[0] == 1 ? TC_DIFF_AXIS_YZ : (dim[1] == 2 ? TC_DIFF_AXIS_XZ : TC_DIFF_AXIS_XY));
   double a[2][2] = {{v3_at(si->dpdu, dim[0]), v3_at(si->dpdv, dim[0])}, {v3_at(si->dpdu, dim[1]), v3_at(si->dpdv, dim[1])}};
   double bx[2] = {v3_at(px, dim[0]) - v3_at(si->p, dim[0]), v3_at(px, dim[1]) - v3_at(si->p, dim[1])};
   double by[2] = {v3_at(py, dim[0]) - v3_at(si->p, dim[0]), v3_at(py, dim[1]) - v3_at(si->p, dim[1])};
-  if (!solve_2x2(a, bx, &si->dudx, &si->dvdx)) { si->dudx = 0.0; si->dvdx = 0.0; }
-  if (!solve_2x2(a, by, &si->dudy, &si->dvdy)) { si->dudy = 0.0; si->dvdy = 0.0; }
+  if (!solve_2x2(a, bx, &si->dudx, &si->dvdx)) { tex_count(TC_DIFF_SOLVE_FAILED); si->dudx = 0.0; si->dvdx = 0.0; }
+  if (!solve_2x2(a, by, &si->dudy, &si->dvdy)) { tex_count(TC_DIFF_SOLVE_FAILED); si->dudy = 0.0; si->dvdy = 0.0; }
 }
 
 // ---- textures (texture/*.rs) over the flat graph of rrt_scene_desc.textures ---------------------------------------
@@ -1329,6 +1361,9 @@ inline int f2i_sat(double v) {   // Rust `as i32`: saturating, NaN -> 0
 double noise_flt(double x, double y, double z) {   // :73-105
   int ix = f2i_sat(std::floor(x)), iy = f2i_sat(std::floor(y)), iz = f2i_sat(std::floor(z));
   double dx = x - (double)ix, dy = y - (double)iy, dz = z - (double)iz;
+  tex_count(TC_NOISE_CALLS);
+  if (ix < 0 || iy < 0 || iz < 0) tex_count(TC_NOISE_NEGATIVE_LATTICE);
+  if (std::fabs(x) >= 2147483648.0 || std::fabs(y) >= 2147483648.0 || std::fabs(z) >= 2147483648.0) tex_count(TC_NOISE_SATURATED);
   ix &= 255; iy &= 255; iz &= 255;
   double w000 = noise_grad(ix, iy, iz, dx, dy, dz), w100 = noise_grad(ix + 1, iy, iz, dx - 1.0, dy, dz);
   double w010 = noise_grad(ix, iy + 1, iz, dx, dy - 1.0, dz), w110 = noise_grad(ix + 1, iy + 1, iz, dx - 1.0, dy - 1.0, dz);
@@ -1340,10 +1375,17 @@ double noise_flt(double x, double y, double z) {   // :73-105
   return lerp_r(wz, y0, y1);
 }
 inline double smooth_step(double mn, double mx, double v) { double t = clampd((v - mn) / (mx - mn), 0.0, 1.0); return t * t * (-2.0 * t + 3.0); }
+inline void noise_sum_census(double n, int n_int, int max_octaves) {
+  tex_count(TC_NOISE_SUMS);
+  if (n_int == 0) tex_count(TC_NOISE_N_INT_0);
+  if (n > 0.0 && n < (double)max_octaves) tex_count(TC_NOISE_PARTIAL);
+  if (n == (double)max_octaves) tex_count(TC_NOISE_ALL_OCTAVES);
+}
 double tex_fbm(V3 p, V3 dpdx, V3 dpdy, double omega, int max_octaves) {   // fbm :138-153
   double l2 = rmax(len2(dpdx), len2(dpdy));
   double n = clampd(-1.0 - 0.5 * std::log2(l2), 0.0, (double)max_octaves);
   int n_int = f2i_sat(std::floor(n));
+  noise_sum_census(n, n_int, max_octaves);
   double sum = 0.0, lambda = 1.0, o = 1.0;
   for (int i = 0; i < n_int; i++) { V3 q = p * lambda; sum += o * noise_flt(q.x, q.y, q.z); lambda *= 1.99; o *= omega; }
   double n_partial = n - (double)n_int;
@@ -1355,6 +1397,7 @@ double tex_turbulence(V3 p, V3 dpdx, V3 dpdy, double omega, int max_octaves) {  
   double l2 = rmax(len2(dpdx), len2(dpdy));
   double n = clampd(-1.0 - 0.5 * std::log2(l2), 0.0, (double)max_octaves);
   int n_int = f2i_sat(std::floor(n));
+  noise_sum_census(n, n_int, max_octaves);
   double sum = 0.0, lambda = 1.0, o = 1.0;
   for (int i = 0; i < n_int; i++) { V3 q = p * lambda; sum += o * std::fabs(noise_flt(q.x, q.y, q.z)); lambda *= 1.99; o *= omega; }
   double n_partial = n - (double)n_int;
@@ -1369,11 +1412,15 @@ inline void map_sphere(const double* m, V3 p, double* s, double* t) {
   V3 v = vnormalize(xf_pt(m, p) - V3());
   double theta = std::acos(clampd(v.z, -1.0, 1.0));
   double phi = std::atan2(v.y, v.x);
-  if (phi < 0.0) phi += 2.0 * PI;
+  tex_count(TC_ROUND_CALLS);
+  if (theta < 0.05 || theta > PI - 0.05) tex_count(TC_ROUND_POLE);
+  if (phi < 0.0) { tex_count(TC_ROUND_PHI_WRAPPED); phi += 2.0 * PI; }
   *s = theta / PI; *t = phi / (PI * 2.0);
 }
 inline void map_cylinder(const double* m, V3 p, double* s, double* t) {
   V3 v = vnormalize(xf_pt(m, p) - V3());
+  tex_count(TC_ROUND_CALLS);
+  if (std::fabs(v.z) > std::cos(0.05)) tex_count(TC_ROUND_POLE);
   *s = (PI + std::atan2(v.y, v.x)) / (2.0 * PI); *t = v.z;
 }
 void tex_map_2d(const rrt_texture& t, const SI& si, double st[2], double dstdx[2], double dstdy[2]) {
@@ -1392,6 +1439,8 @@ void tex_map_2d(const rrt_texture& t, const SI& si, double st[2], double dstdx[2
       dstdx[0] = (sx[0] - st[0]) / delta; dstdx[1] = (sx[1] - st[1]) / delta;
       f(t.world_to_texture, si.p + si.dpdy * delta, &sy[0], &sy[1]);
       dstdy[0] = (sy[0] - st[0]) / delta; dstdy[1] = (sy[1] - st[1]) / delta;
+      if (dstdx[1] > 0.5) tex_count(TC_FOLD_DX_HIGH); else if (dstdx[1] < -0.5) tex_count(TC_FOLD_DX_LOW);
+      if (dstdy[1] > 0.5) tex_count(TC_FOLD_DY_HIGH); else if (dstdy[1] < -0.5) tex_count(TC_FOLD_DY_LOW);
       if (dstdx[1] > 0.5) dstdx[1] = 1.0 - dstdx[1]; else if (dstdx[1] < -0.5) dstdx[1] = -(dstdx[1] + 1.0);
       if (dstdy[1] > 0.5) dstdy[1] = 1.0 - dstdy[1]; else if (dstdy[1] < -0.5) dstdy[1] = -(dstdy[1] + 1.0);
       return;
@@ -1515,20 +1564,41 @@ struct OracleMip {
   }
 };
 
-Rgb tex_eval(const rrt_scene_desc* d, int id, const SI& si);
-inline Rgb tex_child(const rrt_scene_desc* d, const rrt_texture& t, int slot, const SI& si) {
-  return t.child[slot] >= 0 ? tex_eval(d, t.child[slot], si) : Rgb(t.fallback[slot]);
-}
+Rgb tex_eval(const rrt_scene_desc* d, int id, const SI& si, int level = 1);
+struct TexChild {   // the children of one node, evaluated one level below it
+  const rrt_scene_desc* d; const rrt_texture& t; const SI& si; int level;
+  Rgb operator()(int slot) const {
+    if (t.child[slot] >= 0) return tex_eval(d, t.child[slot], si, level + 1);
+    tex_count((t.type == RRT_TEX_MIX ? TC_FB_MIX_T1 : (t.type == RRT_TEX_SCALE ? TC_FB_SCALE_T1 : TC_FB_CHECKER_T1)) + slot);
+    return Rgb(t.fallback[slot]);
+  }
+};
 // Texture::evaluate of every in-scope texture; a float texture carries its value in all three channels
-Rgb tex_eval(const rrt_scene_desc* d, int id, const SI& si) {
+Rgb tex_eval(const rrt_scene_desc* d, int id, const SI& si, int level) {
   const rrt_texture& t = d->textures[id];
+  const TexChild child{d, t, si, level};
+  tex_count_max(TC_DEPTH_MAX, (uint64_t)level);
+  switch (t.type) {
+    case RRT_TEX_CONSTANT: tex_count(TC_NODE_CONSTANT); break;
+    case RRT_TEX_MIX: tex_count(TC_NODE_MIX); break;
+    case RRT_TEX_BILERP: tex_count(TC_NODE_BILERP); break;
+    case RRT_TEX_CHECKER2D: tex_count(TC_NODE_CHECKER2D); break;
+    case RRT_TEX_CHECKER3D: tex_count(TC_NODE_CHECKER3D); break;
+    case RRT_TEX_SCALE: tex_count(TC_NODE_SCALE); break;
+    case RRT_TEX_WINDY: tex_count(TC_NODE_WINDY); break;
+    case RRT_TEX_WRINKLED: tex_count(TC_NODE_WRINKLED); break;
+    case RRT_TEX_UV: tex_count(TC_NODE_UV); break;
+    case RRT_TEX_IMAGE: tex_count(TC_NODE_IMAGE); break;
+    default: break;
+  }
   switch (t.type) {
     case RRT_TEX_CONSTANT: return Rgb(t.v[0]);
     case RRT_TEX_MIX: {   // mix.rs:32-38
-      double amt = tex_child(d, t, 2, si).c[0];
-      return tex_child(d, t, 0, si) * (1.0 - amt) + tex_child(d, t, 1, si) * amt;
+      double amt = child(2).c[0];
+      if (amt < 0.0 || amt > 1.0) tex_count(TC_MIX_AMOUNT_OUTSIDE);
+      return child(0) * (1.0 - amt) + child(1) * amt;
     }
-    case RRT_TEX_SCALE: return tex_child(d, t, 0, si) * tex_child(d, t, 1, si);   // scale.rs:30-32
+    case RRT_TEX_SCALE: return child(0) * child(1);   // scale.rs:30-32
     case RRT_TEX_BILERP: {   // bilerp.rs:33-43
       double st[2], dx[2], dy[2];
       tex_map_2d(t, si, st, dx, dy);
@@ -1543,18 +1613,22 @@ Rgb tex_eval(const rrt_scene_desc* d, int id, const SI& si) {
       double st[2], dx[2], dy[2];
       tex_map_2d(t, si, st, dx, dy);
       bool first = (f2i_sat(std::floor(st[0])) + f2i_sat(std::floor(st[1]))) % 2 == 0;
-      if (t.aa_none) return tex_child(d, t, first ? 0 : 1, si);
+      if (f2i_sat(std::floor(st[0])) + f2i_sat(std::floor(st[1])) < 0) tex_count(TC_CHK_NEGATIVE_SUM);
+      if (t.aa_none) { tex_count(TC_CHK_AA_NONE); return child(first ? 0 : 1); }
       double ds = rmax(std::fabs(dx[0]), std::fabs(dx[1])), dt = rmax(std::fabs(dy[0]), std::fabs(dy[1]));
       double s0 = st[0] - ds, s1 = st[0] + ds, t0 = st[1] - dt, t1 = st[1] + dt;
-      if (std::floor(s0) == std::floor(s1) && std::floor(t0) == std::floor(t1)) return tex_child(d, t, first ? 0 : 1, si);
+      if (std::floor(s0) == std::floor(s1) && std::floor(t0) == std::floor(t1)) { tex_count(TC_CHK_SAME_CELL); return child(first ? 0 : 1); }
+      if (s0 < 0.0 || s1 < 0.0 || t0 < 0.0 || t1 < 0.0) tex_count(TC_CHK_BUMP_INT_NEGATIVE);
+      tex_count(ds > 1.0 || dt > 1.0 ? TC_CHK_HALF : TC_CHK_FILTERED);
       double sint = (bump_int(s1) - bump_int(s0)) / (2.0 * ds), tint = (bump_int(t1) - bump_int(t0)) / (2.0 * dt);
       double area2 = sint + tint - 2.0 * sint * tint;
       if (ds > 1.0 || dt > 1.0) area2 = 0.5;
-      return tex_child(d, t, 0, si) * (1.0 - area2) + tex_child(d, t, 1, si) * area2;
+      return child(0) * (1.0 - area2) + child(1) * area2;
     }
     case RRT_TEX_CHECKER3D: {   // checkerboard.rs:121-131
       V3 p = xf_pt(t.world_to_texture, si.p);
-      return tex_child(d, t, f2i_sat(std::floor(p.x) + std::floor(p.y) + std::floor(p.z)) % 2 == 0 ? 0 : 1, si);
+      if (f2i_sat(std::floor(p.x) + std::floor(p.y) + std::floor(p.z)) < 0) tex_count(TC_CHK3_NEGATIVE_SUM);
+      return child(f2i_sat(std::floor(p.x) + std::floor(p.y) + std::floor(p.z)) % 2 == 0 ? 0 : 1);
     }
     case RRT_TEX_WINDY: {   // windy.rs:15-23
       V3 p = xf_pt(t.world_to_texture, si.p), dpdx = xf_vec(t.world_to_texture, si.dpdx), dpdy = xf_vec(t.world_to_texture, si.dpdy);
@@ -1583,6 +1657,7 @@ rrt_material resolve_material(const rrt_scene_desc* d, const rrt_material& m0, c
   for (int k = 0; k < RRT_P_COUNT; k++) {
     if (m.tex[k] < 0) continue;
     Rgb v = tex_eval(d, m.tex[k], si);
+    if (v.c[0] < 0.0 || (dst3[k] && (v.c[1] < 0.0 || v.c[2] < 0.0))) tex_count(TC_MAT_NEGATIVE_VALUE);
     if (dst3[k]) { dst3[k][0] = v.c[0]; dst3[k][1] = v.c[1]; dst3[k][2] = v.c[2]; } else *dst1[k] = v.c[0];
   }
   return m;
@@ -1594,16 +1669,20 @@ rrt_material resolve_material(const rrt_scene_desc* d, const rrt_material& m0, c
 void bump_shading(const rrt_scene_desc* d, int tex, SI* si) {
   SI ev = *si;
   double du = std::fabs(si->dudx) * 0.5 + std::fabs(si->dudy);   // (as written at :26; pbrt halves the sum)
-  if (du == 0.0) du = 0.0005;
+  tex_count(TC_BUMP_CALLS);
+  const bool du_fallback = du == 0.0;
+  if (du == 0.0) { tex_count(TC_BUMP_DU_FALLBACK); du = 0.0005; }
   ev.p = si->p + si->sdpdu * du;
   ev.u = si->u + du; ev.v = si->v;
   const double u_displace = tex_eval(d, tex, ev).c[0];
   double dv = (std::fabs(si->dvdx) + std::fabs(si->dvdy)) * 0.5;
-  if (dv == 0.0) dv = 0.0005;
+  if (dv == 0.0) { tex_count(TC_BUMP_DV_FALLBACK); dv = 0.0005; }
   ev.p = si->p + si->sdpdv * dv;
   ev.u = si->u; ev.v = si->v + dv;
   const double v_displace = tex_eval(d, tex, ev).c[0];
   const double displace = tex_eval(d, tex, *si).c[0];
+  if (u_displace != displace || v_displace != displace) tex_count(TC_BUMP_SLOPE);
+  if (du_fallback && u_displace != displace) tex_count(TC_BUMP_FALLBACK_SLOPE);
   V3 dpdu = si->sdpdu + si->sn * (u_displace - displace) / du + si->sdndu * displace;
   V3 dpdv = si->sdpdv + si->sn * (v_displace - displace) / dv + si->sdndv * displace;
   si_set_shading(si, dpdu, dpdv, si->sdndu, si->sdndv, false);
@@ -2252,6 +2331,11 @@ int oracle_texture_eval(const rrt_scene_desc* d, int32_t tex, const double* si15
 void oracle_mip_census(uint64_t* out, int reset) {
   for (int k = 0; k < MC_COUNT; k++)
     out[k] = reset ? g_mip_census[k].exchange(0, std::memory_order_relaxed) : g_mip_census[k].load(std::memory_order_relaxed);
+}
+// The texture census since the last reset (process-wide; TexCensus order, tests/oracle_lib.py TEX_CENSUS names the counters)
+void oracle_tex_census(uint64_t* out, int reset) {
+  for (int k = 0; k < TC_COUNT; k++)
+    out[k] = reset ? g_tex_census[k].exchange(0, std::memory_order_relaxed) : g_tex_census[k].load(std::memory_order_relaxed);
 }
 // The BSDF branch census since the last reset (process-wide; BsdfCensus order, tests/oracle_lib.py BSDF_CENSUS names the counters)
 void oracle_bsdf_census(uint64_t* out, int reset) {

@@ -301,6 +301,26 @@ void xf_pt(const double* m, const double* p, double* o) {
 void xf_nrm(const double* mi, const double* n, double* o) {
   for (int r = 0; r < 3; r++) o[r] = mi[0 * 4 + r] * n[0] + mi[1 * 4 + r] * n[1] + mi[2 * 4 + r] * n[2];
 }
+// A triangle whose vt give `determinant.abs() < 1e-8` (triangle.rs:300-316) takes dpdu / dpdv, and with vertex normals dndu / dndv (:351-386), from
+// coordinate_system() of an OBJECT-space vector, and TransformedPrimitive rotates the result. coordinate_system() does not commute with a rotation,
+// so such a triangle is not flattened: in world space it would get another frame, and every filtered texture and bump map on it other footprints
+// (tests/texture_shapes.py axes-walls, bump-ramp-uvmesh-vn). Tested as the kernel tests it, in the mode's precision, and in f64. It holds whatever the
+// triangle's material is, and the kept path transforms the ray per triangle test: a mesh whose vt are all degenerate goes onto it whole.
+template <typename R>
+bool uv_degenerate(const rrt_scene_desc* d, const rrt_tri& t) {
+  if (!t.mesh_has_uv) return false;
+  double uv[3][2];
+  for (int k = 0; k < 3; k++) { uv[k][0] = d->uvs[2 * (size_t)t.uv[k]]; uv[k][1] = d->uvs[2 * (size_t)t.uv[k] + 1]; }
+  const double det = (uv[0][0] - uv[2][0]) * (uv[1][1] - uv[2][1]) - (uv[0][1] - uv[2][1]) * (uv[1][0] - uv[2][0]);
+  const R r[3][2] = {{(R)uv[0][0], (R)uv[0][1]}, {(R)uv[1][0], (R)uv[1][1]}, {(R)uv[2][0], (R)uv[2][1]}};
+  // the kernel's a * b - c * d may be contracted to an FMA either way round: all three roundings are tried, and a triangle that any of them calls
+  // degenerate is kept (keeping one that the kernel then finds regular costs time, not correctness)
+  const R a = r[0][0] - r[2][0], b = r[1][1] - r[2][1], c = r[0][1] - r[2][1], e = r[1][0] - r[2][0];
+  const R det_r[3] = {a * b - c * e, (R)std::fma(a, b, -(c * e)), (R)std::fma(-c, e, a * b)};
+  if (std::fabs(det) < 1e-8) return true;
+  for (int k = 0; k < 3; k++) if (std::fabs((double)det_r[k]) < 1e-8) return true;
+  return false;
+}
 }  // namespace
 
 template <typename R>
@@ -373,7 +393,7 @@ FlatScene<R> flatten_scene(const rrt_scene_desc* d, double slab_pad_ulps) {
     bool kept = false;   // non-rigid instance: not flattened, the ray is transformed per test like the reference does (Q15)
     if (pr.instance >= 0) {
       m = d->xforms[pr.instance].m; mi = d->xforms[pr.instance].m_inv;
-      if (keep_all || !is_rigid(m)) {
+      if (keep_all || !is_rigid(m) || uv_degenerate<R>(d, t)) {
         auto it = inst_of.find(pr.instance);
         if (it == inst_of.end()) {
           InstDev<R> I{};

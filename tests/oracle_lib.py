@@ -37,6 +37,8 @@ def lib():
         L.oracle_mip_census.argtypes = [C.c_void_p, C.c_int]
         L.oracle_bsdf_census.restype = None
         L.oracle_bsdf_census.argtypes = [C.c_void_p, C.c_int]
+        L.oracle_tex_census.restype = None
+        L.oracle_tex_census.argtypes = [C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -191,6 +193,36 @@ def bsdf_census(reset=True):
     out = (C.c_uint64 * len(BSDF_CENSUS))()
     lib().oracle_bsdf_census(out, 1 if reset else 0)
     return dict(zip(BSDF_CENSUS, (int(v) for v in out)))
+
+
+TEX_CENSUS = ("node_constant", "node_mix", "node_bilerp", "node_checker2d", "node_checker3d", "node_scale", "node_windy", "node_wrinkled", "node_uv",
+              "node_image", "depth_max",
+              "fb_mix_t1", "fb_mix_t2", "fb_mix_amount", "fb_scale_t1", "fb_scale_t2", "fb_checker_t1", "fb_checker_t2",
+              "chk_aa_none", "chk_same_cell", "chk_filtered", "chk_half", "chk_negative_sum", "chk_bump_int_negative", "chk3_negative_sum",
+              "round_calls", "round_phi_wrapped", "fold_dx_high", "fold_dx_low", "fold_dy_high", "fold_dy_low", "round_pole",
+              "noise_sums", "noise_n_int_0", "noise_partial", "noise_all_octaves", "noise_calls", "noise_negative_lattice", "noise_saturated",
+              "diff_calls", "diff_no_aux", "diff_not_finite", "diff_axis_yz", "diff_axis_xz", "diff_axis_xy", "diff_solve_failed",
+              "bump_calls", "bump_du_fallback", "bump_dv_fallback", "bump_slope", "bump_fallback_slope",
+              "tri_hits", "tri_degenerate_uv", "tri_negative_det", "tri_coord_dn",
+              "mix_amount_outside", "mat_negative_value")
+
+
+def tex_census(reset=True):
+    """What the oracle's texture code did since the last reset (TexCensus in rrt_oracle.cpp), process-wide: nodes evaluated per type and the deepest
+    level reached (depth_max: a maximum, the root is level 1); fallback constants used per type and slot (a 3D checkerboard counts with the 2D one); 2D
+    checkerboard evaluations that returned at aamode none, at "same cell", from the bump_int expression (filtered) and from the area2 = 0.5 shortcut
+    (half), those whose cell sum floor(s) + floor(t) is negative and those whose bump_int saw a negative argument; 3D checkerboard evaluations with a
+    negative cell sum; sphere() / cylinder() calls (three per mapping), those with phi < 0 wrapped, those within 0.05 rad of a pole, and the folds of
+    dst[1] > 0.5 / < -0.5 for dstdx and dstdy; fbm / turbulence calls (noise_sums) with n_int == 0, with 0 < n < octaves and with n == octaves,
+    noise() calls, those with a negative lattice coordinate and those with a coordinate past 2^31 (a saturated cast); compute_differentials calls,
+    those without an auxiliary ray, with tx or ty not finite, per dominant-axis branch (the pair of axes kept) and solve_2x2 failures (two solves per
+    call); Material::bump calls, its du / dv == 0 fallbacks, the calls whose
+    displaced evaluations differ from the one at the hit (bump_slope: a finite difference that is not 0) and those of them on the du fallback; successful triangle intersection tests (every candidate the traversal accepts, not
+    only the closest), those with a degenerate uv, with a negative uv determinant, and with dndu / dndv from coordinate_system(dn); Mix amounts
+    outside [0, 1]; texture values with a negative channel handed to a material parameter. Call it once to reset, render, call it again to read."""
+    out = (C.c_uint64 * len(TEX_CENSUS))()
+    lib().oracle_tex_census(out, 1 if reset else 0)
+    return dict(zip(TEX_CENSUS, (int(v) for v in out)))
 
 
 def surface_differentials(n, p, dpdu, dpdv, rxo, rxd, ryo, ryd):
