@@ -1805,9 +1805,18 @@ void compute_scattering(const Scene& sc, SI& si, const RayDiff& rd, Bsdf* bsdf, 
 // ---- lights (lights/point.rs, lights/diffuse.rs, shape/mod.rs sample_ref/pdf_ref) ----------------------
 struct LightSample { Rgb li; V3 wi; double pdf = 0; V3 p1, n1; bool have_vis = false; };
 
+// Light census (oracle_light_census): which branch of the light code below every call took and which light the two choosers chose, so that a test
+// frame can be shown to reach the branch it is for (tests/light_shapes.py). Relaxed atomic counters, as the BSDF census: they count and nothing else.
+enum LightCensus { LC_POINT, LC_DISTANT, LC_SPHERE_EMITTER, LC_TRI_EMITTER, LC_TRI_NORMALS_KEPT, LC_TRI_NORMALS_FLIPPED, LC_TRI_NORMALS_MODE2,
+                   LC_LI_BLACK, LC_PDF_ZERO, LC_PDF_NOT_POSITIVE, LC_EMITTER_BACKFACE, LC_F_BLACK, LC_OCCLUDED, LC_UNOCCLUDED,
+                   LC_CHOOSE_DISTRIB, LC_CHOOSE_PLAIN, LC_CHOICE_CLAMPED, LC_CHOICE_BOUNDARY, LC_CHOSEN_FIRST, LC_CHOSEN_LAST = LC_CHOSEN_FIRST + 31, LC_COUNT };
+std::atomic<uint64_t> g_light_census[LC_COUNT];
+inline void light_count(int k) { g_light_census[k].fetch_add(1, std::memory_order_relaxed); }
+
 // Shape::sample for the two light shapes
 void shape_sample(const Scene& sc, const rrt_light& L, double u0, double u1, V3* p, V3* n, double* pdf) {
   if (L.shape_type == RRT_PRIM_SPHERE) {  // Sphere::sample sphere.rs:265-285
+    light_count(LC_SPHERE_EMITTER);
     SphereRef S = sphere_ref(sc, L.shape);
     V3 p_obj = V3() + uniform_sample_sphere(u0, u1) * S.s->radius;
     *n = nnormalize(xf_nrm(S.mi, V3(p_obj.x, p_obj.y, p_obj.z)));
@@ -1815,6 +1824,7 @@ void shape_sample(const Scene& sc, const rrt_light& L, double u0, double u1, V3*
     *p = xf_pt(S.m, p_obj);
     *pdf = 1.0 / L.area;
   } else {                                // Triangle::sample triangle.rs:393-418 (Q19)
+    light_count(LC_TRI_EMITTER);
     const rrt_tri& t = sc.d->tris[L.shape];
     V3 b = uniform_sample_sphere(u0, u1);
     V3 p0 = sc.P(t.v[0]), p1 = sc.P(t.v[1]), p2 = sc.P(t.v[2]);
@@ -1822,6 +1832,8 @@ void shape_sample(const Scene& sc, const rrt_light& L, double u0, double u1, V3*
     *n = vnormalize(cross(p1 - p0, p2 - p0));
     if (t.mesh_has_n) {  // `!self.mesh.n.is_empty()` (2 = normals present but no indices: n = [0,0,0])
       V3 ns = sc.N(t.n[0]) * b.x + sc.N(t.n[1]) * b.y + sc.N(t.n[2]) * b.z;
+      if (t.mesh_has_n == 2) light_count(LC_TRI_NORMALS_MODE2);
+      light_count(dot(*n, ns) < 0.0 ? LC_TRI_NORMALS_FLIPPED : LC_TRI_NORMALS_KEPT);
       *n = faceforward(*n, ns);
     }
     *pdf = 1.0 / tri_area(sc, t);
@@ -1845,6 +1857,7 @@ double shape_pdf_ref(const Scene& sc, const rrt_light& L, V3 ref_p, V3 wi) {
 LightSample light_sample_li(const Scene& sc, const rrt_light& L, V3 ref_p, double u0, double u1) {
   LightSample s;
   if (L.type == RRT_LIGHT_POINT) {  // point.rs:55-77
+    light_count(LC_POINT);
     V3 pl(L.p_light[0], L.p_light[1], L.p_light[2]);
     s.wi = vnormalize(pl - ref_p);
     s.pdf = 1.0;
@@ -1853,6 +1866,7 @@ LightSample light_sample_li(const Scene& sc, const rrt_light& L, V3 ref_p, doubl
     return s;
   }
   if (L.type == RRT_LIGHT_DISTANT) {  // distant.rs:67-92: wi = w_light, pdf = 1, p1 = p + w_light * 2 * world_radius
+    light_count(LC_DISTANT);
     V3 w(L.w_light[0], L.w_light[1], L.w_light[2]);
     s.wi = w;
     s.pdf = 1.0;
@@ -1876,6 +1890,7 @@ LightSample light_sample_li(const Scene& sc, const rrt_light& L, V3 ref_p, doubl
   if (pdf == 0.0 || len2(p - ref_p) == 0.0) { s.pdf = 0.0; s.li = Rgb(); return s; }
   s.wi = vnormalize(p - ref_p);
   s.p1 = p; s.n1 = n; s.have_vis = true;
+  if (dot(n, -s.wi) <= 0.0) light_count(LC_EMITTER_BACKFACE);
   s.li = (dot(n, -s.wi) > 0.0) ? Rgb(L.spectrum) : Rgb();  // AreaLight::l diffuse.rs:133-141
   return s;
 }
@@ -1908,15 +1923,19 @@ Rgb estimate_direct(const Scene& sc, const SI& si, const Bsdf& bsdf, double us0,
   light_pdf = ls.pdf;
   Rgb li = ls.li;
   V3 wi = ls.wi;
+  if (light_pdf == 0.0) light_count(LC_PDF_ZERO);
+  else if (!(light_pdf > 0.0)) light_count(LC_PDF_NOT_POSITIVE);   // a NaN pdf
+  else if (li.is_black()) light_count(LC_LI_BLACK);
   if (light_pdf > 0.0 && !li.is_black()) {
     Rgb f;
     if (bsdf.present) {
       f = bsdf.f(si.wo, wi, flags) * absdot(wi, si.sn);
       scattering_pdf = bsdf.pdf(si.wo, wi, flags);
     }
-    if (f.is_black()) bsdf_count(BC_DIRECT_F_BLACK);
+    if (f.is_black()) { bsdf_count(BC_DIRECT_F_BLACK); light_count(LC_F_BLACK); }
     if (!f.is_black()) {
       if (!unoccluded(sc, si.p, si.n, ls.p1, ls.n1, cnt)) li = Rgb();
+      light_count(li.is_black() ? LC_OCCLUDED : LC_UNOCCLUDED);
       if (!li.is_black()) {
         if (is_delta_light(L)) ld = ld + f * li / light_pdf;
         else { double w = power_heuristic(1, light_pdf, 1, scattering_pdf); ld = ld + li * f * w / light_pdf; }
@@ -1970,7 +1989,9 @@ struct UniformLightDistrib {
     }
     // `clamp_t(first - 1, 0, len-2)` on usize: first >= 1 because cdf[0] = 0 <= u for u >= 0
     size_t off = first - 1;
-    if (off > cdf.size() - 2) off = cdf.size() - 2;
+    if (off > cdf.size() - 2) { off = cdf.size() - 2; light_count(LC_CHOICE_CLAMPED); }
+    // (census: u within 2^-23 of an inner cdf entry - a sample that an fp32 rounding of u or of the cdf can hand to the neighbouring light)
+    if ((off > 0 && u - cdf[off] <= 0x1p-23) || (off + 2 < cdf.size() && cdf[off + 1] - u <= 0x1p-23)) light_count(LC_CHOICE_BOUNDARY);
     *pdf = func_int > 0.0 ? 1.0 / (func_int * (double)n) : 0.0;
     return off;
   }
@@ -1983,14 +2004,22 @@ Rgb uniform_sample_one_light(const Scene& sc, const SI& si, const Bsdf& bsdf, Sa
   size_t light_num;
   double light_pdf = 0.0;
   if (distrib) {
+    light_count(LC_CHOOSE_DISTRIB);
     light_num = distrib->sample_discrete(smp.get_1d(), &light_pdf);
     if (light_pdf == 0.0) return Rgb();
   } else {
     double v = smp.get_1d() * (double)n_lights;
     size_t vi = (v != v || v <= 0.0) ? 0 : (size_t)v;
+    light_count(LC_CHOOSE_PLAIN);
+    if (vi > n_lights - 1) light_count(LC_CHOICE_CLAMPED);
+    { // (census: the same boundary test on v = u * n, where the device multiplies in fp32)
+      const double k = std::floor(v + 0.5);
+      if (k > 0.0 && k < (double)n_lights && std::fabs(v - k) <= (double)n_lights * 0x1p-23) light_count(LC_CHOICE_BOUNDARY);
+    }
     light_num = std::min(vi, n_lights - 1);
     light_pdf = 1.0 / (double)n_lights;
   }
+  light_count(LC_CHOSEN_FIRST + (int)std::min<size_t>(light_num, 31));
   double ul0, ul1, us0, us1;
   smp.get_2d(&ul0, &ul1);
   smp.get_2d(&us0, &us1);
@@ -2341,6 +2370,23 @@ void oracle_tex_census(uint64_t* out, int reset) {
 void oracle_bsdf_census(uint64_t* out, int reset) {
   for (int k = 0; k < BC_COUNT; k++)
     out[k] = reset ? g_bsdf_census[k].exchange(0, std::memory_order_relaxed) : g_bsdf_census[k].load(std::memory_order_relaxed);
+}
+// The light census since the last reset (process-wide; LightCensus order, tests/oracle_lib.py LIGHT_CENSUS names the counters)
+void oracle_light_census(uint64_t* out, int reset) {
+  for (int k = 0; k < LC_COUNT; k++)
+    out[k] = reset ? g_light_census[k].exchange(0, std::memory_order_relaxed) : g_light_census[k].load(std::memory_order_relaxed);
+}
+// Light::sample_li of lights[light] for the reference point ref_p: out13 = {li.rgb, wi.xyz, pdf, p1.xyz, n1.xyz} (p1 / n1: the far end of the
+// visibility tester; all zero where sample_li returns before it makes one)
+int oracle_light_sample(const rrt_scene_desc* d, uint32_t light, const double* ref_p, double u0, double u1, double* out13) {
+  return guarded([&]() {
+    if ((size_t)light >= d->n_lights) throw OraclePanic{"oracle_light_sample: light index out of range"};
+    Scene sc{d, false};
+    LightSample s = light_sample_li(sc, d->lights[light], V3(ref_p[0], ref_p[1], ref_p[2]), u0, u1);
+    out13[0] = s.li.c[0]; out13[1] = s.li.c[1]; out13[2] = s.li.c[2];
+    out13[3] = s.wi.x; out13[4] = s.wi.y; out13[5] = s.wi.z; out13[6] = s.pdf;
+    out13[7] = s.p1.x; out13[8] = s.p1.y; out13[9] = s.p1.z; out13[10] = s.n1.x; out13[11] = s.n1.y; out13[12] = s.n1.z;
+  });
 }
 // SurfaceInteraction::compute_differentials: in24 = {n, p, dpdu, dpdv, rx_origin, rx_direction, ry_origin, ry_direction},
 // out10 = {dpdx.xyz, dpdy.xyz, dudx, dvdx, dudy, dvdy}

@@ -926,46 +926,6 @@ RRT_DEV Rgb<R> light_sample_li(const Light<R>& L, V3<R> ref_p, R u0, R u1, V3<R>
   return (dot(n, -*wi) > R(0)) ? Rgb<R>(L.spectrum) : Rgb<R>();  // DiffuseAreaLight::l diffuse.rs:133-141
 }
 
-// Sphere::intersect (sphere.rs:124-259) reduced to what Shape::pdf_ref (shape/mod.rs:49-66) reads: hit point
-// and ist.n. Only needed for the MIS weight of area lights.
-template <typename R>
-RRT_DEV bool sphere_hit_for_pdf(const Light<R>& L, V3<R> ro, V3<R> rd, V3<R>* p_world, V3<R>* n_world) {
-  V3<R> oo = aff_pt(L.mi, ro), od = vnormalize(vnormalize(aff_vec(L.mi, rd)));
-  R a = od.x * od.x + od.y * od.y + od.z * od.z;
-  R b = R(2) * (od.x * oo.x + od.y * oo.y + od.z * oo.z);
-  R c = oo.x * oo.x + oo.y * oo.y + oo.z * oo.z - L.radius * L.radius;
-  R t0, t1;
-  if (!quadratic(a, b, c, &t0, &t1)) return false;
-  if (t0 > R(1999999999.0) || t1 <= R(0)) return false;
-  R th = t0;
-  if (t0 <= R(0)) { th = t1; if (th > R(1999999999.0)) return false; }
-  V3<R> ph = ro + rd * th;  // world ray (Q16)
-  if (ph.x == R(0) && ph.y == R(0)) ph.x = R(1e-5) * L.radius;
-  R phi = atan2(ph.y, ph.x);
-  if (phi < R(0)) phi += R(2) * R(RRT_PI);
-  if ((L.z_min > -L.radius && ph.z < L.z_min) || (L.z_max < L.radius && ph.z > L.z_max) || (phi > L.phi_max)) {
-    if (th == t1) return false;
-    if (t1 > R(1999999999.0)) return false;
-    th = t1;
-    ph = oo + od * th;
-    ph = ph * (L.radius / len(ph));
-    if (ph.x == R(0) && ph.y == R(0)) ph.x = R(1e-5) * L.radius;
-    phi = atan2(ph.y, ph.x);
-    if (phi < R(0)) phi += R(2) * R(RRT_PI);
-    if ((L.z_min > -L.radius && ph.z < L.z_min) || (L.z_max < L.radius && ph.z > L.z_max) || (phi > L.phi_max)) return false;
-  }
-  R theta = acos(clampr(ph.z / L.radius, R(-1), R(1)));
-  R z_radius = sqrt(ph.x * ph.x + ph.y * ph.y);
-  R inv_zr = R(1) / z_radius;
-  R cphi = ph.x * inv_zr, sphi = ph.y * inv_zr;
-  V3<R> dpdu(-L.phi_max * ph.y, L.phi_max * ph.x, R(0));
-  V3<R> dpdv = V3<R>(ph.z * cphi, ph.z * sphi, -L.radius * R(sin(theta))) * (L.theta_max - L.theta_min);
-  V3<R> n = vnormalize(cross(dpdu, dpdv));
-  *p_world = aff_pt(L.m, ph);
-  *n_world = aff_nrm(L.mi, n);
-  return true;
-}
-
 // estimate_direct's light-sampling half (integrator/mod.rs:403-481), handle_media = false, specular = false.
 // Returns true and fills the shadow ray + contribution when a visibility test is needed.
 // The BSDF-sampling half (:483-556) can only add `li * f * weight / pdf` with li = 0 (no primitive carries an

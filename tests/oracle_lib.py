@@ -39,6 +39,10 @@ def lib():
         L.oracle_bsdf_census.argtypes = [C.c_void_p, C.c_int]
         L.oracle_tex_census.restype = None
         L.oracle_tex_census.argtypes = [C.c_void_p, C.c_int]
+        L.oracle_light_census.restype = None
+        L.oracle_light_census.argtypes = [C.c_void_p, C.c_int]
+        L.oracle_light_sample.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        L.oracle_light_sample.restype = C.c_int
         _lib = L
     return _lib
 
@@ -223,6 +227,36 @@ def tex_census(reset=True):
     out = (C.c_uint64 * len(TEX_CENSUS))()
     lib().oracle_tex_census(out, 1 if reset else 0)
     return dict(zip(TEX_CENSUS, (int(v) for v in out)))
+
+
+LIGHT_CENSUS = ("point", "distant", "sphere_emitter", "tri_emitter", "tri_normals_kept", "tri_normals_flipped", "tri_normals_mode2",
+                "li_black", "pdf_zero", "pdf_not_positive", "emitter_backface", "f_black", "occluded", "unoccluded",
+                "choose_distrib", "choose_plain", "choice_clamped", "choice_boundary")
+LIGHT_CHOSEN = 32
+
+
+def light_census(reset=True):
+    """What the oracle's light code did since the last reset (LightCensus in rrt_oracle.cpp), process-wide: Light::sample_li calls per kind (point, distant,
+    and Shape::sample of a sphere and of a triangle emitter); triangle emitters with vertex normals whose faceforward kept and turned the geometric
+    normal, and those of a mesh with `vn` lines and no normal indices (mode 2; they count as kept or flipped too); estimate_direct calls whose light
+    sample had pdf > 0 and a black li, pdf == 0, a pdf that is neither (NaN); area-light samples with dot(n, -wi) <= 0; estimate_direct calls that
+    returned on a black f, whose shadow ray was occluded and was not; uniform_sample_one_light calls that chose by the light distribution (Path) and by
+    v * n_lights (DirectLighting `one`), those of either whose index had to be clamped to the last light, and those whose sample lies within 2^-23 of an inner entry of the light
+    cdf (v = u * n_lights within n_lights * 2^-23 of an inner integer): the choices an fp32 rounding can hand to the neighbouring light. `chosen` is the list of how often each
+    light index was chosen (indices past 31 count as 31). Call it once to reset, render, call it again to read."""
+    out = (C.c_uint64 * (len(LIGHT_CENSUS) + LIGHT_CHOSEN))()
+    lib().oracle_light_census(out, 1 if reset else 0)
+    n = dict(zip(LIGHT_CENSUS, (int(v) for v in out)))
+    n["chosen"] = [int(v) for v in out[len(LIGHT_CENSUS):]]
+    return n
+
+
+def light_sample(scene, light, ref_p, u0=0.5, u1=0.5):
+    """Light::sample_li of scene.desc.lights[light] for the reference point ref_p: dict(li, wi, pdf, p1, n1); p1 / n1 are the far end of the visibility tester."""
+    ref_p = np.ascontiguousarray(ref_p, np.float64)
+    out = np.zeros(13)
+    _check(lib().oracle_light_sample(_d(scene), light, ref_p.ctypes.data, u0, u1, out.ctypes.data))
+    return dict(li=out[0:3].copy(), wi=out[3:6].copy(), pdf=out[6], p1=out[7:10].copy(), n1=out[10:13].copy())
 
 
 def surface_differentials(n, p, dpdu, dpdv, rxo, rxd, ryo, ryd):
