@@ -2037,6 +2037,33 @@ Rgb uniform_sample_all_lights(const Scene& sc, const SI& si, const Bsdf& bsdf, S
   return l;
 }
 
+// Path census (oracle_path_census): what the three integrator loops below did with every camera sample - how a path ended and at which bounce, which
+// vertices drew for next-event estimation, what Russian roulette tested, drew and decided, how deep the DirectLighting / Debug recursion went - so that
+// a test frame can be shown to reach the loop state it is for (tests/path_shapes.py). Relaxed atomic counters, as the light census: they count and
+// nothing else. PC_DIM_MAX and PC_LEVEL_MAX are maxima; the histograms have bins 0 .. 64 and an overflow bin.
+constexpr int kPathBins = 66;
+enum PathCensus { PC_STARTED, PC_END_ESCAPED, PC_END_DEPTH, PC_END_BLACK_F, PC_END_PDF_ZERO, PC_END_ROULETTE,
+                  PC_VERTEX_NEE, PC_VERTEX_SPECULAR_ONLY, PC_VERTEX_NO_LIGHTS,
+                  PC_RR_TESTS, PC_RR_DRAWS, PC_RR_FLOOR, PC_RR_SURVIVORS, PC_RR_ETA_DECIDED, PC_ETA_ENTER, PC_ETA_LEAVE, PC_DIM_MAX,
+                  PC_RR_DRAW_NEAR, PC_RR_TEST_NEAR,
+                  PC_LI_CALLS, PC_REFLECT_TAKEN, PC_TRANSMIT_TAKEN, PC_RECURSION_REFUSED, PC_LEVEL_MAX,
+                  PC_HIST_ENDS, PC_HIST_LI = PC_HIST_ENDS + 5 * kPathBins, PC_COUNT = PC_HIST_LI + kPathBins };
+std::atomic<uint64_t> g_path_census[PC_COUNT];
+inline void path_count(int k) { g_path_census[k].fetch_add(1, std::memory_order_relaxed); }
+inline void path_max(int k, uint64_t v) {
+  uint64_t cur = g_path_census[k].load(std::memory_order_relaxed);
+  while (cur < v && !g_path_census[k].compare_exchange_weak(cur, v, std::memory_order_relaxed)) {}
+}
+// a path's end: `cause` is one of PC_END_*, `bounce` the value of `bounces` when the loop was left
+inline void path_end(int cause, long bounce) {
+  path_count(cause);
+  path_count(PC_HIST_ENDS + (cause - PC_END_ESCAPED) * kPathBins + (int)std::min<long>(bounce, kPathBins - 1));
+}
+inline bool has_specular_lobe(const Bsdf& bsdf) {
+  for (int i = 0; i < bsdf.n; i++) if (bsdf.lobes[i].type & BXDF_SPECULAR) return true;
+  return false;
+}
+
 struct Integ {
   const Scene& sc;
   const rrt_integrator& in;
@@ -2049,25 +2076,29 @@ struct Integ {
     bool specular_bounce = false;
     long bounces = 0;
     double eta_scale = 1.0;
+    path_count(PC_STARTED);
     while (true) {
       SI isect;
       bool found = scene_intersect(sc, &ray, &isect, nullptr, cnt);
       if (bounces >= (long)in.max_depth) bsdf_count(BC_PATH_LAST_QUERY);   // the query whose hit only emission would read (path.rs:77,91)
+      if (bounces >= (long)in.max_depth) path_end(PC_END_DEPTH, bounces); else if (!found) path_end(PC_END_ESCAPED, bounces);
       // isect.le() is 0 (no area-light primitives, Q18); infinite_lights is empty on supported scenes
       (void)specular_bounce;
       if (!found || bounces >= (long)in.max_depth) break;
       Bsdf bsdf;
       compute_scattering(sc, isect, rdiff, &bsdf);
       if (bsdf.num_components(BXDF_ALL & ~BXDF_SPECULAR) > 0) {
+        path_count(sc.d->n_lights > 0 ? PC_VERTEX_NEE : PC_VERTEX_NO_LIGHTS);
         Rgb ld = beta * uniform_sample_one_light(sc, isect, bsdf, smp, &distrib, cnt);
         l = l + ld;
-      }
+      } else path_count(PC_VERTEX_SPECULAR_ONLY);
       V3 wo = -ray.d, wi;
       double pdf = 0.0, u0, u1;
       uint8_t flags = 0;
       smp.get_2d(&u0, &u1);
       Rgb f = bsdf.sample_f(wo, &wi, u0, u1, &pdf, BXDF_ALL, &flags);
-      if (f.is_black() || pdf == 0.0) break;
+      path_max(PC_DIM_MAX, smp.dimension);
+      if (f.is_black() || pdf == 0.0) { path_end(f.is_black() ? PC_END_BLACK_F : PC_END_PDF_ZERO, bounces); break; }
       beta = beta * (f * absdot(wi, isect.sn) / pdf);
       if (!(beta.y() > 0.0)) throw OraclePanic{"path.rs:146 assert!(beta.y() > 0.0)"};
       if (!std::isfinite(beta.y())) throw OraclePanic{"path.rs:147 assert!(beta.y().is_finite())"};
@@ -2075,13 +2106,25 @@ struct Integ {
       if ((flags & BXDF_SPECULAR) && (flags & BXDF_TRANSMISSION)) {   // path.rs:150-162
         double eta = bsdf.eta;
         eta_scale *= (dot(wo, isect.n) > 0.0) ? eta * eta : 1.0 / (eta * eta);
+        path_count(dot(wo, isect.n) > 0.0 ? PC_ETA_ENTER : PC_ETA_LEAVE);
       }
       ray = ray_new(isect.p, wi, INF);  // spawn_ray: no origin offset (Q8)
       rdiff = RayDiff();                // `.into()`: has_differentials = false (path.rs:163)
       Rgb rr_beta = beta * eta_scale;
+      if (bounces > 3) {   // (census only: what the test below compares)
+        path_count(PC_RR_TESTS);
+        if ((beta.max_component() < in.rr_threshold) != (rr_beta.max_component() < in.rr_threshold)) path_count(PC_RR_ETA_DECIDED);
+        if (std::fabs(rr_beta.max_component() - in.rr_threshold) < 0x1p-20 * std::fabs(in.rr_threshold)) path_count(PC_RR_TEST_NEAR);
+      }
       if (rr_beta.max_component() < in.rr_threshold && bounces > 3) {
         double q = rmax(1.0 - rr_beta.max_component(), 0.05);
-        if (smp.get_1d() < q) break;
+        const double u_rr = smp.get_1d();
+        path_count(PC_RR_DRAWS);
+        path_max(PC_DIM_MAX, smp.dimension);
+        if (1.0 - rr_beta.max_component() < 0.05) path_count(PC_RR_FLOOR);
+        if (std::fabs(u_rr - q) < 0x1p-20) path_count(PC_RR_DRAW_NEAR);
+        if (u_rr < q) { path_end(PC_END_ROULETTE, bounces); break; }
+        path_count(PC_RR_SURVIVORS);
         beta = beta / (1.0 - q);
         if (!std::isfinite(beta.y())) throw OraclePanic{"path.rs:220 assert!(beta.y().is_finite())"};
       }
@@ -2117,6 +2160,7 @@ struct Integ {
           cd.rxd = wi - dwodx + (dndx * dot(wo, ns) + ns * ddndx) * 0.2;
           cd.ryd = wi - dwody + (dndy * dot(wo, ns) + ns * ddndy) * 0.2;
         }
+        path_count(PC_REFLECT_TAKEN);
         out = out + f * li(rd, cd, depth + 1) * absdot(wi, ns) / pdf;
       }
     }
@@ -2147,6 +2191,7 @@ struct Integ {
           cd.rxd = wi - dwodx * eta + (dndx * mu + ns * dmudx);
           cd.ryd = wi - dwody * eta + (dndy * mu + ns * dmudy);
         }
+        path_count(PC_TRANSMIT_TAKEN);
         out = out + f * li(rd, cd, depth + 1) * absdot(wi, ns) / pdf;   // `ns` is the flipped one here when it was flipped (:293)
       }
     }
@@ -2155,8 +2200,15 @@ struct Integ {
   }
 
   // DirectLightingIntegrator::li directlighting.rs:72-132
+  // (census: one li call at reference depth `depth`, which starts at 1)
+  static void li_call(int depth) {
+    path_count(PC_LI_CALLS);
+    path_count(PC_HIST_LI + std::min(depth, kPathBins - 1));
+    path_max(PC_LEVEL_MAX, (uint64_t)depth);
+  }
   Rgb li_direct(Ray ray, RayDiff rdiff, Sampler& smp, int depth) {
     SI isect;
+    li_call(depth);
     if (!scene_intersect(sc, &ray, &isect, nullptr, cnt)) {
       if (sc.d->n_lights > 0) return Rgb();  // `for light in lights { l += le; return l }` (le = 0)
       throw OraclePanic{"directlighting.rs:91 unbounded recursion: miss with an empty light list (Q20)"};
@@ -2169,11 +2221,13 @@ struct Integ {
       else l = l + uniform_sample_one_light(sc, isect, bsdf, smp, nullptr, cnt);
     }
     if ((depth + 1) < in.max_depth) l = l + specular_terms(ray, rdiff, isect, bsdf, smp, depth, [&](Ray r, RayDiff cd, int d) { return li_direct(r, cd, smp, d); });
+    else if (has_specular_lobe(bsdf)) path_count(PC_RECURSION_REFUSED);
     return l;
   }
   // IntersectDebugIntegrator::li intersect_debug.rs:56-89
   Rgb li_debug(Ray ray, RayDiff rdiff, Sampler& smp, int depth) {
     SI isect;
+    li_call(depth);
     if (!scene_intersect(sc, &ray, &isect, nullptr, cnt)) return Rgb();
     Rgb l(0.1, 0.1, 0.1);
     Bsdf bsdf;
@@ -2181,6 +2235,7 @@ struct Integ {
     Rgb s_l;
     if (sc.d->n_lights > 0) s_l = s_l + uniform_sample_all_lights(sc, isect, bsdf, smp, cnt);
     if ((depth + 1) < in.max_depth) s_l = s_l + specular_terms(ray, rdiff, isect, bsdf, smp, depth, [&](Ray r, RayDiff cd, int d) { return li_debug(r, cd, smp, d); });
+    else if (has_specular_lobe(bsdf)) path_count(PC_RECURSION_REFUSED);
     return l + s_l;
   }
   // AOIntegrator::li ao.rs:52-99: compute_scattering_functions is never called, so isect.bsdf is None and
@@ -2375,6 +2430,12 @@ void oracle_bsdf_census(uint64_t* out, int reset) {
 void oracle_light_census(uint64_t* out, int reset) {
   for (int k = 0; k < LC_COUNT; k++)
     out[k] = reset ? g_light_census[k].exchange(0, std::memory_order_relaxed) : g_light_census[k].load(std::memory_order_relaxed);
+}
+// The path census since the last reset (process-wide; PathCensus order, tests/oracle_lib.py PATH_CENSUS names the counters; then five end-cause
+// histograms and the li-call histogram of 66 bins each)
+void oracle_path_census(uint64_t* out, int reset) {
+  for (int k = 0; k < PC_COUNT; k++)
+    out[k] = reset ? g_path_census[k].exchange(0, std::memory_order_relaxed) : g_path_census[k].load(std::memory_order_relaxed);
 }
 // Light::sample_li of lights[light] for the reference point ref_p: out13 = {li.rgb, wi.xyz, pdf, p1.xyz, n1.xyz} (p1 / n1: the far end of the
 // visibility tester; all zero where sample_li returns before it makes one)

@@ -1471,9 +1471,12 @@ static __global__ void k_accumulate_counts(uint32_t* c, unsigned long long* tota
 static __global__ void k_accumulate_shadow(const uint32_t* shadow_count, unsigned long long* totals) { totals[3] += *shadow_count; }
 // bounce rays answered by the horizon tables in the shading launch just finished: queries all the same (totals[8] says how many)
 static __global__ void k_accumulate_sky(uint32_t* c, unsigned long long* totals) { totals[2] += c[C_SKY]; totals[8] += c[C_SKY]; c[C_SKY] = 0; }
-static __global__ void k_accumulate_camera(uint32_t* c, unsigned long long* totals) {
+// queries: 0 where the integrator never issues the camera rays' closest-hit query (Path at max_depth <= 0: it is the dead query at bounces == max_depth),
+// so that the rays the root-box test answered are not counted as queries either
+static __global__ void k_accumulate_camera(uint32_t* c, unsigned long long* totals, int queries) {
   totals[4] += c[C_CAMERA_RAYS]; c[C_CAMERA_RAYS] = 0;
-  totals[2] += c[C_CULLED]; totals[7] += c[C_CULLED]; c[C_CULLED] = 0;   // queries all the same: answered by the root-box test in the camera kernel
+  if (queries) totals[2] += c[C_CULLED];   // queries all the same: answered by the root-box test in the camera kernel
+  totals[7] += c[C_CULLED]; c[C_CULLED] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------

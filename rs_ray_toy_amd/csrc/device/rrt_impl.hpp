@@ -568,7 +568,7 @@ class Handle : public HandleBase {
     // rrt_render_passes: this pool pass's slots of every plane start at 0, as raygen starts L (on the main stream: the shadow stream waits for shading)
     for (uint32_t k = 0; k < passes_n_; k++) HIP_CHECK(hipMemsetAsync(pool_.pass_L + (size_t)k * pool_.pass_stride, 0, nslots * sizeof(typename Vec4T<R>::type), st_));
     tock(e);
-    hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
+    hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p, (integ == RRT_INT_PATH && max_depth <= 0) ? 0 : 1);
     if (integ == RRT_INT_PATH) {
       // bounce b: closest -> shade (NEE + BSDF sample + RR) -> shadow rays; paths live while bounces < max_depth
       const bool overlap = two_shadow_queues() && shadow_buf_[1][0] && !count_traversal_ && max_depth > 1;

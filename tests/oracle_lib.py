@@ -41,6 +41,8 @@ def lib():
         L.oracle_tex_census.argtypes = [C.c_void_p, C.c_int]
         L.oracle_light_census.restype = None
         L.oracle_light_census.argtypes = [C.c_void_p, C.c_int]
+        L.oracle_path_census.restype = None
+        L.oracle_path_census.argtypes = [C.c_void_p, C.c_int]
         L.oracle_light_sample.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
         L.oracle_light_sample.restype = C.c_int
         _lib = L
@@ -251,12 +253,51 @@ def light_census(reset=True):
     return n
 
 
+PATH_CENSUS = ("started", "end_escaped", "end_depth", "end_black_f", "end_pdf_zero", "end_roulette",
+               "vertex_nee", "vertex_specular_only", "vertex_no_lights",
+               "rr_tests", "rr_draws", "rr_floor", "rr_survivors", "rr_eta_decided", "eta_enter", "eta_leave", "dim_max",
+               "rr_draw_near", "rr_test_near",
+               "li_calls", "reflect_taken", "transmit_taken", "recursion_refused", "level_max")
+PATH_ENDS = ("escaped", "depth", "black_f", "pdf_zero", "roulette")
+PATH_BINS = 66
+
+
+def path_census(reset=True):
+    """What the oracle's integrator loops did since the last reset (PathCensus in rrt_oracle.cpp), process-wide. Path: camera samples that entered li_path
+    (started); ends by cause - the closest-hit query missed while bounces < max_depth (escaped), bounces reached max_depth (depth), sample_f returned a
+    black f, a pdf of 0, Russian roulette ended the path; vertices that drew for next-event estimation, that did not because no lobe is non-specular (all specular, or a BSDF without lobes), and
+    that have a non-specular lobe in a scene without lights (no draw either); vertices with bounces > 3, where the roulette test compares (rr_tests),
+    those of them that took the draw (rr_draws), draws whose q = max(1 - rr_max, 0.05) sits on the floor, draws survived; tests that `beta` alone
+    would have decided the other way than `beta * eta_scale` did (rr_eta_decided); eta_scale updates at a specular transmission from outside
+    (eta_enter) and from inside; the largest Halton dimension counter after a draw (dim_max, a maximum); roulette draws with |u - q| < 2^-20 and tests
+    with |rr_max - threshold| < 2^-20 |threshold|: the decisions an fp32 rounding can flip. DirectLighting and Debug: li calls, specular_reflect and
+    specular_transmit recursions taken, li calls that did not recurse because depth + 1 >= max_depth at a hit with a specular lobe, and the deepest
+    reference depth reached (level_max, a maximum; the camera ray is depth 1). `ends` maps each cause to its histogram over the value of `bounces` at
+    the end (bins 0 .. 64 and an overflow bin), `li_depth` is the histogram of li calls over the reference depth. Call it once to reset, render, call it
+    again to read."""
+    n_flat = len(PATH_CENSUS)
+    out = (C.c_uint64 * (n_flat + (len(PATH_ENDS) + 1) * PATH_BINS))()
+    lib().oracle_path_census(out, 1 if reset else 0)
+    n = dict(zip(PATH_CENSUS, (int(v) for v in out)))
+    n["ends"] = {c: [int(v) for v in out[n_flat + k * PATH_BINS:n_flat + (k + 1) * PATH_BINS]] for k, c in enumerate(PATH_ENDS)}
+    n["li_depth"] = [int(v) for v in out[n_flat + len(PATH_ENDS) * PATH_BINS:]]
+    return n
+
+
 def light_sample(scene, light, ref_p, u0=0.5, u1=0.5):
     """Light::sample_li of scene.desc.lights[light] for the reference point ref_p: dict(li, wi, pdf, p1, n1); p1 / n1 are the far end of the visibility tester."""
     ref_p = np.ascontiguousarray(ref_p, np.float64)
     out = np.zeros(13)
     _check(lib().oracle_light_sample(_d(scene), light, ref_p.ctypes.data, u0, u1, out.ctypes.data))
     return dict(li=out[0:3].copy(), wi=out[3:6].copy(), pdf=out[6], p1=out[7:10].copy(), n1=out[10:13].copy())
+
+
+def fp32_bar(d32, allowance=0.0):
+    """test_gpu_parity.py::test_transmissive_materials_path's fp32 bar on d32, the per-pixel difference of an fp32 frame from the oracle's relative to the
+    oracle's brightest pixel: more than 99 % of the pixels within 1e-4 (less `allowance`, the share of the pixels a test can show from the oracle alone to
+    hold a decision that an fp32 rounding may flip), the median below 1e-5. The table tests (test_material_shapes.py, test_light_shapes.py,
+    test_path_shapes.py) share it from here."""
+    assert (d32 < 1e-4).mean() > 0.99 - allowance and np.median(d32) < 1e-5, ((d32 < 1e-4).mean(), np.median(d32), d32.max())
 
 
 def surface_differentials(n, p, dpdu, dpdv, rxo, rxd, ryo, ryd):

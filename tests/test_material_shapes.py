@@ -249,8 +249,7 @@ def test_fp32_frame_close_to_oracle(name, workdir):
         return
     d32 = np.abs(f32[..., :3] - ref[..., :3]).max(-1) / scale
     print(f"{name}: f32 within 1e-4: {(d32 < 1e-4).mean():.4f}, median {np.median(d32):.3e}, max {d32.max():.3e}")
-    if name not in F64_ONLY:
-        assert (d32 < 1e-4).mean() > 0.99 and np.median(d32) < 1e-5, ((d32 < 1e-4).mean(), np.median(d32), d32.max())
+    if name not in F64_ONLY: O.fp32_bar(d32)
 
 
 KERNEL_CLASS = [k for k in FRAMES if MS.CASES[k].carrier in ("walls", "field", "field_cube") and MS.CASES[k].per_hit is None and MS.CASES[k].integrator == MS.PATH and
@@ -280,7 +279,7 @@ def test_kernel_class_changes_nothing(name, workdir):
     assert (d < 1e-6).mean() > 0.995 and np.median(d) < 1e-7, ((d < 1e-6).mean(), d.max())
     for film in (spec, gen) if name not in F64_ONLY else ():      # (no fp32 statement against the oracle for those: material_shapes.py says why)
         dd = np.abs(film[..., :3].astype(np.float64) - ref[..., :3]).max(-1) / scale
-        assert (dd < 1e-4).mean() > 0.99 and np.median(dd) < 1e-5, ((dd < 1e-4).mean(), dd.max())
+        O.fp32_bar(dd)
 
 
 def _general_kernel_anyway(c):
