@@ -104,6 +104,61 @@ struct FrameRec {
 
 template <typename R>
 class Handle : public HandleBase {
+  // ---- what the entry points below share: the argument checks, the pixel and sample counts of a call, the film window of a wide filter ---------
+  // The film kernels in their box form (k_film_box, k_aov_box, k_matte_box ...) are the closed form for the default box filter (radius exactly
+  // 0.5: every sample lands in its own pixel with weight 1); a smaller radius leaves samples near the pixel borders in no pixel at all, a larger
+  // one splats: both take the general (wide) kernels
+  bool wide_filter() const {
+    const rrt_film& f = desc_.film;
+    return f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
+  }
+  void check_rect(const char* msg, const int32_t rect[4], bool allow_empty = false) const {
+    const rrt_film& f = desc_.film;
+    const bool inside = rect[0] >= 0 && rect[1] >= 0 && rect[2] <= f.xres && rect[3] <= f.yres;
+    const bool ordered = allow_empty ? (rect[0] <= rect[2] && rect[1] <= rect[3]) : (rect[0] < rect[2] && rect[1] < rect[3]);
+    if (!inside || !ordered) throw std::invalid_argument(msg);
+  }
+  void check_no_crop() const {
+    const rrt_film& f = desc_.film;
+    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
+  }
+  // the rows of a rect that belong to this rank: those of the interleaved band_h-row bands b with b % n_ranks == rank (partition.py)
+  size_t band_rows(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank) const {
+    const size_t rh = (size_t)(rect[3] - rect[1]);
+    if (n_ranks <= 1) return rh;
+    size_t rows = 0;
+    for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == rank) rows++;
+    return rows;
+  }
+  // the samples of a pixel a frame takes: numbers 1 .. nsamp-1 (Q1), the first max_samples of them where that is not 0
+  uint64_t frame_samples(uint64_t max_samples = 0) const {
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel, n = nsamp > 1 ? nsamp - 1 : 0;
+    return max_samples != 0 ? std::min(n, max_samples) : n;
+  }
+  // the film pixels the samples of a rect can touch under a wide filter: the rect grown by ceil(r + 0.5), clipped to the film; n = ew x eh
+  struct FilmWindow { int ex0, ey0, ew, eh, reach_x, reach_y; size_t n; };
+  FilmWindow film_window(const int32_t rect[4]) const {
+    const rrt_film& f = desc_.film;
+    const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
+    const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
+    const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
+    return {ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0)};
+  }
+  // What launch_raygen sets for the pass it last ran for, put back when a first-hit call ends (a frame's tile-tree and film-record state is its
+  // own), and the queue halves as the call found them (swapped: the follow levels have swapped them an odd number of times)
+  struct RaygenStateGuard {
+    Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6]; bool swapped = false;
+    explicit RaygenStateGuard(Handle* hh) : h(hh), tt_ok(hh->tt_pass_ok_), runs_ok(hh->film_runs_ok_), root_cull(hh->scene_.root_cull) {
+      for (int k = 0; k < 6; k++) root_box[k] = hh->scene_.root_box[k];
+    }
+    RaygenStateGuard(const RaygenStateGuard&) = delete;
+    RaygenStateGuard& operator=(const RaygenStateGuard&) = delete;
+    ~RaygenStateGuard() {
+      h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k];
+      if (swapped) h->swap_queues();
+    }
+  };
+
  public:
   Handle(int device, const rrt_scene_desc* d) : dev_(device), desc_(*d) {
     HIP_CHECK(hipSetDevice(dev_));
@@ -149,6 +204,7 @@ class Handle : public HandleBase {
   void film_geometry(int* xres, int* yres, bool* splats) const override {
     const rrt_film& f = desc_.film;
     *xres = f.xres; *yres = f.yres;
+    // (not wide_filter(): a box filter narrower than 0.5 takes the wide kernels, but none of its samples reaches a neighbouring pixel)
     *splats = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] > 0.5 || f.filter_radius[1] > 0.5;
   }
 
@@ -242,8 +298,7 @@ class Handle : public HandleBase {
   void camera_samples(const int32_t rect[4], uint64_t s0, uint64_t s1, double* dims5, double* ray_od6, double* weight) override {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > desc_.film.xres || rect[3] > desc_.film.yres || rect[0] > rect[2] || rect[1] > rect[3])
-      throw std::invalid_argument("camera_samples: rect outside the film");
+    check_rect("camera_samples: rect outside the film", rect, /*allow_empty=*/true);
     if (s1 < s0 || s1 > desc_.sampler.samples_per_pixel) throw std::invalid_argument("camera_samples: sample range outside [0, samples_per_pixel]");
     const size_t npix = (size_t)(rect[2] - rect[0]) * (size_t)(rect[3] - rect[1]), ns = (size_t)(s1 - s0), n = npix * ns;
     if (n == 0) return;
@@ -320,9 +375,7 @@ class Handle : public HandleBase {
   void render_moments(const int32_t rect[4], int rank, int world, void* film_user, void* moments_user, int mem, rrt_render_stats* stats) override {
     if (pending_) throw std::invalid_argument("render_moments: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
     if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_moments: bad rank/world");
-    const rrt_film& f = desc_.film;
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_moments: rect outside the film");
+    check_rect("render_moments: rect outside the film", rect);
     render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user);
   }
   // ---- rrt_render_frame_aov: the moments frame and the feature buffers of rrt_render_aov from one camera pass --------------------------------------------
@@ -336,15 +389,10 @@ class Handle : public HandleBase {
     if (pending_) throw std::invalid_argument("render_frame_aov: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
     if (aov->precision != precision()) throw std::invalid_argument("render_frame_aov: plane precision must match the handle");
     if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_frame_aov: bad rank/world");
-    const rrt_film& f = desc_.film;
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_frame_aov: rect outside the film");
+    check_rect("render_frame_aov: rect outside the film", rect);
     const int integ = desc_.integrator.type;
     const bool queued = (integ == RRT_INT_PATH && desc_.integrator.max_depth > 0) || ((integ == RRT_INT_DIRECT || integ == RRT_INT_DEBUG) && !(has_transmissive_ || tex_depth_ > 0));
-    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    uint64_t prefix = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
-    if (aov_max_samples != 0) prefix = std::min<uint64_t>(prefix, aov_max_samples);
-    FrameAov fa{aov, queued ? prefix : 0};
+    FrameAov fa{aov, queued ? frame_samples(aov_max_samples) : 0};
     render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user, &fa);
     if (!queued) render_aov(rect, rank, world, aov_max_samples, aov);
   }
@@ -358,9 +406,8 @@ class Handle : public HandleBase {
       if (light_group[i] >= 32) throw std::invalid_argument("render_passes: light_group[" + std::to_string(i) + "] = " + std::to_string((int)light_group[i]) + ": a group is 0 .. 31");
     if (pending_) throw std::invalid_argument("render_passes: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
     if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_passes: bad rank/world");
+    check_rect("render_passes: rect outside the film", rect);
     const rrt_film& f = desc_.film;
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_passes: rect outside the film");
     if (desc_.integrator.type != RRT_INT_PATH)
       throw UnsupportedError("render_passes: the passes are the Path integrator's next-event terms; DirectLighting, AO and Debug frames have no passes");
     if (!std::isinf(f.max_sample_luminance))
@@ -415,18 +462,10 @@ class Handle : public HandleBase {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
     const rrt_film& f = desc_.film;
-    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render rect outside the film");
-    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    size_t rh_all = (size_t)(rect[3] - rect[1]);
-    if (n_ranks > 1) {  // number of rows of this rank's bands
-      size_t rows = 0;
-      for (size_t y = 0; y < rh_all; y++) if ((y / band_h) % n_ranks == rank) rows++;
-      rh_all = rows;
-    }
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = rh_all, rpix = rw * rh;
-    const uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;  // samples 1 .. nsamp-1 (Q1)
+    check_no_crop();
+    check_rect("render rect outside the film", rect);
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, n_ranks, rank), rpix = rw * rh;
+    const uint64_t s_total = frame_samples();
     if (rpix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }   // a rank that owns no band (world > yres / 16): nothing to add to the caller's film
 
     const bool with_moments = moments_user != nullptr || fa != nullptr;
@@ -517,18 +556,23 @@ class Handle : public HandleBase {
   }
   // the passes of sample numbers 1 + s_lo .. s_hi of a rect's (or its bands') rw x rh pixels: pixel groups and sample chunks from what the pools hold
   void rect_passes(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_lo, uint64_t s_hi, bool with_moments, FrameRec& fr) {
+    for_each_pass(rect, band_h, n_ranks, rank, rw, rh, s_lo, s_hi, passes_n_ > 0 ? pass_cap_ : cap_, [&](const PassDesc& pd) { run_pass(pd, nullptr, rect, with_moments, fr); });
+  }
+  // the cutter: sample numbers 1 + s_lo .. s_hi of rw x rh pixels as passes of at most cap slots - pixel groups outermost, sample chunks inside
+  template <class F>
+  void for_each_pass(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_lo, uint64_t s_hi, size_t cap, F&& fn) {
     const size_t rpix = rw * rh;
-    const size_t cap = passes_n_ > 0 ? pass_cap_ : cap_;
+    if (rpix == 0 || s_hi <= s_lo) return;
     const size_t group = std::min(rpix, cap);                            // pixels per group
     const uint64_t s_chunk = std::max<uint64_t>(1, cap / group);          // samples per pass
-    for (size_t g0 = 0; g0 < rpix && s_hi > s_lo; g0 += group) {
+    // tile order of the pixels (PassDesc::tiled) where the rect allows it: whole kTileW x kTileH tiles
+    const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
+    for (size_t g0 = 0; g0 < rpix; g0 += group) {
       const size_t npix = std::min(group, rpix - g0);
       for (uint64_t sb = s_lo; sb < s_hi; sb += s_chunk) {
         const uint64_t ns = std::min<uint64_t>(s_chunk, s_hi - sb);
-        // tile order of the pixels (PassDesc::tiled) where the rect allows it: whole kTileW x kTileH tiles
-        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
         PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, rank, tiled};
-        run_pass(pd, nullptr, rect, with_moments, fr);
+        fn(pd);
       }
     }
   }
@@ -537,9 +581,8 @@ class Handle : public HandleBase {
   void run_pass(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, FrameRec& fr_ref) {
     FrameRec* const fr = &fr_ref;
     const rrt_film& f = desc_.film;
-    // k_film_box is the closed form for the default box filter (radius exactly 0.5: every sample lands in its own pixel with weight 1);
-    // a smaller radius leaves samples near the pixel borders in no pixel at all, a larger one splats: both take the general kernel
-    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
+    const bool wide = wide_filter();
+    const FilmWindow win = film_window(rect);
     const bool timing = fr->timing;
     auto& evs = fr->evs;
     auto tick = [&](int cat, hipStream_t stream = nullptr) {
@@ -670,30 +713,25 @@ class Handle : public HandleBase {
     for (int k = -1; k < (int)passes_n_; k++) {
       R* const film_dst = k < 0 ? film_.p : pass_films_.p + (size_t)k * ((size_t)f.xres * (size_t)f.yres * 4);
       if (k >= 0) pool_.L = pool_.pass_L + (size_t)k * pool_.pass_stride;
-      if (!wide_filter && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
+      if (!wide && film_runs_ok_) {   // the camera kernels of this pass wrote record runs (launch_raygen); never in a moments frame
         if constexpr (std::is_same<R, float>::value)
           hipLaunchKernelGGL(k_film_box_runs, dim3((uint32_t)((npix / 64 + kFrTiles - 1) / kFrTiles)), dim3(64 * kFrTiles), 0, st_, scene_, pool_, pd, film_dst, film_runs_.p, (uint32_t)(ns / 8));
       }
-      else if (!wide_filter) {
+      else if (!wide) {
         const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
         if (list) hipLaunchKernelGGL((k_film_box_moments_list<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_dst, moments_.p);
         else if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p);
         else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst);
       }
       else {
-        // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film
-        const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-        const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-        const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-        const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-        const dim3 fg((uint32_t)((en + kBlock - 1) / kBlock));
-        if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-        else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+        const dim3 fg((uint32_t)((win.n + kBlock - 1) / kBlock));
+        if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p, win.ex0, win.ey0, win.ew, win.eh, win.reach_x, win.reach_y, f.yres);
+        else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, win.ex0, win.ey0, win.ew, win.eh, win.reach_x, win.reach_y, f.yres);
       }
     }
     pool_.L = frame_L;
     tock(e);
-    if (aov_ns > 0) launch_aov_gather_frame(pd, aov_ns, rect, wide_filter);
+    if (aov_ns > 0) launch_aov_gather_frame(pd, aov_ns, win);
     HIP_CHECK(hipGetLastError());
   }
   // the path shading kernel the scene's materials select (shade_kinds_); PS: its rrt_render_passes instantiation
@@ -727,21 +765,19 @@ class Handle : public HandleBase {
     else hipLaunchKernelGGL((k_aov_shade_frame<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, aov_serial_, slot_end);
   }
   // second half, beside the moments film kernel: the pass's PassDesc with ns cut to the feature buffers' samples, gathered into the internal planes
-  void launch_aov_gather_frame(PassDesc pd, uint32_t aov_ns, const int32_t rect[4], bool wide_filter) {
+  void launch_aov_gather_frame(PassDesc pd, uint32_t aov_ns, const FilmWindow& w) {
     using V4 = typename Vec4T<R>::type;
-    const rrt_film& f = desc_.film;
     pd.ns = aov_ns;
-    if (!wide_filter) {
-      hipLaunchKernelGGL((k_aov_box_frame<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_);
-      return;
-    }
-    // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as run_pass)
-    const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-    const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-    const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-    const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-    hipLaunchKernelGGL((k_aov_wide_frame<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_,
-                       ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+    if (!wide_filter()) hipLaunchKernelGGL((k_aov_box_frame<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_);
+    else hipLaunchKernelGGL((k_aov_wide_frame<R>), dim3((uint32_t)((w.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_,
+                            w.ex0, w.ey0, w.ew, w.eh, w.reach_x, w.reach_y, desc_.film.yres);
+  }
+  // the gather of the first-hit calls (render_aov, render_aov_follow): every sample of the pass, the records k_aov_shade / k_aov_follow left
+  void launch_aov_gather(const PassDesc& pd, const FilmWindow& w) {
+    using V4 = typename Vec4T<R>::type;
+    if (!wide_filter()) hipLaunchKernelGGL((k_aov_box<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p);
+    else hipLaunchKernelGGL((k_aov_wide<R>), dim3((uint32_t)((w.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p,
+                            w.ex0, w.ey0, w.ew, w.eh, w.reach_x, w.reach_y, desc_.film.yres);
   }
   // the per-slot records of the first-hit shading kernels, sized like the pools; rec_a - the flag words - zeroed when allocated, so that a slot no
   // kernel has written yet carries no pass's stamp (k_aov_shade_frame)
@@ -761,15 +797,16 @@ class Handle : public HandleBase {
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipStreamSynchronize(st_));
     } else {
-      std::vector<R> tmp(plane_n);
-      for (int k = 0; k < 3; k++) {
-        if (!user[k]) continue;
-        HIP_CHECK(hipMemcpyAsync(tmp.data(), aov_planes_.p + k * plane_n, plane_n * sizeof(R), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        R* dst = (R*)user[k];
-        for (size_t i = 0; i < plane_n; i++) dst[i] += tmp[i];
-      }
+      for (int k = 0; k < 3; k++)
+        if (user[k]) add_to_host(aov_planes_.p + k * plane_n, (R*)user[k], plane_n);
     }
+  }
+  // a device plane added to a host array (+=): staged, one synchronisation of the stream
+  void add_to_host(const R* dev, R* host, size_t n) {
+    std::vector<R> tmp(n);
+    HIP_CHECK(hipMemcpyAsync(tmp.data(), dev, n * sizeof(R), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    for (size_t i = 0; i < n; i++) host[i] += tmp[i];
   }
   // one internal film (RGB sums + weight sum), converted to XYZ, added to a caller's film (+=): enqueued for device memory, done on return for host memory
   void merge_film(const R* src, void* film_user, int film_mem) {
@@ -782,11 +819,7 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemsetAsync(film_xyz_.p, 0, nfilm * sizeof(R), st_));
     hipLaunchKernelGGL((k_film_add<R>), dim3((uint32_t)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, src, film_xyz_.p, npx);
     HIP_CHECK(hipGetLastError());
-    std::vector<R> tmp(nfilm);
-    HIP_CHECK(hipMemcpyAsync(tmp.data(), film_xyz_.p, nfilm * sizeof(R), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));
-    R* dst = (R*)film_user;
-    for (size_t i = 0; i < nfilm; i++) dst[i] += tmp[i];
+    add_to_host(film_xyz_.p, (R*)film_user, nfilm);
   }
   // the internal film, converted to XYZ, and the internal moments buffer (where moments_user is given) added to the caller's buffers (+=); wait = 0
   // (device memory only): enqueued, not waited for
@@ -800,15 +833,8 @@ class Handle : public HandleBase {
       HIP_CHECK(hipGetLastError());
       if (!wait) return;
       HIP_CHECK(hipStreamSynchronize(st_));
-    } else {
-      if (with_moments) {
-        std::vector<R> tmp(nfilm);
-        HIP_CHECK(hipMemcpyAsync(tmp.data(), moments_.p, nfilm * sizeof(R), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        R* dm = (R*)moments_user;
-        for (size_t i = 0; i < nfilm; i++) dm[i] += tmp[i];
-      }
     }
+    else if (with_moments) add_to_host(moments_.p, (R*)moments_user, nfilm);
   }
   // ---- rrt_render_adaptive: a moments frame that stops sampling the 8 x 8 tiles whose error estimate fell below the threshold ------------------------------
   // Round 0 is the moments frame's own passes over the rect for sample numbers 1 .. k0 (tile trees and all). After each round k_tile_error measures the
@@ -823,14 +849,11 @@ class Handle : public HandleBase {
     const rrt_film& f = desc_.film;
     if (desc_.sampler.type == RRT_SAMPLER_STRATIFIED)
       throw UnsupportedError("render_adaptive: StratifiedSampler (the first k samples of a stratified pixel are not a k-sample stratified pixel; use the HaltonSampler)");
-    if (f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5)
+    if (wide_filter())
       throw UnsupportedError("render_adaptive: pixel filters other than the box filter of radius 0.5 (a wider filter splats across tiles with different sample counts)");
-    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_adaptive: rect outside the film");
-    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    const uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
-    const uint64_t K = std::min<uint64_t>(ap->max_samples ? ap->max_samples : s_total, s_total), k0 = std::min<uint64_t>(ap->min_samples, K);
+    check_no_crop();
+    check_rect("render_adaptive: rect outside the film", rect);
+    const uint64_t K = frame_samples(ap->max_samples), k0 = std::min<uint64_t>(ap->min_samples, K);
     const size_t rw = (size_t)(rect[2] - rect[0]), rh = (size_t)(rect[3] - rect[1]), rpix = rw * rh;
     const uint32_t tiles_x = (uint32_t)(rw / kTileW), n_tiles = tiles_x * (uint32_t)(rh / kTileH);
     const auto kind = mem == RRT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -884,9 +907,8 @@ class Handle : public HandleBase {
   // ---- rrt_tile_error: k_tile_error over every tile of the rect, on the caller's plane --------------------------------------------------------------------
   void tile_error(const void* moments, int mem, const int32_t rect[4], double* out) override {
     if (pending_) throw std::invalid_argument("tile_error: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    check_rect("tile_error: rect outside the film", rect);
     const rrt_film& f = desc_.film;
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("tile_error: rect outside the film");
     HIP_CHECK(hipSetDevice(dev_));
     using V4 = typename Vec4T<R>::type;
     const size_t npix = (size_t)f.xres * (size_t)f.yres;
@@ -903,83 +925,85 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemcpyAsync(out, te_out_.p, n_tiles * sizeof(double), mem == RRT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
   }
-  // ---- first-hit feature buffers (rrt_render_aov): the frame's camera samples, traced once, into albedo / normal / depth planes -------------
-  // The pass loop of render_impl (same pixel groups and sample chunks from cap_) with three launches per pass: camera kernels, closest hit,
-  // k_aov_shade, then the gather-form film kernel over the handle's internal planes. Nothing of the frame's state is kept changed: the
-  // internal film, the statistics' totals and the tile-tree state are not touched (tile trees are used where a frame has built them, never
-  // built here), and what launch_raygen sets per pass is put back.
+  // ---- the first-hit calls: rrt_render_aov, rrt_render_aov_follow, rrt_render_mattes ---------------------------------------------------------------
+  // Each traces the frame's camera samples once and keeps something of the surface they see instead of radiance. They share first_hit_passes:
+  // the passes of a frame (for_each_pass: the same pixel groups and sample chunks from cap_), and per pass the camera kernels, the closest-hit
+  // launch over the camera queue (tile trees where a frame has built them, never built here), the call's `shade` - what a slot keeps of its hit,
+  // written into the call's per-slot records - and the call's `gather`, the film kernel in gather form over those records. Nothing of the frame's
+  // state is kept changed: the internal film, the statistics' totals and the tile-tree state are not touched, and a RaygenStateGuard of the
+  // call puts back what launch_raygen sets per pass. The caller sizes the pools and its records before.
+  template <class Shade, class Gather>
+  void first_hit_passes(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_total, Shade&& shade, Gather&& gather) {
+    for_each_pass(rect, band_h, n_ranks, rank, rw, rh, 0, s_total, cap_, [&](const PassDesc& pd) {
+      const uint32_t grid = (uint32_t)(((size_t)pd.npix * pd.ns + kBlock - 1) / kBlock);
+      hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+      launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
+      launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
+      shade(pd, grid);
+      gather(pd);
+      HIP_CHECK(hipGetLastError());
+    });
+  }
+  // ---- feature buffers (rrt_render_aov) and feature buffers through mirrors and glass (rrt_render_aov_follow): albedo / normal / depth planes -------
+  // One body: rrt_render_aov is rrt_render_aov_follow with max_follow = 0 under its own name. shade: k_aov_shade for the first hits' records, then
+  // per level k_aov_follow, the queue rotation and a closest-hit launch over the device-side count of followed entries - no host read-back
+  // between levels, launches sized by the pass like the path loop's; with max_follow = 0 the level loop ends before its first launch. gather:
+  // k_aov_box / k_aov_wide into the handle's internal planes, which aov_merge_out adds to the caller's. The guard also puts the queue halves back
+  // that the levels swap.
   void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) override {
-    if (pending_) throw std::invalid_argument("render_aov: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (out->precision != precision()) throw std::invalid_argument("render_aov: plane precision must match the handle");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_aov: bad rank/world");
+    aov_passes("render_aov", rect, rank, world, max_samples, 0, out);
+  }
+  void render_aov_follow(const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) override {
+    aov_passes("render_aov_follow", rect, rank, world, max_samples, max_follow, out);
+  }
+  void aov_passes(const std::string& who, const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) {
+    if (pending_) throw std::invalid_argument(who + ": a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (out->precision != precision()) throw std::invalid_argument(who + ": plane precision must match the handle");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument(who + ": bad rank/world");
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
-    const rrt_film& f = desc_.film;
-    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
-    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_aov: rect outside the film");
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30, n_ranks = (uint32_t)world;
-    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    const size_t W = (size_t)f.xres, H = (size_t)f.yres, plane_n = W * H * 4;
-    size_t rh = (size_t)(rect[3] - rect[1]);
-    if (n_ranks > 1) {   // rows of this rank's bands
-      size_t rows = 0;
-      for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == (uint32_t)rank) rows++;
-      rh = rows;
-    }
-    const size_t rw = (size_t)(rect[2] - rect[0]), rpix = rw * rh;
-    uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
-    if (max_samples != 0) s_total = std::min<uint64_t>(s_total, max_samples);
+    check_no_crop();
+    check_rect((who + ": rect outside the film").c_str(), rect);
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
+    const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank), rpix = rw * rh;
+    const uint64_t s_total = frame_samples(max_samples);
     if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
-    using V4 = typename Vec4T<R>::type;
-    struct Restore {   // what launch_raygen sets for the pass it last ran for
-      Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6];
-      ~Restore() { h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k]; }
-    } restore{this, tt_pass_ok_, film_runs_ok_, scene_.root_cull, {scene_.root_box[0], scene_.root_box[1], scene_.root_box[2], scene_.root_box[3], scene_.root_box[4], scene_.root_box[5]}};
+    if (!has_specular_) max_follow = 0;   // no surface of the scene is followed: every chain ends on its first hit, and no level is launched to find that out
+    RaygenStateGuard guard(this);
 
     if (aov_planes_.n != 3 * plane_n) aov_planes_.alloc(3 * plane_n);
     HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
     ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
     ensure_aov_recs();
-    const size_t group = std::min(rpix, cap_);                     // pixels per group
-    const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
-    for (size_t g0 = 0; g0 < rpix; g0 += group) {
-      const size_t npix = std::min(group, rpix - g0);
-      for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
-        const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
-        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
-        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, (uint32_t)rank, tiled};
-        const size_t nslots = npix * (size_t)ns;
-        const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
-        launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
-        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
+    const FilmWindow win = film_window(rect);
+    first_hit_passes(rect, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, s_total,
+      [&](const PassDesc&, uint32_t grid) {
         const dim3 sg(std::min(grid, 16384u));
+        // level 0's records are k_aov_shade's own (see k_aov_follow)
         if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
         else hipLaunchKernelGGL((k_aov_shade<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
-        if (!wide_filter) hipLaunchKernelGGL((k_aov_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p);
-        else {
-          // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as render_impl)
-          const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-          const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-          const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-          const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-          hipLaunchKernelGGL((k_aov_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p,
-                             ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
+        for (uint32_t k = 0; k <= max_follow; k++) {
+          const int level0 = k == 0 ? 1 : 0, may_follow = k < max_follow ? 1 : 0;
+          if (level0 && !may_follow) break;   // max_follow = 0: the first hits are the planes
+          if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_follow<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
+          else hipLaunchKernelGGL((k_aov_follow<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
+          if (!may_follow) break;
+          swap_queues(); guard.swapped = !guard.swapped;
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);   // active <- next
+          launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/false);
         }
-        HIP_CHECK(hipGetLastError());
-      }
-    }
+      },
+      [&](const PassDesc& pd) { launch_aov_gather(pd, win); });
     aov_merge_out(out);   // into the caller's planes (+=)
     check_device_errors();
   }
-  // ---- ID mattes (rrt_render_mattes): render_aov's pass loop with k_matte_ids in k_aov_shade's place and a (id, coverage) table in the planes' ----------
+  // ---- ID mattes (rrt_render_mattes): first_hit_passes with shade = k_matte_ids and gather = k_matte_box / k_matte_wide into a (id, coverage) table -----
   // Per call: the ids of the entries of prim_order are built on the host and uploaded (they are the caller's, not the scene's: nothing of the scene
   // preparation knows them), the caller's table is copied into the internal slot-major one (k_matte_load; a host table is staged), the passes insert
-  // into it (k_matte_box / k_matte_wide), k_matte_rank sorts it out. What render_aov puts back per pass is put back here. Load, rank and the
-  // staging of a host table run over the whole W x H x K table whatever the rect: a frame cut into n calls moves the table n times.
+  // into it, k_matte_rank sorts it out. Load, rank and the staging of a host table run over the whole W x H x K table whatever the rect - also for
+  // a rank without rows or a call without samples, which runs no pass: a frame cut into n calls moves the table n times.
   void render_mattes(const int32_t rect[4], int rank, int world, uint64_t max_samples, const uint32_t* prim_id, size_t n_prim_id, const rrt_mattes* out) override {
     if (pending_) throw std::invalid_argument("render_mattes: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
     if (prim_id && n_prim_id != desc_.n_prims)
@@ -988,29 +1012,16 @@ class Handle : public HandleBase {
     if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_mattes: bad rank/world");
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
-    const rrt_film& f = desc_.film;
-    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
-    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_mattes: rect outside the film");
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30, n_ranks = (uint32_t)world;
-    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    const size_t W = (size_t)f.xres, H = (size_t)f.yres, NP = W * H;
+    check_no_crop();
+    check_rect("render_mattes: rect outside the film", rect);
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
+    const size_t NP = (size_t)desc_.film.xres * (size_t)desc_.film.yres;
     const uint32_t K = (uint32_t)out->n_slots;
-    size_t rh = (size_t)(rect[3] - rect[1]);
-    if (n_ranks > 1) {   // rows of this rank's bands
-      size_t rows = 0;
-      for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == (uint32_t)rank) rows++;
-      rh = rows;
-    }
-    const size_t rw = (size_t)(rect[2] - rect[0]), rpix = rw * rh;
-    uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
-    if (max_samples != 0) s_total = std::min<uint64_t>(s_total, max_samples);
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank), rpix = rw * rh;
+    const uint64_t s_total = frame_samples(max_samples);
     using V4 = typename Vec4T<R>::type;
-    struct Restore {   // what launch_raygen sets for the pass it last ran for
-      Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6];
-      ~Restore() { h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k]; }
-    } restore{this, tt_pass_ok_, film_runs_ok_, scene_.root_cull, {scene_.root_box[0], scene_.root_box[1], scene_.root_box[2], scene_.root_box[3], scene_.root_box[4], scene_.root_box[5]}};
+    RaygenStateGuard guard(this);
+
 
     // the id of every entry of prim_order
     const size_t n_ord = matte_order_.size();
@@ -1045,34 +1056,17 @@ class Handle : public HandleBase {
     if (rpix > 0 && s_total > 0) {
       ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
       if (matte_rec_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); matte_rec_.alloc(cap_); }
-      const size_t group = std::min(rpix, cap_);                     // pixels per group
-      const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
-      for (size_t g0 = 0; g0 < rpix; g0 += group) {
-        const size_t npix = std::min(group, rpix - g0);
-        for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
-          const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
-          const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
-          PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, (uint32_t)rank, tiled};
-          const size_t nslots = npix * (size_t)ns;
-          const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
-          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
-          launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
-          launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
-          const dim3 sg(std::min(grid, 16384u));
-          hipLaunchKernelGGL((k_matte_ids<R>), sg, dim3(kBlock), 0, st_, pool_, (const uint32_t*)matte_id_dev_.p, (uint32_t)n_ord, matte_rec_.p);
-          if (!wide_filter) hipLaunchKernelGGL((k_matte_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p);
-          else {
-            // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as render_aov)
-            const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-            const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-            const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-            const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-            hipLaunchKernelGGL((k_matte_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p,
-                               ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-          }
-          HIP_CHECK(hipGetLastError());
-        }
-      }
+      const bool wide = wide_filter();
+      const FilmWindow w = film_window(rect);
+      first_hit_passes(rect, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, s_total,
+        [&](const PassDesc&, uint32_t grid) {
+          hipLaunchKernelGGL((k_matte_ids<R>), dim3(std::min(grid, 16384u)), dim3(kBlock), 0, st_, pool_, (const uint32_t*)matte_id_dev_.p, (uint32_t)n_ord, matte_rec_.p);
+        },
+        [&](const PassDesc& pd) {
+          if (!wide) hipLaunchKernelGGL((k_matte_box<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p);
+          else hipLaunchKernelGGL((k_matte_wide<R>), dim3((uint32_t)((w.n + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p,
+                                  w.ex0, w.ey0, w.ew, w.eh, w.reach_x, w.reach_y, desc_.film.yres);
+        });
     }
     // ranked, into the caller's table
     hipLaunchKernelGGL((k_matte_rank<R>), dim3(pix_grid), dim3(kBlock), lds, st_, tab, host ? matte_stage_ids_.p : out->ids, host ? matte_stage_cov_.p : (R*)out->coverage);
@@ -1117,92 +1111,6 @@ class Handle : public HandleBase {
     HIP_CHECK(hipGetLastError());
     if (host) HIP_CHECK(hipMemcpyAsync(alpha, matte_alpha_.p, NP * sizeof(R), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
-  }
-  // ---- feature buffers through mirrors and glass (rrt_render_aov_follow): render_aov's pass loop with a level loop in place of k_aov_shade ------------
-  // Per pass: camera kernels, closest hit over the camera queue (tile trees where a frame has built them), k_aov_shade for the first hits' records,
-  // then per level k_aov_follow, the queue rotation and a closest-hit launch over the device-side count of followed entries - no host read-back between levels, launches sized by the
-  // pass like the path loop's - and render_aov's own gather kernels. What launch_raygen sets per pass and the queue halves the levels swap are put back.
-  void render_aov_follow(const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) override {
-    if (pending_) throw std::invalid_argument("render_aov_follow: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (out->precision != precision()) throw std::invalid_argument("render_aov_follow: plane precision must match the handle");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_aov_follow: bad rank/world");
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
-    const rrt_film& f = desc_.film;
-    const bool wide_filter = f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5;
-    if (f.crop[0] != 0 || f.crop[1] != 0 || f.crop[2] != f.xres || f.crop[3] != f.yres) throw UnsupportedError("film crop window");
-    if (rect[0] < 0 || rect[1] < 0 || rect[2] > f.xres || rect[3] > f.yres || rect[0] >= rect[2] || rect[1] >= rect[3])
-      throw std::invalid_argument("render_aov_follow: rect outside the film");
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30, n_ranks = (uint32_t)world;
-    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
-    const size_t W = (size_t)f.xres, H = (size_t)f.yres, plane_n = W * H * 4;
-    size_t rh = (size_t)(rect[3] - rect[1]);
-    if (n_ranks > 1) {   // rows of this rank's bands
-      size_t rows = 0;
-      for (size_t y = 0; y < rh; y++) if ((y / band_h) % n_ranks == (uint32_t)rank) rows++;
-      rh = rows;
-    }
-    const size_t rw = (size_t)(rect[2] - rect[0]), rpix = rw * rh;
-    uint64_t s_total = nsamp > 1 ? nsamp - 1 : 0;   // samples 1 .. nsamp-1 (Q1)
-    if (max_samples != 0) s_total = std::min<uint64_t>(s_total, max_samples);
-    if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
-    if (!has_specular_) max_follow = 0;   // no surface of the scene is followed: every chain ends on its first hit, and no level is launched to find that out
-    using V4 = typename Vec4T<R>::type;
-    struct Restore {   // what launch_raygen sets for the pass it last ran for, and the queue halves as the call found them
-      Handle* h; bool tt_ok, runs_ok; uint32_t root_cull; float root_box[6]; bool swapped;
-      ~Restore() {
-        h->tt_pass_ok_ = tt_ok; h->film_runs_ok_ = runs_ok; h->scene_.root_cull = root_cull; for (int k = 0; k < 6; k++) h->scene_.root_box[k] = root_box[k];
-        if (swapped) h->swap_queues();
-      }
-    } restore{this, tt_pass_ok_, film_runs_ok_, scene_.root_cull, {scene_.root_box[0], scene_.root_box[1], scene_.root_box[2], scene_.root_box[3], scene_.root_box[4], scene_.root_box[5]}, false};
-
-    if (aov_planes_.n != 3 * plane_n) aov_planes_.alloc(3 * plane_n);
-    HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
-    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
-    ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
-    ensure_aov_recs();
-    const size_t group = std::min(rpix, cap_);                     // pixels per group
-    const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / group);   // samples per pass
-    for (size_t g0 = 0; g0 < rpix; g0 += group) {
-      const size_t npix = std::min(group, rpix - g0);
-      for (uint64_t sb = 0; sb < s_total; sb += s_chunk) {
-        const uint64_t ns = std::min<uint64_t>(s_chunk, s_total - sb);
-        const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
-        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, (uint32_t)rank, tiled};
-        const size_t nslots = npix * (size_t)ns;
-        const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
-        launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
-        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/true);
-        const dim3 sg(std::min(grid, 16384u));
-        // level 0's records are k_aov_shade's own (see k_aov_follow)
-        if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
-        else hipLaunchKernelGGL((k_aov_shade<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
-        for (uint32_t k = 0; k <= max_follow; k++) {
-          const int level0 = k == 0 ? 1 : 0, may_follow = k < max_follow ? 1 : 0;
-          if (level0 && !may_follow) break;   // max_follow = 0: the first hits are the planes
-          if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_follow<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
-          else hipLaunchKernelGGL((k_aov_follow<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
-          if (!may_follow) break;
-          swap_queues(); restore.swapped = !restore.swapped;
-          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);   // active <- next
-          launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/false);
-        }
-        if (!wide_filter) hipLaunchKernelGGL((k_aov_box<R>), dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p);
-        else {
-          // film pixels the samples of this rect can touch: the rect grown by ceil(r + 0.5), clipped to the film (as render_impl)
-          const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
-          const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
-          const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-          const size_t en = (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0);
-          hipLaunchKernelGGL((k_aov_wide<R>), dim3((uint32_t)((en + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p,
-                             ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres);
-        }
-        HIP_CHECK(hipGetLastError());
-      }
-    }
-    aov_merge_out(out);   // into the caller's planes (+=)
-    check_device_errors();
   }
   // ---- rrt_denoise (device/dfilter.hpp): prepare, initial variance, one a-trous launch per iteration, finish ---------------------------------------------
   // Only the handle's stream and its own work buffers are used: nothing of the frame's state is read or written.
@@ -1724,8 +1632,7 @@ class Handle : public HandleBase {
         const uint32_t total = pd.npix * pd.ns;
         if (pix_off_.n < 2 * (size_t)pd.npix) { HIP_CHECK(hipStreamSynchronize(st_)); pix_off_.alloc(2 * (size_t)pd.npix); }
         pool_.pix_off = pix_off_.p;
-        const rrt_film& f = desc_.film;
-        const int write_samp = (f.filter_type != RRT_FILTER_BOX || f.filter_radius[0] != 0.5 || f.filter_radius[1] != 0.5) ? 1 : 0;   // only k_film_wide reads p_film
+        const int write_samp = wide_filter() ? 1 : 0;   // only the wide film kernels read p_film
         if (list) hipLaunchKernelGGL(k_pixel_offsets_list, dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, scene_, pool_, pd, list);
         else hipLaunchKernelGGL(k_pixel_offsets, dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, scene_, pool_, pd);
         // (dead samples: weight 0, Q2 - written by k_raygen_main_f32 itself, one coalesced store per sample)

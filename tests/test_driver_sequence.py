@@ -1,0 +1,86 @@
+"""The driver's calls one after another on one handle (device/rrt_impl.hpp: the frame layer, and the first-hit calls that share one pass loop and
+one guard for what a pass leaves set in the handle).
+
+The "handle is untouched" tests of test_aov.py, test_aov_follow.py, test_mattes.py and test_frame_aov.py each put one call between two frames. Here
+a frame, the feature buffers, the followed feature buffers, the mattes, the fused frame, the adaptive frame, the moments frame, a refused call and
+once more the followed buffers and the frame run on ONE handle, and each result is, bit for bit, what the same call gives on a fresh handle.
+
+Scene: aov_follow_scenes.mirror_floor at 32 x 24 (the mirror makes the follow levels run), Path integrator, Halton, 9 samples per pixel, under the
+box filter and under the Gaussian filter of test_aov_follow.py (the wide film window), both precisions. Every handle has max_paths = 1000 set
+before its first call: the pools hold 1000 slots, so the 768 pixels x 8 samples of a call are cut into one pass per sample number (the frame's
+launch count shows it, as in test_mattes.py::test_small_pools).
+"""
+import numpy as np
+import pytest
+
+import aov_follow_scenes as FS
+from rs_ray_toy_amd import RRT_F32, RRT_F64, RRT_FIXED_BVH, Renderer, RrtError, Scene
+
+GAUSS = {"filter_type": "GaussianFilter", "radius": [1.5, 1.5], "alpha": 1.0}
+MAX_PATHS = 1000
+STAT_KEYS = ("camera_rays", "closest_queries", "any_queries", "tile_launches", "root_culled")
+
+# name -> the call; every call returns arrays (or nests of them) only
+CALLS = {
+    "render": lambda r: r.render(),
+    "aov": lambda r: r.render_aov(),
+    "follow": lambda r: r.render_aov(follow=3),
+    "mattes": lambda r: r.render_mattes(ids="prim", slots=3),
+    "frame_aov": lambda r: r.render_frame_aov(),
+    "adaptive": lambda r: r.render_adaptive(min_samples=4, batch=2),
+    "moments": lambda r: r.render_moments(),
+}
+
+
+def _handle(sc, prec):
+    r = Renderer(sc, 0, prec)
+    r.set_option("max_paths", MAX_PATHS)
+    return r
+
+
+def _flat(x):
+    """the arrays of a result, in a fixed order"""
+    if isinstance(x, dict): return [a for k in sorted(x) for a in _flat(x[k])]
+    if isinstance(x, (tuple, list)): return [a for y in x for a in _flat(y)]
+    return [x]
+
+
+def _assert_equal(name, got, want):
+    g, w = _flat(got), _flat(want)
+    assert len(g) == len(w) and len(g) > 0, name
+    for k, (a, b) in enumerate(zip(g, w)):
+        assert a.dtype == b.dtype and np.array_equal(a, b), (name, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", [RRT_F32, RRT_F64], ids=["f32", "f64"])
+@pytest.mark.parametrize("filt", [None, GAUSS], ids=["box", "gauss"])
+def test_calls_in_sequence_are_calls_on_fresh_handles(prec, filt, workdir):
+    cfg, root = FS.mirror_floor(workdir, (32, 24))
+    if filt: cfg["Film"]["Filter"] = dict(filt)
+    sc = Scene.loads(cfg, root, flags=RRT_FIXED_BVH)
+    names = [n for n in CALLS if not (n == "adaptive" and filt)]      # rrt_render_adaptive takes the box filter of radius 0.5 only
+
+    want = {}
+    for n in names:
+        fresh = _handle(sc, prec)
+        want[n] = CALLS[n](fresh)
+        fresh.close()
+    assert want["render"][..., :3].max() > 0 and want["aov"]["depth"][..., 2].max() > 0
+    assert not np.array_equal(want["follow"]["depth"], want["aov"]["depth"])      # the follow levels ran
+    assert want["mattes"]["coverage"].max() > 0
+
+    r = _handle(sc, prec)
+    first, s_first = r.render(stats=True)
+    assert s_first.closest_launches >= 8      # at least one launch per sample number: the pools hold max_paths slots
+    _assert_equal("render", first, want["render"])
+    for n in names[1:]:
+        _assert_equal(n, CALLS[n](r), want[n])
+    with pytest.raises(RrtError, match="render_aov: rect outside the film"):
+        r.render_aov(rect=(0, 0, 33, 24))
+    _assert_equal("follow again", CALLS["follow"](r), want["follow"])
+    last, s_last = r.render(stats=True)
+    r.close()
+    _assert_equal("render again", last, want["render"])
+    for key in STAT_KEYS:
+        assert getattr(s_first, key) == getattr(s_last, key), key
