@@ -362,6 +362,56 @@ int rrt_camera_samples(rrt_handle*, const int32_t rect[4], uint64_t s0, uint64_t
 int rrt_render_rect(rrt_handle*, const int32_t rect[4], void* film_xyzw, int film_mem,
                     rrt_render_stats* stats /* may be NULL */);
 
+/* Radiance along caller-supplied rays (no counterpart in the reference, whose only way into an integrator is its RealisticCamera): another
+ * camera, light probes and baking, or a look at what each sample of a pixel carried. The caller's rays take the place of the camera kernels;
+ * everything behind them - traversal, shading, sampler streams, film - is the frame's own code on the same pool state.
+ *
+ * rrt_ray_samples: SoA like rrt_rays, element type = the handle's precision, all arrays in `mem`.
+ *   d:          taken as given; must be unit length, as the camera's is.
+ *   weight:     may be NULL = 1 everywhere. A sample with weight 0 (or below, or NaN) is dead: never traced.
+ *   rxo .. ryd: optional ray differentials, all twelve arrays NULL or all set: origin and direction of rx and of ry, ALREADY scaled as
+ *               scale_differentials leaves them (integrator/mod.rs:94-96). NULL: rx = ry = the ray itself (zero footprint). Read only when
+ *               the scene has textured materials.
+ *   pixel, sample_num: the sampler stream of each ray - the state the frame's sample (x, y, sample_num) has after get_camerasample
+ *               (samplers/mod.rs:28-34). pixel = y << 16 | x inside the film, sample_num in 1 .. nsamp-1. Used by rrt_radiance only;
+ *               rrt_render_rays derives both from the layout.
+ *
+ * rrt_radiance: rgb4[4 i .. 4 i + 3] = {Li.r, Li.g, Li.b, 0} of ray i (handle precision, in rays->mem, 16-byte aligned there), Li by the
+ * scene's integrator - Path, DirectLighting or Debug; AOIntegrator returns 0, as the frame's does (ao.rs:62-64). The sampler starts where the
+ * frame's sample (pixel, sample_num) stands after its camera sample: HaltonSampler index halton_pixel_offset + sample_num * stride,
+ * StratifiedSampler the (pixel, sample_num) index the camera kernels form, dimension counters past the camera's, bounce 0. The ray is traced
+ * as the frame traces a camera ray: t_max = inf, no start triangle. Two rays that name the same (pixel, sample_num) are legal and simply
+ * correlated. weight (beyond dead or alive), Film.max_sample_luminance and the pixel filter play no part; a dead ray yields 0. A ray's result
+ * depends on its own inputs only - not on its position in the batch, nor on how the batch is cut into pool-sized chunks ("max_paths").
+ *
+ * rrt_render_rays: what rrt_render_rect does for sample_num in [s0, s1) of the rect's pixels, with the camera kernels replaced by the
+ * caller's (ray, weight, p_film) per sample, laid out [pixel][sample] over the rect as rrt_camera_samples lays its outputs out. p_film: 2
+ * per sample, handle precision, in rays->mem, raster coordinates (a sample of pixel (x, y) has p_film in [x, x+1) x [y, y+1), as the
+ * reference's samplers place it). Everything else is the frame's: FilmTile::add_sample through the film's own filter, weight-0 samples
+ * still adding filter weight (Q2), the max_sample_luminance clamp, the tripled weight (Q3), += into the caller's film, the frame
+ * statistics - camera_rays counts the weights > 0; what belongs to the camera kernels (tile_launches, root_culled) is 0. Fed the handle's
+ * own rrt_camera_samples, it reproduces rrt_render_rect's film.
+ *
+ * Both leave the handle as it was (a frame rendered before and after is the same frame). Errors, before any device work where the host
+ * can see the arguments: RRT_EINVAL for NULL arguments, a precision that is not the handle's, partly set differentials, a rect outside the
+ * film, s0 < 1, s1 > nsamp or s0 >= s1, n == 0, a frame in flight, a pixel or sample_num out of range - for device-resident arrays that
+ * last check is made on the device before anything is traced, and the call returns RRT_EINVAL with nothing written to rgb4. RRT_EUNSUP /
+ * RRT_EPANIC as rrt_render_rect gives for the scene.
+ * Not provided: rank / world bands, _begin / _end (frames in flight), and the moments, passes and feature-buffer forms of the frame.
+ * Measured (tools/render_rays_time.py, profiles/render_rays_time.json; config 4 at 1024^2, 32 spp, depth 8, fp32, samples and film in device
+ * memory, one MI355X): rrt_render_rays on the handle's own camera samples 5.49 ms against rrt_render_rect's 6.42 ms (0.85), the same film bits. */
+typedef struct rrt_ray_samples {
+  int32_t mem, precision;
+  const void *ox, *oy, *oz, *dx, *dy, *dz;
+  const void *weight;
+  const void *rxo[3], *rxd[3], *ryo[3], *ryd[3];
+  const uint32_t *pixel;
+  const uint32_t *sample_num;
+} rrt_ray_samples;
+int rrt_radiance(rrt_handle*, const rrt_ray_samples* rays, size_t n, void* rgb4);
+int rrt_render_rays(rrt_handle*, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film,
+                    void* film_xyzw, int film_mem, rrt_render_stats* stats /* may be NULL */);
+
 /* Multi-GPU film partition: the same, for the rows of the interleaved 16-row tile bands b with
  * b % world == rank (tile height of integrator/mod.rs:55), rendered as one pixel set. Box filter: the ranks' films are
  * disjoint; wider filters: a sample's splat may land in a neighbour's rows of this rank's film. Either way summing

@@ -143,6 +143,11 @@ class Hits(C.Structure):
                 ("u", C.c_void_p), ("v", C.c_void_p), ("nodes_visited", C.c_void_p), ("prims_tested", C.c_void_p)]
 
 
+class RaySamples(C.Structure):
+    _fields_ = ([("mem", C.c_int32), ("precision", C.c_int32)] + [(k, C.c_void_p) for k in ("ox", "oy", "oz", "dx", "dy", "dz", "weight")]
+                + [(k, C.c_void_p * 3) for k in ("rxo", "rxd", "ryo", "ryd")] + [("pixel", C.c_void_p), ("sample_num", C.c_void_p)])
+
+
 class RenderStats(C.Structure):
     _fields_ = [("camera_samples", C.c_uint64), ("camera_rays", C.c_uint64), ("closest_queries", C.c_uint64),
                 ("any_queries", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
@@ -204,6 +209,9 @@ PROTOTYPES = {
     "rrt_camera_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "rrt_render_rect": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
+    "rrt_radiance": (C.c_int, [C.c_void_p, C.POINTER(RaySamples), C.c_size_t, C.c_void_p]),
+    "rrt_render_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, C.POINTER(RaySamples), C.c_void_p, C.c_void_p, C.c_int,
+                                  C.POINTER(RenderStats)]),
     "rrt_render_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_render_bands_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rrt_render_end": (C.c_int, [C.c_void_p]),

@@ -205,6 +205,73 @@ class Renderer:
         _check(A.lib().rrt_render_rect(self._h, r, film.ctypes.data, A.RRT_MEM_HOST, C.byref(st) if stats else None))
         return (film, st) if stats else film
 
+    # radiance along caller-supplied rays (rrt_radiance, rrt_render_rays)
+    def _ray_samples(self, o, d, weight, diffs, pixel=None, sample_num=None):
+        """rrt_ray_samples over host arrays: o, d (n, 3); weight (n,) or None; diffs None or (rxo, rxd, ryo, ryd), (n, 3) each. Returns the
+        struct and the arrays it points into (keep them alive for the call)."""
+        o = np.asarray(o); d = np.asarray(d)
+        keep = [np.ascontiguousarray(a, self.dtype) for a in (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2])]
+        rs = A.RaySamples(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in keep])
+        if weight is not None:
+            keep.append(np.ascontiguousarray(weight, self.dtype))
+            rs.weight = keep[-1].ctypes.data
+        if diffs is not None:
+            for name, a in zip(("rxo", "rxd", "ryo", "ryd"), diffs):
+                cols = [np.ascontiguousarray(np.asarray(a)[:, k], self.dtype) for k in range(3)]
+                keep += cols
+                setattr(rs, name, (C.c_void_p * 3)(*[c.ctypes.data for c in cols]))
+        if pixel is not None:
+            pixel = np.asarray(pixel)
+            if pixel.ndim == 2:   # (n, 2) of (x, y) -> y << 16 | x
+                pixel = (pixel[:, 1].astype(np.uint32) << 16) | pixel[:, 0].astype(np.uint32)
+            keep += [np.ascontiguousarray(pixel, np.uint32), np.ascontiguousarray(sample_num, np.uint32)]
+            rs.pixel, rs.sample_num = keep[-2].ctypes.data, keep[-1].ctypes.data
+        return rs, keep
+
+    def radiance(self, o, d, pixel, sample_num, weight=None, diffs=None, out=None):
+        """Li of the scene's integrator along each ray (rrt_radiance): o, d (n, 3) host arrays, d unit length; pixel (n, 2) of (x, y) or (n,)
+        packed y << 16 | x, and sample_num (n,) in 1 .. nsamp-1 name the sampler stream of each ray; weight 0 = dead ray (result 0).
+        Returns (n, 3) RGB, a view of `out` where a C-contiguous (>= n, 4) array of the renderer's dtype is given to write into."""
+        n = len(np.asarray(sample_num))
+        rs, keep = self._ray_samples(o, d, weight, diffs, pixel, sample_num)
+        if out is None:
+            out = np.zeros((n, 4), self.dtype)
+        assert out.dtype == self.dtype and out.flags.c_contiguous and out.shape[0] >= n and out.shape[1:] == (4,)
+        _check(A.lib().rrt_radiance(self._h, C.byref(rs), n, out.ctypes.data))
+        return out[:n, :3]
+
+    def render_rays(self, rect, s0, s1, rays, weight, p_film, film=None, stats=False, diffs=None):
+        """rrt_render_rays: the frame's film for sample numbers [s0, s1) of the rect's pixels, the camera replaced by the caller's samples in
+        camera_samples' layout [pixel][sample]: rays (n, 6) origin + unit direction, weight (n,) or None (= 1), p_film (n, 2) raster
+        coordinates. Returns the (H, W, 4) XYZ + weight film (+= into `film` where given)."""
+        W, H = self.scene.resolution
+        if film is None:
+            film = np.zeros((H, W, 4), self.dtype)
+        rays = np.asarray(rays)
+        rs, keep = self._ray_samples(rays[:, :3], rays[:, 3:6], weight, diffs)
+        pf = np.ascontiguousarray(p_film, self.dtype)
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_rays(self._h, r, s0, s1, C.byref(rs), pf.ctypes.data, film.ctypes.data, A.RRT_MEM_HOST, C.byref(st) if stats else None))
+        return (film, st) if stats else film
+
+    def radiance_device(self, ptrs6, pixel_ptr, sample_num_ptr, n, rgb4_ptr, weight_ptr=None, diff_ptrs12=None):
+        """rrt_radiance on device-resident arrays (raw pointers): ptrs6 = ox, oy, oz, dx, dy, dz; rgb4_ptr: n * 4 values, device memory."""
+        rs = A.RaySamples(A.RRT_MEM_DEVICE, self.precision, *ptrs6, weight_ptr)
+        if diff_ptrs12 is not None:
+            for k, name in enumerate(("rxo", "rxd", "ryo", "ryd")):
+                setattr(rs, name, (C.c_void_p * 3)(*diff_ptrs12[3 * k:3 * k + 3]))
+        rs.pixel, rs.sample_num = pixel_ptr, sample_num_ptr
+        _check(A.lib().rrt_radiance(self._h, C.byref(rs), n, rgb4_ptr))
+
+    def render_rays_device(self, rect, s0, s1, ptrs6, weight_ptr, p_film_ptr, film_ptr, stats=True):
+        """rrt_render_rays on device-resident samples into a device film (+=)."""
+        rs = A.RaySamples(A.RRT_MEM_DEVICE, self.precision, *ptrs6, weight_ptr)
+        st = A.RenderStats()
+        r = (C.c_int32 * 4)(*rect)
+        _check(A.lib().rrt_render_rays(self._h, r, s0, s1, C.byref(rs), p_film_ptr, film_ptr, A.RRT_MEM_DEVICE, C.byref(st) if stats else None))
+        return st
+
     def render_bands_device(self, rank, world, film_ptr, stats=True):
         """This rank's interleaved 16-row bands (partition.py) into a device film (+=)."""
         st = A.RenderStats()

@@ -28,7 +28,8 @@ template <typename R> struct ShadeBlock { static constexpr int n = 256; };
 #endif
 template <> struct ShadeBlock<float> { static constexpr int n = RRT_SHADE_BLOCK; };
 enum { ERR_SHADING_NORMAL = 1, ERR_BETA = 4, ERR_NULL_BSDF = 8, ERR_MIPMAP = 16, ERR_HALTON_DIMS = 32, ERR_ST_DIMS = 64, ERR_NO_LIGHTS = 128,
-       ERR_KIND_SET = 256 /* a material produced a lobe outside the shading kernel's kind set (dmath.hpp): host-side selection error */ };
+       ERR_KIND_SET = 256 /* a material produced a lobe outside the shading kernel's kind set (dmath.hpp): host-side selection error */,
+       ERR_INGEST = 512 /* k_ingest_rays: a pixel or sample_num of rrt_ray_samples outside the film / outside 1 .. nsamp-1 */ };
 static_assert(ERR_ST_DIMS == kErrStDims, "error bit shared with dmath.hpp");
 static_assert(ERR_HALTON_DIMS == kErrHaltonDims, "error bit shared with dmath.hpp");
 
@@ -693,6 +694,128 @@ __global__ void __launch_bounds__(kBlock) k_camera_dump(Pools<R> p, PassDesc pd,
     rr[0] = (double)ro.x; rr[1] = (double)ro.y; rr[2] = (double)ro.z;
     rr[3] = (double)rd.x; rr[4] = (double)rd.y; rr[5] = (double)rd.z;
   }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Caller-supplied rays (rrt_radiance, rrt_render_rays): the second producer of the pool state the integrators consume - k_ingest_rays leaves what
+// k_raygen + k_raygen_aux leave for a pass - and, for rrt_radiance, the second consumer of L beside the film kernels.
+// ------------------------------------------------------------------------------------------------------------
+// rrt_ray_samples on the device (staged there for a host-memory call). p_film set = rrt_render_rays: sample (x, y, sample_num) of the pass lies at
+// ((y - ry0) * rw + (x - rx0)) * ns_all + (sample_num - s0) of every array, the [pixel][sample] layout of rrt_camera_samples over the call's rect
+// (PassDesc::rx0 / ry0 / rw). p_film null = rrt_radiance: slot i of the pass is ray base + i, its sampler stream named by pixel / sample_num.
+template <typename R>
+struct RaySamples {
+  const R *o[3], *d[3];
+  const R* weight;                                // null = 1 everywhere
+  const R *rxo[3], *rxd[3], *ryo[3], *ryd[3];     // all null (rx = ry = the ray) or all set
+  const R* p_film;
+  const uint32_t *pixel, *sample_num;
+  uint64_t base;
+  uint32_t s0, ns_all;
+  // Workgroup shape: 2^pb_log2 pixels x (kBlock >> pb_log2) samples of the pass, pixels on the fast lanes. The caller's arrays run sample-fastest
+  // and the slots pixel-fastest, so a wave of one sample x 64 pixels would fetch one element from each of 64 runs ns_all elements apart - every
+  // 128-byte line fetched ns_all times over the launch, by workgroups too far apart to meet in a cache. With min(ns, 32) samples in the workgroup
+  // (the host picks the shape) its four waves read the same few contiguous runs within the lifetime of one workgroup, and the 8+ neighbouring
+  // pixels of a sample still make whole 128-byte lines of the 16-byte per-slot records (samp, L, differentials). rrt_radiance: 256 x 1, a plain
+  // coalesced copy.
+  uint32_t pb_log2;
+};
+// One thread per slot of a tile, kIngestTiles tiles per workgroup. check_only: nothing but the range check of pixel / sample_num is done (rrt_radiance on device-resident arrays
+// runs it over the whole batch first, so that a refused call has written nothing); the check itself is made in every launch, and a sample that
+// fails it is dead - no table of the sampler is ever indexed by an unchecked value. write_samp: as the camera kernels' (launch_raygen).
+constexpr uint32_t kIngestTiles = 4;   // pixel tiles per workgroup of k_ingest_rays: one queue reservation for all of them
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_ingest_rays(SceneDev<R> s, Pools<R> p, PassDesc pd, RaySamples<R> in, int enqueue, int write_samp, int check_only) {
+  const uint32_t pb = 1u << in.pb_log2, sb = (uint32_t)kBlock >> in.pb_log2;
+  const uint32_t sl = blockIdx.y * sb + (threadIdx.x >> in.pb_log2);
+  __shared__ uint32_t push_lds[kBlock / 64 + 2];
+  // The workgroup takes kIngestTiles tiles of pb pixels x sb samples and reserves queue space for their live samples with ONE atomic: every
+  // workgroup of the launch adds to the same counter, and those additions are served one after the other (measured at 1024^2 x 32 samples: 131 072
+  // reservations made the launch 1.5 ms long whatever it loaded or stored)
+  bool alive[kIngestTiles];
+  uint32_t slot[kIngestTiles], index[kIngestTiles], rank[kIngestTiles], total = 0;
+  V3<R> o[kIngestTiles], d[kIngestTiles];
+#pragma unroll
+  for (uint32_t k = 0; k < kIngestTiles; k++) {
+    const uint32_t pl = (blockIdx.x * kIngestTiles + k) * pb + (threadIdx.x & (pb - 1u));
+    alive[k] = false; slot[k] = 0; index[k] = 0;
+    if (pl < pd.npix && sl < pd.ns) {
+      slot[k] = sl * pd.npix + pl;
+      size_t i;
+      uint32_t px, py, sample_num;
+      R pfx, pfy;
+      bool ok = true;
+      if (in.p_film) {
+        pass_pixel(pd, pd.pix_begin + pl, &px, &py);
+        sample_num = pd.s_begin + sl;
+        i = ((size_t)(py - (uint32_t)pd.ry0) * (uint32_t)pd.rw + (px - (uint32_t)pd.rx0)) * in.ns_all + (sample_num - in.s0);
+        pfx = pfy = R(0);
+        if (write_samp) { pfx = in.p_film[2 * i]; pfy = in.p_film[2 * i + 1]; }
+      } else {
+        i = (size_t)in.base + slot[k];
+        const uint32_t pw = in.pixel[i];
+        px = pw & 0xffffu; py = pw >> 16; sample_num = in.sample_num[i];
+        ok = px < (uint32_t)s.xres && py < (uint32_t)s.yres && sample_num >= 1u && sample_num < s.nsamp;
+        if (!ok) atomicOr(s.err, (uint32_t)ERR_INGEST);
+        pfx = (R)px + R(0.5); pfy = (R)py + R(0.5);   // no film in rrt_radiance: never written (write_samp = 0)
+      }
+      if (!check_only) {
+        const R w = in.weight ? in.weight[i] : R(1);
+        alive[k] = ok && w > R(0);
+        p.weight[slot[k]] = alive[k] ? w : R(0);
+        if (write_samp) p.samp[slot[k]] = mk4<R>(pfx, pfy, R(0), R(0));   // only the wide film kernels read p_film
+        if (alive[k]) {   // (a dead sample's index and radiance record are never read: the queue, film_sample_radiance, k_radiance_out)
+          if (s.sampler_type == 1u) index[k] = ((py * (uint32_t)s.xres + px) << 10) | sample_num;   // as k_raygen forms them
+          else index[k] = halton_pixel_offset(s, px, py) + sample_num * s.stride;
+          p.hindex[slot[k]] = index[k];
+          p.L[slot[k]] = mk4<R>(R(0), R(0), R(0), R(0));
+          o[k] = V3<R>(in.o[0][i], in.o[1][i], in.o[2][i]); d[k] = V3<R>(in.d[0][i], in.d[1][i], in.d[2][i]);
+          if (p.rdx_o) {
+            V3<R> rxo = o[k], rxd = d[k], ryo = o[k], ryd = d[k];
+            if (in.rxo[0]) {
+              rxo = V3<R>(in.rxo[0][i], in.rxo[1][i], in.rxo[2][i]); rxd = V3<R>(in.rxd[0][i], in.rxd[1][i], in.rxd[2][i]);
+              ryo = V3<R>(in.ryo[0][i], in.ryo[1][i], in.ryo[2][i]); ryd = V3<R>(in.ryd[0][i], in.ryd[1][i], in.ryd[2][i]);
+            }
+            p.rdx_o[slot[k]] = mk4<R>(rxo.x, rxo.y, rxo.z, R(0)); p.rdx_d[slot[k]] = mk4<R>(rxd.x, rxd.y, rxd.z, R(0));
+            p.rdy_o[slot[k]] = mk4<R>(ryo.x, ryo.y, ryo.z, R(0)); p.rdy_d[slot[k]] = mk4<R>(ryd.x, ryd.y, ryd.z, R(0));
+          }
+        }
+      }
+    }
+    if (!check_only) {   // (block-uniform) rank among the workgroup's live samples: tiles in turn, block order inside a tile
+      uint32_t n_tile;
+      rank[k] = total + block_rank(alive[k], push_lds, &n_tile);
+      total += n_tile;
+    }
+  }
+  if (check_only) return;
+  // camera rays = the weights > 0: where they are enqueued that is the queue's own count, copied by k_ingest_count behind this launch
+  uint32_t* const counter = &p.counters[enqueue ? C_ACTIVE : C_CAMERA_RAYS];
+  if (threadIdx.x == 0) push_lds[kBlock / 64 + 1] = total ? atomicAdd(counter, total) : 0u;
+  __syncthreads();
+  const uint32_t first = push_lds[kBlock / 64 + 1];
+  if (!enqueue) return;
+#pragma unroll
+  for (uint32_t k = 0; k < kIngestTiles; k++) {
+    if (!alive[k]) continue;
+    const uint32_t q = first + rank[k];
+    p.q_active[q] = QEnt{slot[k], s.cam_db, index[k], 0u};   // camera dimensions consumed, bounce 0
+    p.path[q] = mk4<R>(R(1), R(1), R(1), R(1));
+    store_ray<R>(p.ray_o, p.ray_d, q, o[k], V3<R>(), d[k], Const<R>::inf, -1);
+  }
+}
+static __global__ void k_ingest_count(uint32_t* c) { c[C_CAMERA_RAYS] = c[C_ACTIVE]; }
+
+// rrt_radiance: Li of the first n slots as {r, g, b, 0}, one 128-bit (f64: 256-bit) load and store per thread; a dead slot's record is not the
+// integrator's to write, so it is answered here
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_radiance_out(Pools<R> p, typename Vec4T<R>::type* rgb4, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  typename Vec4T<R>::type l = mk4<R>(R(0), R(0), R(0), R(0));
+  if (p.weight[i] > R(0)) l = p.L[i];
+  l.w = R(0);
+  rgb4[i] = l;
 }
 
 // ------------------------------------------------------------------------------------------------------------

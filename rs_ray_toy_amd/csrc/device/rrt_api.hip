@@ -86,6 +86,41 @@ int rrt_render_rect(rrt_handle* h, const int32_t rect[4], void* film_xyzw, int f
   return guarded([&]() { h->impl->render_rect(rect, film_xyzw, film_mem, stats); });
 }
 
+namespace {
+// the caller's own description of its rays, wrong whichever handle it comes with: checked before any device work, each with its own message
+int ray_samples_check(const std::string& name, const rrt_ray_samples* r, bool with_stream) {
+  auto bad = [&](const char* what) { rrt::set_last_error(name + ": " + what); return (int)RRT_EINVAL; };
+  if (!r) return bad("null ray description (rrt_ray_samples)");
+  if (r->mem != RRT_MEM_HOST && r->mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (!r->ox || !r->oy || !r->oz || !r->dx || !r->dy || !r->dz) return bad("null ray array");
+  int set = 0;
+  for (int k = 0; k < 3; k++) set += (r->rxo[k] != nullptr) + (r->rxd[k] != nullptr) + (r->ryo[k] != nullptr) + (r->ryd[k] != nullptr);
+  if (set != 0 && set != 12) return bad("ray differentials partly set (all twelve arrays or none)");
+  if (with_stream && (!r->pixel || !r->sample_num)) return bad("null pixel or sample_num array");
+  return RRT_OK;
+}
+}  // namespace
+
+int rrt_radiance(rrt_handle* h, const rrt_ray_samples* rays, size_t n, void* rgb4) {
+  if (const int rc = ray_samples_check("rrt_radiance", rays, true); rc != RRT_OK) return rc;
+  if (!rgb4) { rrt::set_last_error("rrt_radiance: null output"); return RRT_EINVAL; }
+  if (n == 0) { rrt::set_last_error("rrt_radiance: n must be > 0"); return RRT_EINVAL; }
+  if (n > 0x7fffffffu) { rrt::set_last_error("rrt_radiance: batch too large"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_radiance: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->radiance(rays, n, rgb4); });
+}
+
+int rrt_render_rays(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_xyzw, int film_mem,
+                    rrt_render_stats* stats) {
+  if (const int rc = ray_samples_check("rrt_render_rays", rays, false); rc != RRT_OK) return rc;
+  if (!rect) { rrt::set_last_error("rrt_render_rays: null rect"); return RRT_EINVAL; }
+  if (!p_film) { rrt::set_last_error("rrt_render_rays: null p_film"); return RRT_EINVAL; }
+  if (!film_xyzw) { rrt::set_last_error("rrt_render_rays: null film"); return RRT_EINVAL; }
+  if (film_mem != RRT_MEM_HOST && film_mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_rays: bad film_mem"); return RRT_EINVAL; }
+  if (!h) { rrt::set_last_error("rrt_render_rays: null handle"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_rays(rect, s0, s1, rays, p_film, film_xyzw, film_mem, stats); });
+}
+
 int rrt_render_bands(rrt_handle* h, int rank, int world, void* film_xyzw, int film_mem, rrt_render_stats* stats) {
   if (!h || !film_xyzw) { rrt::set_last_error("rrt_render_bands: null argument"); return RRT_EINVAL; }
   if (film_mem != RRT_MEM_HOST && film_mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_bands: bad film_mem"); return RRT_EINVAL; }

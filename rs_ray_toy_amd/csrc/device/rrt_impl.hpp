@@ -43,6 +43,8 @@ struct HandleBase {
   virtual void trace_any(const rrt_rays* rays, size_t n, uint8_t* occluded) = 0;
   virtual void camera_samples(const int32_t rect[4], uint64_t s0, uint64_t s1, double* dims5, double* ray_od6, double* weight) = 0;
   virtual void render_rect(const int32_t rect[4], void* film, int film_mem, rrt_render_stats* stats) = 0;
+  virtual void radiance(const rrt_ray_samples* rays, size_t n, void* rgb4) = 0;
+  virtual void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film, int film_mem, rrt_render_stats* stats) = 0;   // p_film in rays->mem
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
   virtual void render_end(rrt_render_stats* stats) = 0;
@@ -319,6 +321,157 @@ class Handle : public HandleBase {
     HIP_CHECK(hipStreamSynchronize(st_));
   }
 
+  // ---- radiance along caller-supplied rays: rrt_radiance, rrt_render_rays ------------------------------------------------------------------------
+  // k_ingest_rays in place of the camera kernels, then pass_integrate as a frame's pass runs it; what follows is k_radiance_out (rrt_radiance) or the
+  // frame's own film part (rrt_render_rays). No camera kernel has run for these passes, so the first closest-hit launch goes the generic queue way:
+  // no tile trees, no root cull, no film-record runs (RaysPassState, put back by its RaygenStateGuard). Horizon tables, shadow lists, the two shadow
+  // queues and shading compaction depend on geometry only and stay on.
+  struct RaysPassState : RaygenStateGuard {
+    explicit RaysPassState(Handle* hh) : RaygenStateGuard(hh) { hh->tt_pass_ok_ = false; hh->film_runs_ok_ = false; hh->scene_.root_cull = 0u; }
+  };
+  // the caller's arrays as the kernel takes them: the pointers themselves for device memory, else copies in `stage` (n elements each)
+  struct RayStage { DevBuf<R> r; DevBuf<uint32_t> u; };
+  RaySamples<R> ray_samples_device(const rrt_ray_samples* rays, const void* p_film, size_t n, bool with_stream, RayStage& stage) {
+    const bool diffs = rays->rxo[0] != nullptr && tex_depth_ > 0;   // read only when the scene has textured materials
+    const void* real[20];
+    int nr = 0;
+    const void* const od[6] = {rays->ox, rays->oy, rays->oz, rays->dx, rays->dy, rays->dz};
+    for (int k = 0; k < 6; k++) real[nr++] = od[k];
+    real[nr++] = rays->weight;
+    for (int k = 0; k < 3; k++) real[nr++] = diffs ? rays->rxo[k] : nullptr;
+    for (int k = 0; k < 3; k++) real[nr++] = diffs ? rays->rxd[k] : nullptr;
+    for (int k = 0; k < 3; k++) real[nr++] = diffs ? rays->ryo[k] : nullptr;
+    for (int k = 0; k < 3; k++) real[nr++] = diffs ? rays->ryd[k] : nullptr;
+    const void* pf = p_film;
+    const void* words[2] = {with_stream ? rays->pixel : nullptr, with_stream ? rays->sample_num : nullptr};
+    if (rays->mem != RRT_MEM_DEVICE) {
+      size_t need = p_film ? 2 * n : 0;
+      for (int k = 0; k < nr; k++) if (real[k]) need += n;
+      stage.r.alloc(need);
+      R* dst = stage.r.p;
+      for (int k = 0; k < nr; k++) if (real[k]) { HIP_CHECK(hipMemcpyAsync(dst, real[k], n * sizeof(R), hipMemcpyHostToDevice, st_)); real[k] = dst; dst += n; }
+      if (p_film) { HIP_CHECK(hipMemcpyAsync(dst, p_film, 2 * n * sizeof(R), hipMemcpyHostToDevice, st_)); pf = dst; }
+      if (with_stream) {
+        stage.u.alloc(2 * n);
+        for (int k = 0; k < 2; k++) { HIP_CHECK(hipMemcpyAsync(stage.u.p + k * n, words[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, st_)); words[k] = stage.u.p + k * n; }
+      }
+    }
+    RaySamples<R> in{};
+    for (int k = 0; k < 3; k++) {
+      in.o[k] = (const R*)real[k]; in.d[k] = (const R*)real[3 + k];
+      in.rxo[k] = (const R*)real[7 + k]; in.rxd[k] = (const R*)real[10 + k]; in.ryo[k] = (const R*)real[13 + k]; in.ryd[k] = (const R*)real[16 + k];
+    }
+    in.weight = (const R*)real[6];
+    in.p_film = (const R*)pf;
+    in.pixel = (const uint32_t*)words[0]; in.sample_num = (const uint32_t*)words[1];
+    return in;
+  }
+  // what both calls refuse before any device work
+  void check_ray_samples(const char* who, const rrt_ray_samples* rays) const {
+    const std::string w(who);
+    if (pending_) throw std::invalid_argument(w + ": a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (rays->precision != precision()) throw std::invalid_argument(w + ": ray precision must match the handle");
+  }
+  void launch_ingest(const PassDesc& pd, RaySamples<R> in, int check_only) {
+    // workgroup shape (RaySamples::pb_log2): the next power of two >= min(ns, 32) samples, the rest of the 256 threads pixels
+    uint32_t sb = 1;
+    while (sb < std::min<uint32_t>(pd.ns, 32u)) sb <<= 1;
+    const uint32_t pb = (uint32_t)kBlock / sb;
+    in.pb_log2 = 0;
+    while ((1u << in.pb_log2) < pb) in.pb_log2++;
+    const dim3 g((pd.npix + pb * kIngestTiles - 1) / (pb * kIngestTiles), (pd.ns + sb - 1) / sb);
+    const int enqueue = desc_.integrator.type != RRT_INT_AO ? 1 : 0;
+    hipLaunchKernelGGL((k_ingest_rays<R>), g, dim3(kBlock), 0, st_, scene_, pool_, pd, in, enqueue, in.p_film != nullptr && wide_filter() ? 1 : 0, check_only);
+    if (enqueue && !check_only) hipLaunchKernelGGL(k_ingest_count, dim3(1), dim3(1), 0, st_, counters_.p);
+    HIP_CHECK(hipGetLastError());
+  }
+  bool ingest_refused() {
+    uint32_t err = 0;
+    HIP_CHECK(hipStreamSynchronize(st_));
+    HIP_CHECK(hipMemcpy(&err, counters_.p + C_ERROR, sizeof(err), hipMemcpyDeviceToHost));
+    return (err & ERR_INGEST) != 0u;
+  }
+  void radiance(const rrt_ray_samples* rays, size_t n, void* rgb4) override {
+    using V4 = typename Vec4T<R>::type;
+    check_ray_samples("rrt_radiance", rays);
+    const rrt_film& f = desc_.film;
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel;
+    const bool host = rays->mem != RRT_MEM_DEVICE;
+    if (host) {   // device-resident arrays: the same check by k_ingest_rays, below
+      for (size_t i = 0; i < n; i++) {
+        const uint32_t pw = rays->pixel[i], sn = rays->sample_num[i];
+        if ((int32_t)(pw & 0xffffu) >= f.xres || (int32_t)(pw >> 16) >= f.yres) throw std::invalid_argument("rrt_radiance: pixel outside the film (ray " + std::to_string(i) + ")");
+        if (sn < 1 || sn >= nsamp) throw std::invalid_argument("rrt_radiance: sample_num outside 1 .. nsamp-1 (ray " + std::to_string(i) + ")");
+      }
+    }
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    RaysPassState guard(this);
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
+    if (totals_.n == 0) totals_.alloc(12);
+    HIP_CHECK(hipMemsetAsync(totals_.p, 0, 12 * sizeof(unsigned long long), st_));
+    const size_t chunk = pool_slots(n);
+    ensure_pools(chunk);
+    RayStage stage;
+    RaySamples<R> in = ray_samples_device(rays, nullptr, n, true, stage);
+    const PassDesc whole{0, 0, 1, 0u, (uint32_t)n, 1u, 1u, 1u << 30, 1u, 0u, 0u};
+    if (!host) {
+      launch_ingest(whole, in, 1);
+      if (ingest_refused()) {
+        HIP_CHECK(hipMemsetAsync(counters_.p + C_ERROR, 0, sizeof(uint32_t), st_));
+        throw std::invalid_argument("rrt_radiance: a pixel outside the film or a sample_num outside 1 .. nsamp-1");
+      }
+    }
+    DevBuf<V4> out_stage;
+    if (host) out_stage.alloc(n);
+    V4* const out = host ? out_stage.p : (V4*)rgb4;
+    FrameRec fr;   // no statistics: no events
+    for (size_t base = 0; base < n; base += chunk) {
+      PassDesc pd = whole;
+      pd.npix = (uint32_t)std::min(chunk, n - base);
+      in.base = base;
+      hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+      launch_ingest(pd, in, 0);
+      pass_integrate(pd, 0u, fr);
+      hipLaunchKernelGGL((k_radiance_out<R>), dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, pool_, out + base, pd.npix);
+      HIP_CHECK(hipGetLastError());
+    }
+    if (host) HIP_CHECK(hipMemcpyAsync(rgb4, out_stage.p, n * sizeof(V4), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    HIP_CHECK(hipStreamSynchronize(st2_));
+    check_device_errors();
+  }
+  void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_user, int film_mem, rrt_render_stats* stats) override {
+    check_ray_samples("rrt_render_rays", rays);
+    check_rect("rrt_render_rays: rect outside the film", rect);
+    if (s0 < 1 || s1 > desc_.sampler.samples_per_pixel || s0 >= s1) throw std::invalid_argument("rrt_render_rays: sample range outside [1, nsamp) or empty");
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    check_no_crop();
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = (size_t)(rect[3] - rect[1]), rpix = rw * rh, ns_all = (size_t)(s1 - s0);
+    RaysPassState guard(this);
+    frame_setup(false, rpix * ns_all, /*tile_trees=*/false);
+    RayStage stage;
+    RaySamples<R> in = ray_samples_device(rays, p_film, rpix * ns_all, false, stage);
+    in.s0 = (uint32_t)s0; in.ns_all = (uint32_t)ns_all;
+    FrameRec fr;
+    fr.timing = stats != nullptr; fr.camera_samples = (uint64_t)rpix * ns_all;
+    if (fr.timing) { fr.ev_begin = fr.make(); fr.ev_end = fr.make(); HIP_CHECK(hipEventRecord(fr.ev_begin, st_)); }
+    for_each_pass(rect, 1u << 30, 1, 0, rw, rh, s0 - 1, s1 - 1, cap_, [&](const PassDesc& pd) {
+      hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+      const size_t e = tick(fr, 0);
+      launch_ingest(pd, in, 0);
+      tock(fr, e);
+      pass_integrate(pd, 0u, fr);
+      pass_film(pd, nullptr, rect, false, 0u, fr);
+    });
+    if (fr.timing) HIP_CHECK(hipEventRecord(fr.ev_end, st_));
+    merge_out(film_user, nullptr, film_mem, true);
+    HIP_CHECK(hipStreamSynchronize(st2_));
+    check_device_errors();
+    if (stats) frame_stats(fr, stats);
+  }
+
   // ---- the frame: SamplerIntegrator::si_render (integrator/mod.rs:48-139) over a pixel rect -------------------
   void render_rect(const int32_t rect[4], void* film_user, int film_mem, rrt_render_stats* stats) override {
     render_impl(rect, 1u << 30, 1, 0, film_user, film_mem, stats);
@@ -502,7 +655,7 @@ class Handle : public HandleBase {
   }
   // internal full-frame film (zeroed; merged into the caller's buffer at the end), the moments buffer beside it in a moments frame, the statistics'
   // totals, and pools for `want` slots or what max_paths allows
-  void frame_setup(bool with_moments, size_t want) {
+  void frame_setup(bool with_moments, size_t want, bool tile_trees = true) {
     const size_t W = (size_t)desc_.film.xres, H = (size_t)desc_.film.yres;
     if (film_.n != W * H * 4) film_.alloc(W * H * 4);
     HIP_CHECK(hipMemsetAsync(film_.p, 0, W * H * 4 * sizeof(R), st_));
@@ -514,6 +667,18 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemsetAsync(totals_.p, 0, 12 * sizeof(unsigned long long), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
 
+    const size_t P = pool_slots(want);
+    ensure_pools(P);
+    if (passes_n_ > 0) passes_setup(P);
+    if constexpr (std::is_same<R, float>::value) {
+      if (tile_trees && tt_state_ == 0 && tile_trees_on_) {
+        build_tile_trees();
+        HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));   // the census ran the camera kernels
+      }
+    }
+  }
+  // the slots a pass of a call that wants `want` of them may hold
+  size_t pool_slots(size_t want) {
     size_t P = std::min(max_paths_, std::max<size_t>(want, 64));
     if ((desc_.integrator.type == RRT_INT_DIRECT || desc_.integrator.type == RRT_INT_DEBUG) && (has_transmissive_ || tex_depth_ > 0) && desc_.integrator.max_depth > kTreeMax) {
       // k_direct_tree keeps (max_depth - kTreeMax) overflow frames per slot of a pass: a quarter of the free memory at most
@@ -522,14 +687,7 @@ class Handle : public HandleBase {
       const size_t per_slot = (size_t)(desc_.integrator.max_depth - kTreeMax) * sizeof(TreeFrame<R>);
       P = std::max<size_t>(64, std::min(P, (free_b / 4) / per_slot));
     }
-    ensure_pools(P);
-    if (passes_n_ > 0) passes_setup(P);
-    if constexpr (std::is_same<R, float>::value) {
-      if (tt_state_ == 0 && tile_trees_on_) {
-        build_tile_trees();
-        HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));   // the census ran the camera kernels
-      }
-    }
+    return P;
   }
   // rrt_render_passes: the passes' internal films (zeroed), the table, one radiance plane per pass and a mask array per shadow queue. The planes come
   // after the pools: a pool pass of such a frame holds at most pass_cap_ slots - what the pools hold, or what half of the memory still free lets the
@@ -576,41 +734,50 @@ class Handle : public HandleBase {
       }
     }
   }
+  // HIP events around a launch of a frame whose statistics are wanted (FrameRec::timing), under the category frame_stats() adds it to
+  size_t tick(FrameRec& fr, int cat, hipStream_t stream = nullptr) {
+    if (!fr.timing) return (size_t)0;
+    const hipEvent_t a = fr.make(), b = fr.make();
+    HIP_CHECK(hipEventRecord(a, stream ? stream : st_));
+    fr.evs.push_back({cat, {a, b}});
+    return fr.evs.size() - 1;
+  }
+  void tock(FrameRec& fr, size_t id, hipStream_t stream = nullptr) { if (fr.timing) HIP_CHECK(hipEventRecord(fr.evs[id].second.second, stream ? stream : st_)); }
   // one pass: camera kernels, the integrator's launches, the film kernel. list: the tiles of a listed pass (list_pixel; box filter of radius 0.5 and
-  // moments only, no tile trees, no film records), NULL for a pass over the rect's own pixel grid
-  void run_pass(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, FrameRec& fr_ref) {
+  // moments only, no tile trees, no film records), NULL for a pass over the rect's own pixel grid. The three parts meet in pool state only (q_active,
+  // counters[C_ACTIVE], ray_o / ray_d, path, L, weight, samp, rdx_*): rrt_radiance and rrt_render_rays put k_ingest_rays in place of the first part.
+  void run_pass(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, FrameRec& fr) {
+    // rrt_render_frame_aov: the leading samples of this pass that the feature buffers take (a pass that begins beyond the prefix: none)
+    const uint64_t s_off = (uint64_t)pd.s_begin - 1;
+    const uint32_t aov_ns = (!list && aov_prefix_ > s_off) ? (uint32_t)std::min<uint64_t>(pd.ns, aov_prefix_ - s_off) : 0u;
+    pass_camera(pd, list, with_moments, fr);
+    pass_integrate(pd, aov_ns, fr);
+    pass_film(pd, list, rect, with_moments, aov_ns, fr);
+  }
+  // first part: the camera kernels fill the pools
+  void pass_camera(const PassDesc& pd, const uint32_t* list, bool with_moments, FrameRec& fr) {
+    const size_t nslots = (size_t)pd.npix * pd.ns;
+    const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+    const size_t e = tick(fr, 0);
+    launch_raygen(pd, grid, nullptr, desc_.integrator.type != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments && passes_n_ == 0, list);
+    // rrt_render_passes: this pool pass's slots of every plane start at 0, as raygen starts L (on the main stream: the shadow stream waits for shading)
+    for (uint32_t k = 0; k < passes_n_; k++) HIP_CHECK(hipMemsetAsync(pool_.pass_L + (size_t)k * pool_.pass_stride, 0, nslots * sizeof(typename Vec4T<R>::type), st_));
+    tock(fr, e);
+  }
+  // second part: the integrator's launches over the queue the first part left, until every slot's L is final. aov_ns: see run_pass
+  void pass_integrate(const PassDesc& pd, uint32_t aov_ns, FrameRec& fr_ref) {
     FrameRec* const fr = &fr_ref;
-    const rrt_film& f = desc_.film;
-    const bool wide = wide_filter();
-    const FilmWindow win = film_window(rect);
-    const bool timing = fr->timing;
-    auto& evs = fr->evs;
-    auto tick = [&](int cat, hipStream_t stream = nullptr) {
-      if (!timing) return (size_t)0;
-      const hipEvent_t a = fr->make(), b = fr->make();
-      HIP_CHECK(hipEventRecord(a, stream ? stream : st_));
-      evs.push_back({cat, {a, b}});
-      return evs.size() - 1;
-    };
-    auto tock = [&](size_t id, hipStream_t stream = nullptr) { if (timing) HIP_CHECK(hipEventRecord(evs[id].second.second, stream ? stream : st_)); };
+    auto tick = [&](int cat, hipStream_t stream = nullptr) { return this->tick(fr_ref, cat, stream); };
+    auto tock = [&](size_t id, hipStream_t stream = nullptr) { this->tock(fr_ref, id, stream); };
     uint64_t& n_closest_launch = fr->n_closest_launch;
     uint64_t& n_any_launch = fr->n_any_launch;
     const int integ = desc_.integrator.type;
     const int max_depth = desc_.integrator.max_depth;
-    const size_t npix = pd.npix;
-    const uint64_t ns = pd.ns;
-    const size_t nslots = npix * (size_t)ns;
+    const size_t nslots = (size_t)pd.npix * pd.ns;
     const uint32_t grid = (uint32_t)((nslots + kBlock - 1) / kBlock);
     const uint32_t sgrid = (uint32_t)((nslots + ShadeBlock<R>::n - 1) / ShadeBlock<R>::n);
-    // rrt_render_frame_aov: the leading samples of this pass that the feature buffers take (a pass that begins beyond the prefix: none)
-    const uint64_t s_off = (uint64_t)pd.s_begin - 1;
-    const uint32_t aov_ns = (!list && aov_prefix_ > s_off) ? (uint32_t)std::min<uint64_t>(ns, aov_prefix_ - s_off) : 0u;
-    hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
-    size_t e = tick(0);
-    launch_raygen(pd, grid, nullptr, integ != RRT_INT_AO ? 1 : 0, true, /*film_records=*/!with_moments && passes_n_ == 0, list);
-    // rrt_render_passes: this pool pass's slots of every plane start at 0, as raygen starts L (on the main stream: the shadow stream waits for shading)
-    for (uint32_t k = 0; k < passes_n_; k++) HIP_CHECK(hipMemsetAsync(pool_.pass_L + (size_t)k * pool_.pass_stride, 0, nslots * sizeof(typename Vec4T<R>::type), st_));
-    tock(e);
+    size_t e = 0;
     hipLaunchKernelGGL(k_accumulate_camera, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p, (integ == RRT_INT_PATH && max_depth <= 0) ? 0 : 1);
     if (integ == RRT_INT_PATH) {
       // bounce b: closest -> shade (NEE + BSDF sample + RR) -> shadow rays; paths live while bounces < max_depth
@@ -706,7 +873,16 @@ class Handle : public HandleBase {
       }
       }
     }
-    e = tick(4);
+    HIP_CHECK(hipGetLastError());
+  }
+  // third part: the film kernel reads L, weight and samp by slot
+  void pass_film(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, uint32_t aov_ns, FrameRec& fr) {
+    const rrt_film& f = desc_.film;
+    const bool wide = wide_filter();
+    const FilmWindow win = film_window(rect);
+    const size_t npix = pd.npix;
+    const uint64_t ns = pd.ns;
+    const size_t e = tick(fr, 4);
     // rrt_render_passes: after the frame's own film (k = -1) the same kernel once per pass, with L pointing at the pass's radiance plane, into the
     // pass's internal film
     typename Vec4T<R>::type* const frame_L = pool_.L;
@@ -730,7 +906,7 @@ class Handle : public HandleBase {
       }
     }
     pool_.L = frame_L;
-    tock(e);
+    tock(fr, e);
     if (aov_ns > 0) launch_aov_gather_frame(pd, aov_ns, win);
     HIP_CHECK(hipGetLastError());
   }
