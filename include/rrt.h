@@ -460,6 +460,40 @@ typedef struct rrt_aov {
 } rrt_aov;            /* any plane may be NULL (not produced); all NULL = RRT_EINVAL */
 int rrt_render_aov(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples, rrt_aov* out);
 
+/* Ambient occlusion and bent normals beside the film: what AOIntegrator::li (ao.rs:65-96) means, per camera sample. (The reference's own
+ * AO frame is black: ao.rs:74 asks the tile sampler for a 2D array only the throw-away pre_sampler requested, Q30 - and a frame of an AO
+ * scene stays black here too. This call is the pass itself, on scenes of every integrator type.) Which samples run is rrt_render_aov's,
+ * word for word: the camera samples rrt_render_rect takes for the rect's pixels, rank / world = bands, max_samples, live = camera weight
+ * > 0, fw = the film's own filter weight, full-frame W*H*4 planes of the handle's precision in host or device memory, added to (+=), no
+ * Q2 and no Q3 tripling, and the handle is left as it was. Per live sample whose camera ray (o, d) hits, with the interaction's fields
+ * as they are after the instance transform:
+ *   n_g = the geometric normal (not normalised under a non-rigid instance), n = faceforward(n_g, -d), s = normalize(dpdu) with the
+ *   GEOMETRIC dpdu (triangle.rs:268-293 / sphere.rs, not shading.dpdu), t = cross(n_g, s) - the un-flipped normal, as ao.rs:76 has it;
+ *   draw i = 0 .. n_samples-1: u_i = the i-th get_2d() of the sample's stream after get_camerasample (HaltonSampler: dimensions 5 + 2i
+ *   and 6 + 2i of the sample's index); wi_local = cosine_sample_hemisphere(u_i), pdf = |z| / pi (cos_sample != 0) or
+ *   uniform_sample_hemisphere(u_i), pdf = 1 / (2 pi) (sampling.rs:245-303); wi = s x + t y + n z; the ray isect.spawn_ray(wi): origin p,
+ *   direction d_i = normalize(wi), t_max = inf (Q8), traced as the integrators' spawned rays are (in fp32: start triangle excluded,
+ *   double-float origin) and answered by BVHAccel::intersect_p (Q11 included); a free ray adds a_i = dot(wi, n) / (pdf * n_samples).
+ *   A draw with pdf == 0 (cosine mode, z == 0) is dropped: ao.rs would form 0 / 0 there.
+ *   a = sum a_i in draw order, b = sum a_i * d_i over the free rays. The reference's scale is kept: a fully open point has a = pi in
+ *   cosine mode (resolve_ao in Python divides by pi and by the weights).
+ * Cost (config 4 at 1024^2, fp32, device planes, max_samples 8, 16 draws, profiles/ao_time.json): 11.3 ms against 2.25 ms for rrt_render_aov over
+ * the same samples; 7.6 ms of it are the 16 any-hit launches (21.7 M rays, 2.85 G rays/s), 1.4 ms the 16 launches that make the rays.
+ * No distance limit is offered: under Q9 / Q10 t_max prunes boxes and nothing else. Errors, before any device work: RRT_EINVAL for NULL
+ * arguments, both planes NULL, n_samples outside 1 .. 256 (5 + 2 n stays below the sampler's 1000 dimensions), a rect outside the film,
+ * bad rank / world, a precision that is not the handle's, or a frame in flight; RRT_EUNSUP, the reason named, for the StratifiedSampler
+ * (its draws past `dimension` are the [-1, 1) generator of Q25); RRT_EUNSUP / RRT_EPANIC as rrt_render_aov gives for the scene. */
+typedef struct rrt_ao_params { int32_t n_samples; int32_t cos_sample; } rrt_ao_params;
+void rrt_ao_defaults(const rrt_handle*, rrt_ao_params*);   /* the scene's Integrator.{n_samples, cos_sample} where its type is AO, else 64 / 1 */
+typedef struct rrt_ao {
+  int32_t mem;        /* RRT_MEM_* of the planes                                                                     */
+  int32_t precision;  /* must equal the handle's                                                                     */
+  void* ao;           /* W*H*4: sum fw*a, sum fw*a*a, sum fw over hit samples, sum fw over live samples               */
+  void* bent;         /* W*H*4: sum fw*b.x, .y, .z, sum fw over hit samples                                           */
+} rrt_ao;             /* either plane may be NULL (not produced); both NULL = RRT_EINVAL */
+int rrt_render_ao(rrt_handle*, const int32_t rect[4], int rank, int world, uint64_t max_samples,
+                  const rrt_ao_params* params /* NULL = rrt_ao_defaults */, rrt_ao* out);
+
 /* Feature buffers through mirrors and glass (no counterpart in the reference): rrt_render_aov's planes with the record of the first
  * non-specular surface along the chain of perfectly specular bounces a camera ray starts - what a denoiser wants on a wall mirror or a
  * window, which first-hit planes show as one flat surface. rect, rank / world, max_samples, the planes' layout, the += semantics, live

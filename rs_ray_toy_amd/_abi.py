@@ -163,6 +163,14 @@ class Aov(C.Structure):
                 ("depth", C.c_void_p)]
 
 
+class AoParams(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("cos_sample", C.c_int32)]
+
+
+class Ao(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32), ("ao", C.c_void_p), ("bent", C.c_void_p)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
                 ("sigma_depth", C.c_double)]
@@ -218,6 +226,8 @@ PROTOTYPES = {
     "rrt_render_end_stats": (C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     "rrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.POINTER(Aov)]),
     "rrt_render_aov_follow": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(Aov)]),
+    "rrt_ao_defaults": (None, [C.c_void_p, C.POINTER(AoParams)]),
+    "rrt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64, C.POINTER(AoParams), C.POINTER(Ao)]),
     "rrt_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
     "rrt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Aov), C.POINTER(DenoiseParams), C.c_void_p]),
     "rrt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),

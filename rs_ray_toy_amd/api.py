@@ -313,6 +313,21 @@ class Renderer:
             _check(A.lib().rrt_render_aov(self._h, r, rank, world, max_samples, C.byref(aov)))
         return out
 
+    # ambient occlusion and bent normals (rrt_render_ao): the raw filtered sums, (H, W, 4) each; resolve_ao() divides them out
+    def render_ao(self, rect=None, max_samples=0, rank=0, world=1, n_samples=None, cos_sample=None, planes=("ao", "bent")):
+        """n_samples / cos_sample: None = rrt_ao_defaults (the scene's own where its integrator is AO, else 64 / cosine)."""
+        W, H = self.scene.resolution
+        rect = rect or (0, 0, W, H)
+        out = {k: np.zeros((H, W, 4), self.dtype) for k in planes}
+        ptr = {k: (out[k].ctypes.data if k in out else None) for k in ("ao", "bent")}
+        ao = A.Ao(A.RRT_MEM_HOST, self.precision, ptr["ao"], ptr["bent"])
+        prm = A.AoParams()
+        A.lib().rrt_ao_defaults(self._h, C.byref(prm))
+        if n_samples is not None: prm.n_samples = int(n_samples)
+        if cos_sample is not None: prm.cos_sample = 1 if cos_sample else 0
+        _check(A.lib().rrt_render_ao(self._h, (C.c_int32 * 4)(*rect), rank, world, max_samples, C.byref(prm), C.byref(ao)))
+        return out
+
     # rrt_render_moments: the frame of render() / render_bands() and the sample-variance plane {S1, S2, S0, S3} beside it; resolve_moments() divides it out
     def render_moments(self, rect=None, rank=0, world=1, film=None, moments=None, stats=False):
         """-> (film, moments[, stats]): both (H, W, 4) host arrays of the handle's precision, added to (+=) where given."""
@@ -665,6 +680,34 @@ def resolve_aov(aov):
     return dict(albedo=albedo, normal=normal, depth=depth, coverage=coverage)
 
 
+def resolve_ao(planes):
+    """The sums of Renderer.render_ao -> dict(ao (H, W) in [0, 1]: the mean of a / pi over the hit samples (1 = fully open, 0 where nothing
+    is hit; the uniform mode's estimate can pass 1 and is clipped), ao_var (H, W): the weighted sample variance of a / pi over the hit
+    samples, bent (H, W, 3): the unit bent normal (0 where nothing is hit or no ray is free; only with the "bent" plane), coverage (H, W) =
+    w_hit / w_live)."""
+    ao = np.asarray(planes["ao"], np.float64)
+    w_hit, w_live = ao[..., 2], ao[..., 3]
+    hit, live = w_hit != 0, w_live != 0
+    wh = np.where(hit, w_hit, 1.0)
+    mean = np.where(hit, ao[..., 0] / wh, 0.0) / np.pi
+    var = np.where(hit, np.maximum(0.0, ao[..., 1] / wh / (np.pi * np.pi) - mean * mean), 0.0)
+    out = dict(ao=np.clip(mean, 0.0, 1.0), ao_var=var, coverage=np.where(live, w_hit / np.where(live, w_live, 1.0), 0.0))
+    if "bent" in planes:
+        b = np.asarray(planes["bent"], np.float64)[..., :3]
+        length = np.linalg.norm(b, axis=-1)
+        out["bent"] = np.where((length > 0)[..., None], b / np.where(length > 0, length, 1.0)[..., None], 0.0)
+    return out
+
+
+def write_ao_png(path, planes):
+    """The resolved occlusion as grey - what rrt_render writes under RRT_AO=<path.png>."""
+    grey = resolve_ao(planes)["ao"]
+    rgba = np.empty(grey.shape + (4,), np.uint8)
+    rgba[..., :3] = np.clip(np.nan_to_num(grey) * 255.0 + 0.5, 0.0, 255.0).astype(np.uint8)[..., None]
+    rgba[..., 3] = 255
+    write_png(path, rgba)
+
+
 def resolve_moments(m):
     """The sums of Renderer.render_moments -> dict(mean (H, W) = S1 / S0: the pixel's mean sample luminance, variance_of_mean (H, W) =
     (S2 / S0 - mean^2) / (n_eff - 1) (0 where n_eff < 2), n_eff (H, W) = S0^2 / S3: Kish's effective sample count)."""
@@ -778,6 +821,9 @@ def deploy_render(filepath, save_to, device=0, precision=A.RRT_F32, flags=0, ove
     write_png(save_to, rgba)
     if os.environ.get("RRT_AOV"):   # as rrt_render: three PNGs after the frame
         write_aov_pngs(os.environ["RRT_AOV"], r.render_aov(follow=follow))
+    if os.environ.get("RRT_AO"):   # as rrt_render: the resolved occlusion as grey after the frame
+        write_ao_png(os.environ["RRT_AO"], r.render_ao(max_samples=int(os.environ.get("RRT_AO_SPP") or 0),
+                                                       n_samples=int(os.environ["RRT_AO_SAMPLES"]) if os.environ.get("RRT_AO_SAMPLES") else None, planes=("ao",)))
     if os.environ.get("RRT_PASSES"):   # as rrt_render: direct, indirect and one PNG per light (the first 14) after the frame
         write_pass_pngs(os.environ["RRT_PASSES"], r, scene.desc.n_lights, scene.desc.film.scale)
     if os.environ.get("RRT_MATTES"):   # as rrt_render: one preview image of the ID mattes after the frame

@@ -17,6 +17,8 @@
 // its first 32 samples come from one call, rrt_render_frame_aov: the same bits as rrt_render_moments followed by rrt_render_aov, one camera pass less.
 // RRT_AOV_FOLLOW = <n> (1..16) makes RRT_AOV and RRT_DENOISE take their planes from rrt_render_aov_follow(max_follow = n): the feature buffers of the
 // first non-specular surface behind mirrors and smooth glass. With RRT_DENOISE_MOMENTS that is rrt_render_moments followed by that call.
+// RRT_AO = <path.png> writes the resolved ambient occlusion as grey after the frame (rrt_render_ao, on device 0 alone): the mean of a / pi over the
+// hit samples; RRT_AO_SAMPLES sets n_samples (default: rrt_ao_defaults), RRT_AO_SPP max_samples (default 0: every sample of the frame).
 // RRT_PASSES = <prefix> writes light-group and bounce passes after the frame (rrt_render_passes, on device 0 alone): <prefix>_direct.png (path vertex 0),
 // <prefix>_indirect.png (vertices >= 1) and <prefix>_light<i>.png for the first 14 lights, each light its own group; Path integrator only.
 // RRT_MATTES = <path.png> writes one preview image of the ID mattes after the frame (rrt_render_mattes, on device 0 alone): per pixel the ids' hash
@@ -68,6 +70,27 @@ int write_aov(rrt_handle* h, int precision, int W, int H, uint32_t follow, const
   const char* names[3] = {"_albedo.png", "_normal.png", "_depth.png"};
   for (int k = 0; k < 3 && rc == RRT_OK; k++) rc = rrt_write_png((prefix + names[k]).c_str(), img[k].data(), W, H);
   return rc;
+}
+
+// the occlusion sums of rrt_render_ao (rrt_ao in rrt.h) -> one grey 8-bit image: the mean of a / pi over the hit samples, clipped to [0, 1]
+template <typename R>
+int write_ao(rrt_handle* h, int precision, int W, int H, uint64_t max_samples, int n_samples, const std::string& path) {
+  const size_t npx = (size_t)W * (size_t)H;
+  std::vector<R> ao(4 * npx, R(0));
+  rrt_ao out{RRT_MEM_HOST, precision, ao.data(), nullptr};
+  rrt_ao_params prm;
+  rrt_ao_defaults(h, &prm);
+  if (n_samples > 0) prm.n_samples = n_samples;
+  const int32_t rect[4] = {0, 0, W, H};
+  const int rc = rrt_render_ao(h, rect, 0, 1, max_samples, &prm, &out);
+  if (rc != RRT_OK) return rc;
+  std::vector<uint8_t> img(4 * npx, 255);
+  for (size_t i = 0; i < npx; i++) {
+    const double w_hit = (double)ao[4 * i + 2];
+    const double v = w_hit != 0.0 ? std::min(1.0, std::max(0.0, (double)ao[4 * i] / w_hit / 3.14159265358979323846)) : 0.0;
+    for (int c = 0; c < 3; c++) img[4 * i + c] = (uint8_t)std::min(255.0, std::max(0.0, (v == v ? v : 0.0) * 255.0 + 0.5));
+  }
+  return rrt_write_png(path.c_str(), img.data(), W, H);
 }
 
 // the pass films of rrt_render_passes -> 8-bit images: direct, indirect, and one per light for the first 14 lights (RRT_MAX_PASSES - 2)
@@ -321,6 +344,20 @@ int main(int argc, char** argv) {
     if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_AOV runs on one GPU: the feature buffers are rendered on device 0 alone\n");
     rc = precision == RRT_F32 ? write_aov<float>(handles[0], precision, W, H, follow, env_aov) : write_aov<double>(handles[0], precision, W, H, follow, env_aov);
     if (rc != RRT_OK) { const int e = fail("rrt_render_aov", rc); cleanup(); return e; }
+  }
+  if (const char* env_ao = std::getenv("RRT_AO"); env_ao && *env_ao) {
+    if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_AO runs on one GPU: the occlusion plane is rendered on device 0 alone\n");
+    const char* env_n = std::getenv("RRT_AO_SAMPLES");
+    const char* env_spp = std::getenv("RRT_AO_SPP");
+    char *end_n = nullptr, *end_spp = nullptr;
+    const long n = (env_n && *env_n) ? std::strtol(env_n, &end_n, 10) : 0, spp = (env_spp && *env_spp) ? std::strtol(env_spp, &end_spp, 10) : 0;
+    if ((end_n && *end_n != '\0') || (end_spp && *end_spp != '\0') || n < 0 || n > 256 || spp < 0) {
+      std::fprintf(stderr, "rrt_render: RRT_AO_SAMPLES must be a number (n_samples, 1..256), RRT_AO_SPP a number (max_samples)\n");
+      cleanup();
+      return 2;
+    }
+    rc = precision == RRT_F32 ? write_ao<float>(handles[0], precision, W, H, (uint64_t)spp, (int)n, env_ao) : write_ao<double>(handles[0], precision, W, H, (uint64_t)spp, (int)n, env_ao);
+    if (rc != RRT_OK) { const int e = fail("rrt_render_ao", rc); cleanup(); return e; }
   }
   if (const char* env_ps = std::getenv("RRT_PASSES"); env_ps && *env_ps) {
     if (n_gpus > 1) std::fprintf(stderr, "rrt_render: RRT_PASSES runs on one GPU: the passes are rendered on device 0 alone\n");

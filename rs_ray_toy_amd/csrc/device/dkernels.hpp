@@ -446,23 +446,35 @@ template <typename R, bool PASSES = false> RRT_DEV void add_pending(const Pools<
   }
 }
 
+// rrt_render_ao: an unoccluded hemisphere ray adds its record {a_i * d_i, slot} to the slot's accumulator {b.xyz, a} (Pools::L points at the
+// call's accumulators, not at radiance): d_i is unit and a_i >= 0, so |a_i * d_i| is a_i. A slot owns one ray per launch: no atomic.
+template <typename R> RRT_DEV void ao_pending(const Pools<R>& p, uint32_t i) {
+  const typename Vec4T<R>::type ld = p.sld[i];
+  const uint32_t slot = real_to_bits(ld.w);
+  typename Vec4T<R>::type b = p.L[slot];
+  b.x += ld.x; b.y += ld.y; b.z += ld.z;
+  b.w += sqrt(ld.x * ld.x + ld.y * ld.y + ld.z * ld.z);
+  p.L[slot] = b;
+}
+
 // Any-hit kernel over the shadow queue: VisibilityTester::unoccluded (lights/mod.rs:60-66); unoccluded paths
 // add their pending contribution to L (estimate_direct integrator/mod.rs:459-481).
-template <typename R, bool DEEP, bool COUNT, bool PASSES = false>
+// AO: the queue holds rrt_render_ao's hemisphere rays (t_max = inf, ao_pending): a template flag, as PASSES is.
+template <typename R, bool DEEP, bool COUNT, bool PASSES = false, bool AO = false>
 __global__ void __launch_bounds__(kBlock) k_shadow(SceneDev<R> s, Pools<R> p, const uint32_t* queue, const uint32_t* count,
                                                     uint32_t* deep_stack, uint32_t deep_stride, unsigned long long* totals) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= *count) return;
   const typename Vec4T<R>::type ro = p.sray_o[i], rd = p.sray_d[i];
   R r_tmax; V3<R> r_lo;
-  ray_tail(ro, R(1) - R(0.0001), &r_tmax, &r_lo);
+  ray_tail(ro, AO ? Const<R>::inf : R(1) - R(0.0001), &r_tmax, &r_lo);
   RayCtx<R> r = make_ctx(V3<R>(ro.x, ro.y, ro.z), V3<R>(rd.x, rd.y, rd.z), r_tmax, r_lo);
   uint32_t nn = 0, np = 0;
   bool occ;
   const int skip = (int)real_to_bits(rd.w);
   if (DEEP) { GlobStack st{deep_stack + i, deep_stride}; occ = traverse_any(s, r, st, skip, &nn, &np); }
   else { PrivStack st; occ = traverse_any(s, r, st, skip, &nn, &np); }
-  if (!occ) add_pending<R, PASSES>(p, i);
+  if (!occ) { if (AO) ao_pending<R>(p, i); else add_pending<R, PASSES>(p, i); }
   if (COUNT && totals) { atomicAdd(&totals[0], (unsigned long long)nn); atomicAdd(&totals[1], (unsigned long long)np); }
 }
 
@@ -1919,6 +1931,158 @@ template <typename R>
 __global__ void k_aov_merge(const R* src, R* dst, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] += src[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Ambient occlusion and bent normals (rrt_render_ao, include/rrt.h): AOIntegrator::li (ao.rs:65-96) over the first hits of the camera queue.
+// ------------------------------------------------------------------------------------------------------------
+// uniform_sample_hemisphere sampling.rs:245-256
+template <typename R> RRT_DEV V3<R> uniform_sample_hemisphere(R u0, R u1) {
+  const R z = u0;
+  const R r = sqrt(rmax(R(0), R(1) - z * z));
+  const R phi = R(2) * R(RRT_PI) * u1;
+  return {r * R(cos(phi)), r * R(sin(phi)), z};
+}
+
+// The interaction's GEOMETRIC dpdu after the instance transform. Surf::sdpdu is that vector on spheres and on triangles without vertex normals;
+// a triangle with them carries the shading frame's there (triangle.rs:330-349), so its dpdu is formed again, by build_surface's own expressions.
+// (Not an output of build_surface: a SurfExt asked for here lives in scratch, and one more optional argument moved the register allocation of
+// an existing kernel.)
+template <typename R>
+RRT_DEV V3<R> ao_dpdu(const SceneDev<R>& s, int prim, const Surf<R>& si) {
+  const Tri<R> tr = s.tris[prim];
+  if (tr.plane == kSphereMark || tr.shade == 0xffffffffu) return si.sdpdu;
+  const TriShade<R>& sh = s.shades[tr.shade];
+  if (sh.has_n != 1) return si.sdpdu;
+  const V3<R> p0(tr.p0), p1(tr.p1), p2(tr.p2);
+  R uv[3][2] = {{R(0), R(0)}, {R(1), R(0)}, {R(1), R(1)}};  // get_uvs :113-128
+  if (sh.has_uv) for (int k = 0; k < 3; k++) { uv[k][0] = sh.uv[k][0]; uv[k][1] = sh.uv[k][1]; }
+  const R duv02[2] = {uv[0][0] - uv[2][0], uv[0][1] - uv[2][1]}, duv12[2] = {uv[1][0] - uv[2][0], uv[1][1] - uv[2][1]};
+  const V3<R> dp02 = p0 - p2, dp12 = p1 - p2;
+  const R determinant = duv02[0] * duv12[1] - duv02[1] * duv12[0];
+  const bool degenerate_uv = rabs(determinant) < R(1e-8);
+  V3<R> dpdu, dpdv;
+  if (!degenerate_uv) {
+    const R i_det = R(1) / determinant;
+    dpdu = (dp02 * duv12[1] - dp12 * duv02[1]) * i_det;
+    dpdv = (dp02 * -duv12[0] + dp12 * duv02[0]) * i_det;
+  }
+  if (degenerate_uv || len2(cross(dpdu, dpdv)) == R(0)) coordinate_system(vnormalize(cross(p2 - p0, p1 - p0)), &dpdu, &dpdv);
+  if (is_inst_tri(tr)) {
+    const InstDev<R>& I = s.insts[inst_of(tr)];
+    if (!I.identity) dpdu = aff_vec(I.m, dpdu);
+  }
+  return dpdu;
+}
+
+// Draw `draw` of every hit of the camera queue: one thread per queue entry, in queue order (slot word, ray and hit record: 128-bit loads), the
+// surface rebuilt as k_aov_shade rebuilds it, the frame of ao.rs:74-76 on the GEOMETRIC dpdu, one hemisphere direction from the sample's own
+// stream (the draw's 2D value: Halton dimensions 5 + 2 draw, 6 + 2 draw), and the ray pushed into the pool's shadow queue with its record
+// {a_i * d_i, slot} - one atomic per block. Misses push nothing; a draw with pdf == 0 (cosine mode, z = 0: ao.rs forms 0 / 0 there) is dropped.
+// p.L points at the call's per-slot accumulators {b.xyz, a}: the first draw starts them (hit: 0, miss: a = -1, the gather kernels' flag).
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_ao_gen(SceneDev<R> s, Pools<R> p, uint32_t draw, uint32_t n_draws, int cos_sample) {
+  __shared__ uint32_t push_lds[kBlock / 64 + 1];
+  using V4 = typename Vec4T<R>::type;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t n = p.counters[C_ACTIVE];
+  if (blockIdx.x * blockDim.x >= n) return;   // whole block past the queue end (the grid is sized for the worst case)
+  bool want = false;
+  uint32_t slot = 0;
+  int prim = -1;
+  V3<R> sh_o, sh_d, o_lo, rec;
+  if (i < n) {
+    const QEnt qe = p.q_active[i];
+    slot = qe.slot;
+    const V4 h = p.hit[i];
+    prim = (int)real_to_bits(h.y);
+    if (draw == 0u) p.L[slot] = mk4<R>(R(0), R(0), R(0), prim >= 0 ? R(0) : R(-1));
+    if (prim >= 0) {
+      const V4 ro = p.ray_o[i], rd = p.ray_d[i];
+      const V3<R> d(rd.x, rd.y, rd.z);
+      const Surf<R> si = build_surface(s, prim, V3<R>(ro.x, ro.y, ro.z), d, h.x, h.z, h.w);
+      if (!si.ok) atomicOr(&p.counters[C_ERROR], (uint32_t)ERR_SHADING_NORMAL);   // primitives.rs:66, as the frame reports it
+      const V3<R> nf = faceforward(si.n, -d);
+      const V3<R> ss = vnormalize(ao_dpdu(s, prim, si));
+      const V3<R> ts = cross(si.n, ss);   // the un-flipped normal, as ao.rs:76 has it
+      const R u0 = to_real<R>(halton_dim(s, qe.index, 5u + 2u * draw)), u1 = to_real<R>(halton_dim(s, qe.index, 6u + 2u * draw));
+      V3<R> wl;
+      R pdf;
+      if (cos_sample) { wl = cosine_sample_hemisphere(u0, u1); pdf = rabs(wl.z) * R(0.31830988618379067154); }
+      else { wl = uniform_sample_hemisphere(u0, u1); pdf = R(1) / (R(2) * R(RRT_PI)); }
+      const V3<R> wi((ss.x * wl.x + ts.x * wl.y) + nf.x * wl.z, (ss.y * wl.x + ts.y * wl.y) + nf.y * wl.z, (ss.z * wl.x + ts.z * wl.y) + nf.z * wl.z);
+      if (pdf != R(0)) {
+        const R a = dot(wi, nf) / (pdf * (R)n_draws);
+        sh_d = vnormalize(wi);   // spawn_ray -> Ray::new_od (Q8: no origin offset)
+        sh_o = si.p; o_lo = si.p_lo;
+        rec = sh_d * a;
+        want = true;
+      }
+    }
+  }
+  const uint32_t qs = block_push(p.shadow_count, want, push_lds);
+  if (want) {
+    store_ray<R>(p.sray_o, p.sray_d, qs, sh_o, o_lo, sh_d, Const<R>::inf, self_prim<R>(prim));
+    p.sld[qs] = mk4u<R>(rec.x, rec.y, rec.z, slot);
+  }
+}
+
+// One live sample with filter weight fw into the two running sums of a pixel (rrt_ao in rrt.h); acc = the slot's accumulator {b.xyz, a}, a < 0 = miss
+template <typename R>
+struct AoPixel { typename Vec4T<R>::type ao, bent; };
+template <typename R>
+RRT_DEV void ao_add(AoPixel<R>& px, R fw, const typename Vec4T<R>::type& acc) {
+  px.ao.w += fw;
+  if (acc.w < R(0)) return;   // a live sample that misses the scene
+  px.ao.x += fw * acc.w; px.ao.y += (fw * acc.w) * acc.w; px.ao.z += fw;
+  px.bent.x += fw * acc.x; px.bent.y += fw * acc.y; px.bent.z += fw * acc.z; px.bent.w += fw;
+}
+
+// Gather forms, as k_aov_box / k_aov_wide: one thread per film pixel, its samples in sample order, running sums in the handle's two internal
+// W x H x 4 planes (`planes`, one after the other) - so the sums do not depend on how the samples were cut into passes.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_ao_box(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* acc) {
+  using V4 = typename Vec4T<R>::type;
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  const size_t pix = (size_t)py_ * (size_t)s.xres + px_, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
+  AoPixel<R> px{reinterpret_cast<const V4*>(planes)[pix], reinterpret_cast<const V4*>(planes + plane_n)[pix]};
+  for (uint32_t sl = 0; sl < pd.ns; sl++) {
+    const uint32_t slot = sl * pd.npix + pl;
+    if (!(p.weight[slot] > R(0))) continue;   // dead sample
+    ao_add(px, R(1), acc[slot]);   // box filter table weight 1
+  }
+  reinterpret_cast<V4*>(planes)[pix] = px.ao;
+  reinterpret_cast<V4*>(planes + plane_n)[pix] = px.bent;
+}
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_ao_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* acc,
+                                                     int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+  using V4 = typename Vec4T<R>::type;
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint32_t)ew * (uint32_t)eh) return;
+  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
+  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
+  AoPixel<R> px{reinterpret_cast<const V4*>(planes)[pix], reinterpret_cast<const V4*>(planes + plane_n)[pix]};
+  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
+    if (sy < 0 || sy >= ymax) continue;
+    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+      uint32_t pl;
+      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
+      for (uint32_t sl = 0; sl < pd.ns; sl++) {
+        const uint32_t slot = sl * pd.npix + pl;
+        if (!(p.weight[slot] > R(0))) continue;
+        const V4 cs = p.samp[slot];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
+        ao_add(px, fw, acc[slot]);
+      }
+    }
+  }
+  reinterpret_cast<V4*>(planes)[pix] = px.ao;
+  reinterpret_cast<V4*>(planes + plane_n)[pix] = px.bent;
 }
 
 // ------------------------------------------------------------------------------------------------------------

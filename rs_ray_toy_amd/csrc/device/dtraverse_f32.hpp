@@ -196,17 +196,19 @@ RRT_DEV bool is_leaf(uint32_t w) { return (int32_t)w < 0; }
 
 // Ray `idx` of the queue this launch serves (POOL_SHADOW: the pool's shadow rays, t_max = 1 - 1e-4; otherwise the closest-ray arrays
 // with their own t_max) -> lane registers; returns the word the walk starts with (kIdle: the ray misses the root box).
-template <bool POOL_SHADOW>
+// AO: the pool's shadow queue holds the hemisphere rays of rrt_render_ao: t_max = inf with the packed origin kept, and no any_list (its entries
+// speak for rays that reach less than one unit far). A template flag, false in every launch of a frame: those instantiations are the code they were.
+template <bool POOL_SHADOW, bool AO = false>
 RRT_DEV uint32_t lane_ray_begin(const TravScene& ts, const Pools<float>& p, bool pool_shadow, uint32_t idx, LaneRay& r, int* start_tri) {
   const float4 ro = (POOL_SHADOW && pool_shadow) ? p.sray_o[idx] : p.ray_o[idx], rd = (POOL_SHADOW && pool_shadow) ? p.sray_d[idx] : p.ray_d[idx];
   V3<float> lo;
-  ray_tail(ro, (POOL_SHADOW && pool_shadow) ? kShadowTmax : Const<float>::inf, &r.tmax, &lo);
+  ray_tail(ro, (POOL_SHADOW && !AO && pool_shadow) ? kShadowTmax : Const<float>::inf, &r.tmax, &lo);
   const int sk = (int)__float_as_uint(rd.w);
   r.oxy = v2f{ro.x, ro.y}; r.ozz = v2f{ro.z, ro.z}; r.dx = rd.x; r.dy = rd.y; r.dz = rd.z;
   r.lx = lo.x; r.ly = lo.y; r.lz = lo.z;
   r.skip_plane = sk >= 0 ? __float_as_uint(ts.tris[(size_t)sk * 12 + 11]) : 0xffffffffu;
   lane_ray_set_inv(r);
-  *start_tri = (POOL_SHADOW && pool_shadow && ts.any_list) ? sk : -1;   // >= 0: the walk starts from any_list[start_tri] (the caller owns the stack)
+  *start_tri = (POOL_SHADOW && !AO && pool_shadow && ts.any_list) ? sk : -1;   // >= 0: the walk starts from any_list[start_tri] (the caller owns the stack)
   if (*start_tri >= 0) return kIdle;
   float tmin;
   if (ts.n_nodes != 0 && box_slabs_f32(ts.root_box[0], ts.root_box[1], ts.root_box[2], ts.root_box[3], ts.root_box[4], ts.root_box[5], r, &tmin) && tmin < r.tmax)
@@ -304,7 +306,7 @@ RRT_DEV bool leaf_step_f32(const TravScene& ts, uint32_t word, LaneRay& r, int* 
 //              are the pool's closest-ray arrays and the verdict is written to occluded[i] (public rrt_trace_any).
 // Grid-stride form for small queues: the wave alternates between "every lane walks interior nodes until it holds a leaf" and "every lane
 // tests its leaf" (while-while); the BFS top of the tree is read from LDS.
-template <bool ANY, bool MIXED = false, bool PASSES = false>
+template <bool ANY, bool MIXED = false, bool PASSES = false, bool AO = false>
 __global__ void __launch_bounds__(kTravBlock) k_trace_pairs_f32(TravScene ts, Pools<float> p, const uint32_t* queue, const uint32_t* count,
                                                                  uint32_t n_fixed, uint8_t* occluded, uint32_t n_lo, uint32_t n_hi) {
   {  // queue-size regime of this kernel (the other traversal kernel is launched next to it for the other regime)
@@ -322,7 +324,7 @@ __global__ void __launch_bounds__(kTravBlock) k_trace_pairs_f32(TravScene ts, Po
   for (uint32_t gid = col; gid < n; gid += gridDim.x * kTravBlock) {
     LaneRay r;
     int start_tri;
-    uint32_t cur = lane_ray_begin<ANY>(ts, p, !occluded, gid, r, &start_tri);
+    uint32_t cur = lane_ray_begin<ANY, AO>(ts, p, !occluded, gid, r, &start_tri);
     int hit = -1;
     float hu = 0.0f, hv = 0.0f;
     bool found = false;
@@ -374,7 +376,7 @@ __global__ void __launch_bounds__(kTravBlock) k_trace_pairs_f32(TravScene ts, Po
     }
     if (ANY) {
       if (occluded) occluded[gid] = found ? 1 : 0;
-      else if (!found) add_pending<float, PASSES>(p, gid);
+      else if (!found) { if (AO) ao_pending<float>(p, gid); else add_pending<float, PASSES>(p, gid); }
     } else {
       p.hit[gid] = make_float4(r.tmax, __uint_as_float((uint32_t)hit), hu, hv);
     }
@@ -478,10 +480,11 @@ __device__ unsigned long long g_pt_stats[2][16];
 #else
 #define RRT_PT_ATTR
 #endif
-template <bool ANY, bool MIXED = false, bool QUAD = false, bool PASSES = false>
+template <bool ANY, bool MIXED = false, bool QUAD = false, bool PASSES = false, bool AO = false>
 __global__ void __launch_bounds__(kPtBlock) RRT_PT_ATTR k_trace_pt_f32(TravScene ts, Pools<float> p, const uint32_t* queue, const uint32_t* count,
                                                             uint32_t n_fixed, uint32_t* work, uint8_t* occluded, uint32_t n_lo, uint32_t n_hi) {
   static_assert(!QUAD || (!ANY && !MIXED), "quad nodes: closest-hit rays of plain triangle scenes only");
+  static_assert(!AO || (ANY && !PASSES), "rrt_render_ao: any-hit launches outside a passes frame");
   {
     const uint32_t nn = count ? *count : n_fixed;
     if (nn < n_lo || nn >= n_hi) return;
@@ -528,7 +531,7 @@ __global__ void __launch_bounds__(kPtBlock) RRT_PT_ATTR k_trace_pt_f32(TravScene
   auto finish = [&](bool found) {
     if (ANY) {
       if (occluded) occluded[qidx] = found ? 1 : 0;
-      else if (!found) add_pending<float, PASSES>(p, qidx);
+      else if (!found) { if (AO) ao_pending<float>(p, qidx); else add_pending<float, PASSES>(p, qidx); }
     } else {
       p.hit[qidx] = make_float4(r.tmax, __uint_as_float((uint32_t)hit), hu, hv);
     }
@@ -581,7 +584,7 @@ __global__ void __launch_bounds__(kPtBlock) RRT_PT_ATTR k_trace_pt_f32(TravScene
           qidx = lo + rank;
           sp = 0; hit = -1; hu = 0.0f; hv = 0.0f;
           int start_tri;
-          cur = lane_ray_begin<ANY>(ts, p, !occluded, qidx, r, &start_tri);
+          cur = lane_ray_begin<ANY, AO>(ts, p, !occluded, qidx, r, &start_tri);
           if (ANY && start_tri >= 0) {   // TravScene::any_list
             const uint4 la = ts.any_list[2 * (size_t)start_tri], lb = ts.any_list[2 * (size_t)start_tri + 1];
             cur = la.x; sp = lb.w;

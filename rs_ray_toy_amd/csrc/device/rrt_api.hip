@@ -151,6 +151,23 @@ int rrt_render_aov(rrt_handle* h, const int32_t rect[4], int rank, int world, ui
   return guarded([&]() { h->impl->render_aov(rect, rank, world, max_samples, out); });
 }
 
+void rrt_ao_defaults(const rrt_handle* h, rrt_ao_params* p) {
+  if (!p) return;
+  p->n_samples = 64; p->cos_sample = 1;
+  if (h) h->impl->ao_defaults(p);
+}
+
+int rrt_render_ao(rrt_handle* h, const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_ao_params* params, rrt_ao* out) {
+  // everything the host can see, before any device work
+  if (!out) { rrt::set_last_error("rrt_render_ao: null output description (rrt_ao)"); return RRT_EINVAL; }
+  if (!out->ao && !out->bent) { rrt::set_last_error("rrt_render_ao: no plane requested (ao and bent are both NULL)"); return RRT_EINVAL; }
+  if (out->mem != RRT_MEM_HOST && out->mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_ao: bad mem"); return RRT_EINVAL; }
+  if (params && params->n_samples < 1) { rrt::set_last_error("rrt_render_ao: n_samples must be at least 1"); return RRT_EINVAL; }
+  if (params && params->n_samples > 256) { rrt::set_last_error("rrt_render_ao: n_samples must be at most 256 (draw i reads sampler dimensions 5 + 2i and 6 + 2i)"); return RRT_EINVAL; }
+  if (!h || !rect) { rrt::set_last_error("rrt_render_ao: null handle or rect"); return RRT_EINVAL; }
+  return guarded([&]() { h->impl->render_ao(rect, rank, world, max_samples, params, out); });
+}
+
 int rrt_render_aov_follow(rrt_handle* h, const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, rrt_aov* out) {
   // rrt_render_aov's checks in its order, then the chain's own bound: all before any device work
   if (!out) { rrt::set_last_error("rrt_render_aov_follow: null output description (rrt_aov)"); return RRT_EINVAL; }

@@ -50,6 +50,8 @@ struct HandleBase {
   virtual void render_end(rrt_render_stats* stats) = 0;
   virtual void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) = 0;
   virtual void render_aov_follow(const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) = 0;
+  virtual void ao_defaults(rrt_ao_params* p) const = 0;
+  virtual void render_ao(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_ao_params* params, const rrt_ao* out) = 0;   // params may be NULL
   virtual void render_moments(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, rrt_render_stats* stats) = 0;
   virtual void render_frame_aov(const int32_t rect[4], int rank, int world, void* film, void* moments, int mem, uint64_t aov_max_samples, const rrt_aov* aov, rrt_render_stats* stats) = 0;   // moments may be NULL
   virtual void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film, void* moments, uint32_t* tile_samples, int mem, rrt_render_stats* stats) = 0;
@@ -1175,6 +1177,90 @@ class Handle : public HandleBase {
     aov_merge_out(out);   // into the caller's planes (+=)
     check_device_errors();
   }
+  // ---- ambient occlusion and bent normals (rrt_render_ao): first_hit_passes with shade = the draw rounds, gather = k_ao_box / k_ao_wide -----------------
+  // Round i of a pass handles draw i of every hit of the pass: k_ao_gen pushes one hemisphere ray per hit into the pool's shadow queue (never more
+  // entries than the camera queue, so no queue exceeds the pool), the any-hit launch over that queue adds the free rays' records into the per-slot
+  // accumulators (Pools::L points at them for the call). A slot occurs once per round and the rounds follow each other on the stream: the sums need
+  // no atomics and their order is the draw order, whatever the pool size. The rays' t_max is inf: the AO instantiations of the any-hit kernels
+  // (persistent, plain and deep), which also leave the per-triangle any-hit lists alone; shadow candidate lists are per light and are not taken.
+  void ao_defaults(rrt_ao_params* p) const override {
+    const bool ao = desc_.integrator.type == RRT_INT_AO;
+    p->n_samples = ao ? desc_.integrator.n_samples : 64;
+    p->cos_sample = ao ? (desc_.integrator.cos_sample ? 1 : 0) : 1;
+  }
+  void launch_ao_any(uint32_t grid) {
+    if (use_persistent()) { launch_persistent(true, nullptr, pool_.shadow_count, 0, grid, nullptr, st_, false, /*ao=*/true); return; }
+    uint32_t* ds = deep_ ? deep_stack_.p : nullptr;
+    const uint32_t stride = deep_ ? (uint32_t)cap_ : 0u;
+    if (deep_) hipLaunchKernelGGL((k_shadow<R, true, false, false, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, (unsigned long long*)nullptr);
+    else hipLaunchKernelGGL((k_shadow<R, false, false, false, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, (unsigned long long*)nullptr);
+    HIP_CHECK(hipGetLastError());
+  }
+  void render_ao(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_ao_params* params, const rrt_ao* out) override {
+    using V4 = typename Vec4T<R>::type;
+    rrt_ao_params prm;
+    if (params) prm = *params; else ao_defaults(&prm);
+    if (prm.n_samples < 1 || prm.n_samples > 256) throw std::invalid_argument("render_ao: n_samples must be 1..256 (draw i reads sampler dimensions 5 + 2i and 6 + 2i, and the permutation tables end at 1000)");
+    if (pending_) throw std::invalid_argument("render_ao: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (out->precision != precision()) throw std::invalid_argument("render_ao: plane precision must match the handle");
+    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_ao: bad rank/world");
+    check_rect("render_ao: rect outside the film", rect);
+    // the StratifiedSampler's draws past `dimension` are the [-1, 1) generator (Q25): no scene means a hemisphere sample drawn from those
+    if (desc_.sampler.type == RRT_SAMPLER_STRATIFIED) throw UnsupportedError("render_ao under the StratifiedSampler (its 2D draws past `dimension` are not in [0, 1))");
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    check_no_crop();
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
+    const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank), rpix = rw * rh;
+    const uint64_t s_total = frame_samples(max_samples);
+    if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
+    RaygenStateGuard guard(this);
+    // what the rounds borrow of the pool: L (the accumulators' place) and the first shadow queue, put back on every way out
+    struct PoolGuard {
+      Pools<R>& p; V4 *L, *so, *sd, *sld; uint32_t* sc;
+      explicit PoolGuard(Pools<R>& pp) : p(pp), L(pp.L), so(pp.sray_o), sd(pp.sray_d), sld(pp.sld), sc(pp.shadow_count) {}
+      ~PoolGuard() { p.L = L; p.sray_o = so; p.sray_d = sd; p.sld = sld; p.shadow_count = sc; }
+    };
+
+    if (ao_planes_.n != 2 * plane_n) ao_planes_.alloc(2 * plane_n);
+    HIP_CHECK(hipMemsetAsync(ao_planes_.p, 0, 2 * plane_n * sizeof(R), st_));
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
+    ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+    if (ao_acc_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); ao_acc_.alloc(cap_); }
+    PoolGuard pool_guard(pool_);
+    pool_.L = ao_acc_.p;
+    pool_.sray_o = shadow_buf_[0][0]; pool_.sray_d = shadow_buf_[0][1]; pool_.sld = shadow_buf_[0][2];
+    pool_.shadow_count = counters_.p + C_SHADOW;
+    const FilmWindow win = film_window(rect);
+    const uint32_t n_draws = (uint32_t)prm.n_samples;
+    const int cos_sample = prm.cos_sample ? 1 : 0;
+    first_hit_passes(rect, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, s_total,
+      [&](const PassDesc&, uint32_t grid) {
+        for (uint32_t i = 0; i < n_draws; i++) {
+          hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);   // the shadow queue and the work cursors start at 0
+          hipLaunchKernelGGL((k_ao_gen<R>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, i, n_draws, cos_sample);
+          launch_ao_any(grid);
+        }
+      },
+      [&](const PassDesc& pd) {
+        if (!wide_filter()) hipLaunchKernelGGL((k_ao_box<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, ao_planes_.p, (const V4*)ao_acc_.p);
+        else hipLaunchKernelGGL((k_ao_wide<R>), dim3((uint32_t)((win.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, ao_planes_.p, (const V4*)ao_acc_.p,
+                                win.ex0, win.ey0, win.ew, win.eh, win.reach_x, win.reach_y, desc_.film.yres);
+      });
+    // into the caller's planes (+=)
+    void* user[2] = {out->ao, out->bent};
+    if (out->mem == RRT_MEM_DEVICE) {
+      for (int k = 0; k < 2; k++)
+        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)(ao_planes_.p + k * plane_n), (R*)user[k], plane_n);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(st_));
+    } else {
+      for (int k = 0; k < 2; k++)
+        if (user[k]) add_to_host(ao_planes_.p + k * plane_n, (R*)user[k], plane_n);
+    }
+    check_device_errors();
+  }
   // ---- ID mattes (rrt_render_mattes): first_hit_passes with shade = k_matte_ids and gather = k_matte_box / k_matte_wide into a (id, coverage) table -----
   // Per call: the ids of the entries of prim_order are built on the host and uploaded (they are the caller's, not the scene's: nothing of the scene
   // preparation knows them), the caller's table is copied into the internal slot-major one (k_matte_load; a host table is staged), the passes insert
@@ -1496,6 +1582,8 @@ class Handle : public HandleBase {
   DevBuf<typename Vec4T<R>::type> dn_c_[2], dn_g_, dn_p_, dn_stage_;   // denoise: the record planes C (ping-pong), G, P of dfilter.hpp, and the staging of host-memory calls (allocated by the first call)
   DevBuf<typename Vec4T<R>::type> dn_stage_m_;   // denoise with a moments plane in host memory: its staging
   bool dn_lds_ = true;       // option "dn_lds"
+  DevBuf<R> ao_planes_;    // render_ao: running sums of the occlusion and bent-normal planes, W x H x 4 each (allocated by the first call)
+  DevBuf<typename Vec4T<R>::type> ao_acc_;   // render_ao: per-slot accumulators {b.xyz, a} of a pass's draws, sized like pool.L (allocated by the first call)
   DevBuf<typename Vec4T<R>::type> aov_rec_a_, aov_rec_b_;   // k_aov_shade's per-slot records {rho.rgb, hit flag}, {n.xyz, t}: sized like pool.L
   // render_passes (all allocated by the first call): the passes' internal films, the folded pass table (Pools::pass_tab) and its host copy, the radiance
   // planes, the mask arrays of the two shadow queues; passes_n_ = the passes of the frame being rendered, 0 outside such a frame
@@ -1853,7 +1941,7 @@ class Handle : public HandleBase {
   }
   // fp32 production traversal (dtraverse_f32.hpp): 64 B pair nodes, LDS stack with global overflow
   bool use_persistent() const { return std::is_same<R, float>::value && persistent_ && pairs_ok_; }
-  void launch_persistent(bool any, const uint32_t* queue, const uint32_t* count, uint32_t n_fixed, uint32_t grid, uint8_t* occluded, hipStream_t stream = nullptr, bool tiles = false) {
+  void launch_persistent(bool any, const uint32_t* queue, const uint32_t* count, uint32_t n_fixed, uint32_t grid, uint8_t* occluded, hipStream_t stream = nullptr, bool tiles = false, bool ao = false) {
     if constexpr (std::is_same<R, float>::value) {
       if (!stream) stream = st_;
       const uint32_t grid_in = grid;
@@ -1889,11 +1977,13 @@ class Handle : public HandleBase {
       if (trav_mode_ != 2) {
         if (trav_mode_ == 3) grid = std::max(1u, std::min(grid, (split + kTravBlock - 1) / kTravBlock));
         if (mixed_) {
-          if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          if (any && ao) hipLaunchKernelGGL((k_trace_pairs_f32<true, true, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          else if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
           else if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
           else hipLaunchKernelGGL((k_trace_pairs_f32<false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
         } else {
-          if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          if (any && ao) hipLaunchKernelGGL((k_trace_pairs_f32<true, false, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
+          else if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
           else if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
           else hipLaunchKernelGGL((k_trace_pairs_f32<false, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
         }
@@ -1940,11 +2030,13 @@ class Handle : public HandleBase {
           const uint32_t gq = std::max(1u, std::min(grid_in, pt_grid_quad_));
           hipLaunchKernelGGL((k_trace_pt_f32<false, false, true>), dim3(gq), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
         } else if (mixed_) {
-          if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, true, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          if (any && ao) hipLaunchKernelGGL((k_trace_pt_f32<true, true, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          else if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, true, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
           else if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
           else hipLaunchKernelGGL((k_trace_pt_f32<false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
         } else {
-          if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          if (any && ao) hipLaunchKernelGGL((k_trace_pt_f32<true, false, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
+          else if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
           else if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
           else hipLaunchKernelGGL((k_trace_pt_f32<false, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
         }
