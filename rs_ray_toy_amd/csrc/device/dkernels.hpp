@@ -534,6 +534,12 @@ struct PassDesc {
   // rows 36.8 ms; 32 x 16 tiles, one sample per workgroup 35.7; 8 x 8 tiles x 8 samples 35.0 (16 x 8 x 4, 16 x 16 x 2: in between).
   uint32_t tiled;
 };
+// The film pixels the samples of a rect can touch under a wide filter (Handle::film_window): the rect grown by the filter's reach
+// ceil(r + 0.5) and clipped to the film, ew x eh pixels from (ex0, ey0); ymax = the film's height. One kernel argument of every wide kernel.
+struct FilmWindow {
+  int ex0, ey0, ew, eh, reach_x, reach_y, ymax;
+  size_t n() const { return (size_t)ew * (size_t)eh; }   // host only: the launch's thread count
+};
 #ifndef RRT_TILE_W
 #define RRT_TILE_W 8u
 #define RRT_TILE_H 8u
@@ -1693,7 +1699,7 @@ RRT_DEV bool pass_pixel_inverse(const PassDesc& pd, int x, int y, uint32_t* pl) 
   return true;
 }
 // One sample of a wide filter at film pixel (x, y): FilmTile::add_sample's footprint test and table look-up (film.rs:77-130). False = the pixel is
-// outside the sample's footprint. k_film_wide and k_aov_wide both weigh through this function, so their weights are the same expressions.
+// outside the sample's footprint. k_film_wide and k_gather_wide both weigh through this function, so their weights are the same expressions.
 template <typename R>
 RRT_DEV bool film_wide_weight(const SceneDev<R>& s, R pfx, R pfy, int x, int y, R* fw) {
   const R dx = pfx - R(0.5), dy = pfy - R(0.5);
@@ -1707,15 +1713,15 @@ RRT_DEV bool film_wide_weight(const SceneDev<R>& s, R pfx, R pfy, int x, int y, 
   return true;
 }
 template <typename R>
-__global__ void __launch_bounds__(kBlock) k_film_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+__global__ void __launch_bounds__(kBlock) k_film_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, FilmWindow win) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint32_t)ew * (uint32_t)eh) return;
-  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
+  if (t >= (uint32_t)win.ew * (uint32_t)win.eh) return;
+  const int x = win.ex0 + (int)(t % (uint32_t)win.ew), y = win.ey0 + (int)(t / (uint32_t)win.ew);
   R* px = film + 4 * ((size_t)y * (size_t)s.xres + (size_t)x);
   R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];   // running RGB + weight sums (see k_film_box)
-  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
-    if (sy < 0 || sy >= ymax) continue;
-    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+  for (int sy = y - win.reach_y; sy <= y + win.reach_y; sy++) {
+    if (sy < 0 || sy >= win.ymax) continue;
+    for (int sx = x - win.reach_x; sx <= x + win.reach_x; sx++) {
       uint32_t pl;
       if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
       for (uint32_t sl = 0; sl < pd.ns; sl++) {
@@ -1736,6 +1742,60 @@ __global__ void __launch_bounds__(kBlock) k_film_wide(SceneDev<R> s, Pools<R> p,
     }
   }
   px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The gather skeletons of the first-hit planes (feature buffers, their frame form, ambient occlusion, ID mattes): k_film_box's and
+// k_film_wide's loops over the LIVE samples of a pass, around an accumulator that says what a pixel keeps. The contract ("The
+// gather contract"):
+//  * box: one thread per pixel of the pass (pass_pixel), its samples in sample order, filter weight 1. wide: one thread per film pixel of
+//    the window, the pass pixels within reach row by row (pass_pixel_inverse), each one's samples in sample order, weighed by film_wide_weight.
+//    This visiting order is what makes a frame and its parts (rects, bands, pool passes) sum to the same bits;
+//  * weight[slot] > 0 is tested BEFORE samp[slot] or any record of the slot is read: a dead sample has neither;
+//  * Acc is a trivially copyable kernel argument (pointers and small scalars) with a per-thread Pixel: load(s, pix) reads the pixel's running
+//    state, add(px, fw, slot) adds one live sample of weight fw from the slot's records, store(s, pix, px) writes the state back. An
+//    accumulator touches its own pixel and its own records only, never the pools, and decides nothing about which samples are visited.
+// Not under the skeleton, on purpose: k_film_wide_moments counts dead samples into its weight sums and tests the footprint before the
+// weight - another visiting rule - and k_film_box / k_film_wide / k_film_box_runs are what a plain frame launches and stay the code they are.
+// ------------------------------------------------------------------------------------------------------------
+template <typename R, class Acc>
+__global__ void __launch_bounds__(kBlock) k_gather_box(SceneDev<R> s, Pools<R> p, PassDesc pd, Acc acc) {
+  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= pd.npix) return;
+  uint32_t px_, py_;
+  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  const size_t pix = (size_t)py_ * (size_t)s.xres + px_;
+  typename Acc::Pixel px = acc.load(s, pix);
+  for (uint32_t sl = 0; sl < pd.ns; sl++) {
+    const uint32_t slot = sl * pd.npix + pl;
+    if (!(p.weight[slot] > R(0))) continue;   // dead sample
+    acc.add(px, R(1), slot);   // box filter table weight 1
+  }
+  acc.store(s, pix, px);
+}
+template <typename R, class Acc>
+__global__ void __launch_bounds__(kBlock) k_gather_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, Acc acc, FilmWindow win) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint32_t)win.ew * (uint32_t)win.eh) return;
+  const int x = win.ex0 + (int)(t % (uint32_t)win.ew), y = win.ey0 + (int)(t / (uint32_t)win.ew);
+  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x;
+  typename Acc::Pixel px = acc.load(s, pix);
+  for (int sy = y - win.reach_y; sy <= y + win.reach_y; sy++) {
+    if (sy < 0 || sy >= win.ymax) continue;
+    for (int sx = x - win.reach_x; sx <= x + win.reach_x; sx++) {
+      uint32_t pl;
+      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
+      for (uint32_t sl = 0; sl < pd.ns; sl++) {
+        const uint32_t slot = sl * pd.npix + pl;
+        if (!(p.weight[slot] > R(0))) continue;
+        const typename Vec4T<R>::type cs = p.samp[slot];
+        R fw;
+        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
+        acc.add(px, fw, slot);
+      }
+    }
+  }
+  acc.store(s, pix, px);
 }
 
 // Film::merge_film_tile (film.rs:248-263): the pixel's RGB contribution sum -> XYZ (rgb_to_xyz spectrum.rs:2084-2090), added to the
@@ -1798,7 +1858,7 @@ __global__ void __launch_bounds__(kBlock) k_combine_passes(CombineArgs a, R* out
 
 // ------------------------------------------------------------------------------------------------------------
 // First-hit feature buffers (rrt_render_aov, include/rrt.h): albedo, normal and depth of the camera rays' first hits, filtered by the
-// film's pixel filter. A pass of their own - camera kernels, closest-hit launch, k_aov_shade, k_aov_box / k_aov_wide - not a branch of
+// film's pixel filter. A pass of their own - camera kernels, closest-hit launch, k_aov_shade, the gather over AovAcc - not a branch of
 // k_shade_path: the frame's kernels and their register budgets stay what they are.
 // ------------------------------------------------------------------------------------------------------------
 // rho of the table in rrt.h from the material's own parameters; a textured one is evaluated through `c` (zero differentials)
@@ -1850,8 +1910,8 @@ __global__ void __launch_bounds__(kBlock) k_aov_shade(SceneDev<R> s, Pools<R> p,
   }
 }
 
-// One live sample with filter weight fw into the three running sums of a pixel (rrt_aov in rrt.h). k_aov_box and k_aov_wide both add
-// through this function.
+// One live sample with filter weight fw into the three running sums of a pixel (rrt_aov in rrt.h): what AovAcc and AovFrameAcc
+// add through, under both gather skeletons.
 template <typename R>
 struct AovPixel { typename Vec4T<R>::type alb, nrm, dep; };
 template <typename R>
@@ -1880,51 +1940,19 @@ RRT_DEV void aov_store(R* planes, size_t plane_n, size_t pix, const AovPixel<R>&
   reinterpret_cast<V4*>(planes + 2 * plane_n)[pix] = px.dep;
 }
 
-// Gather form of k_film_box: one thread per pixel of the pass, its samples in sample order, running sums in the handle's three internal
-// W x H x 4 planes (`planes`, one after the other) - so the sums do not depend on how the samples were cut into passes.
+// The feature buffers under the gather skeletons (k_gather_box / k_gather_wide): running sums in the handle's three internal W x H x 4 planes
+// (`planes`, one after the other), the records k_aov_shade / k_aov_follow left per slot.
 template <typename R>
-__global__ void __launch_bounds__(kBlock) k_aov_box(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b) {
-  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pl >= pd.npix) return;
-  uint32_t px_, py_;
-  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
-  const size_t pix = (size_t)py_ * (size_t)s.xres + px_, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
-  AovPixel<R> px = aov_load(planes, plane_n, pix);
-  for (uint32_t sl = 0; sl < pd.ns; sl++) {
-    const uint32_t slot = sl * pd.npix + pl;
-    if (!(p.weight[slot] > R(0))) continue;   // dead sample
-    aov_add(px, R(1), rec_a[slot], rec_b, slot);   // box filter table weight 1
-  }
-  aov_store(planes, plane_n, pix, px);
-}
-
-// Gather form of k_film_wide: one thread per film pixel within reach of the pass, the samples of every pass pixel within reach in the
-// same order, the film's own footprint test and table look-up (film_wide_weight).
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_aov_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b,
-                                                      int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint32_t)ew * (uint32_t)eh) return;
-  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
-  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
-  AovPixel<R> px = aov_load(planes, plane_n, pix);
-  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
-    if (sy < 0 || sy >= ymax) continue;
-    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
-      uint32_t pl;
-      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
-      for (uint32_t sl = 0; sl < pd.ns; sl++) {
-        const uint32_t slot = sl * pd.npix + pl;
-        if (!(p.weight[slot] > R(0))) continue;
-        const typename Vec4T<R>::type cs = p.samp[slot];
-        R fw;
-        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
-        aov_add(px, fw, rec_a[slot], rec_b, slot);
-      }
-    }
-  }
-  aov_store(planes, plane_n, pix, px);
-}
+struct AovAcc {
+  using V4 = typename Vec4T<R>::type;
+  using Pixel = AovPixel<R>;
+  R* planes;
+  const V4 *rec_a, *rec_b;
+  RRT_DEV static size_t plane_n(const SceneDev<R>& s) { return 4 * (size_t)s.xres * (size_t)s.yres; }
+  RRT_DEV Pixel load(const SceneDev<R>& s, size_t pix) const { return aov_load(planes, plane_n(s), pix); }
+  RRT_DEV void add(Pixel& px, R fw, uint32_t slot) const { aov_add(px, fw, rec_a[slot], rec_b, slot); }
+  RRT_DEV void store(const SceneDev<R>& s, size_t pix, const Pixel& px) const { aov_store(planes, plane_n(s), pix, px); }
+};
 
 // the caller's plane += the internal one (`n` = W x H x 4 values)
 template <typename R>
@@ -2038,64 +2066,35 @@ RRT_DEV void ao_add(AoPixel<R>& px, R fw, const typename Vec4T<R>::type& acc) {
   px.bent.x += fw * acc.x; px.bent.y += fw * acc.y; px.bent.z += fw * acc.z; px.bent.w += fw;
 }
 
-// Gather forms, as k_aov_box / k_aov_wide: one thread per film pixel, its samples in sample order, running sums in the handle's two internal
-// W x H x 4 planes (`planes`, one after the other) - so the sums do not depend on how the samples were cut into passes.
+// Under the gather skeletons: running sums in the handle's two internal W x H x 4 planes (`planes`, one after the other), `acc` = the slots' accumulators
 template <typename R>
-__global__ void __launch_bounds__(kBlock) k_ao_box(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* acc) {
+struct AoAcc {
   using V4 = typename Vec4T<R>::type;
-  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pl >= pd.npix) return;
-  uint32_t px_, py_;
-  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
-  const size_t pix = (size_t)py_ * (size_t)s.xres + px_, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
-  AoPixel<R> px{reinterpret_cast<const V4*>(planes)[pix], reinterpret_cast<const V4*>(planes + plane_n)[pix]};
-  for (uint32_t sl = 0; sl < pd.ns; sl++) {
-    const uint32_t slot = sl * pd.npix + pl;
-    if (!(p.weight[slot] > R(0))) continue;   // dead sample
-    ao_add(px, R(1), acc[slot]);   // box filter table weight 1
+  using Pixel = AoPixel<R>;
+  R* planes;
+  const V4* acc;
+  RRT_DEV static size_t plane_n(const SceneDev<R>& s) { return 4 * (size_t)s.xres * (size_t)s.yres; }
+  RRT_DEV Pixel load(const SceneDev<R>& s, size_t pix) const {
+    return Pixel{reinterpret_cast<const V4*>(planes)[pix], reinterpret_cast<const V4*>(planes + plane_n(s))[pix]};
   }
-  reinterpret_cast<V4*>(planes)[pix] = px.ao;
-  reinterpret_cast<V4*>(planes + plane_n)[pix] = px.bent;
-}
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_ao_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* acc,
-                                                     int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
-  using V4 = typename Vec4T<R>::type;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint32_t)ew * (uint32_t)eh) return;
-  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
-  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
-  AoPixel<R> px{reinterpret_cast<const V4*>(planes)[pix], reinterpret_cast<const V4*>(planes + plane_n)[pix]};
-  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
-    if (sy < 0 || sy >= ymax) continue;
-    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
-      uint32_t pl;
-      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
-      for (uint32_t sl = 0; sl < pd.ns; sl++) {
-        const uint32_t slot = sl * pd.npix + pl;
-        if (!(p.weight[slot] > R(0))) continue;
-        const V4 cs = p.samp[slot];
-        R fw;
-        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
-        ao_add(px, fw, acc[slot]);
-      }
-    }
+  RRT_DEV void add(Pixel& px, R fw, uint32_t slot) const { ao_add(px, fw, acc[slot]); }
+  RRT_DEV void store(const SceneDev<R>& s, size_t pix, const Pixel& px) const {
+    reinterpret_cast<V4*>(planes)[pix] = px.ao;
+    reinterpret_cast<V4*>(planes + plane_n(s))[pix] = px.bent;
   }
-  reinterpret_cast<V4*>(planes)[pix] = px.ao;
-  reinterpret_cast<V4*>(planes + plane_n)[pix] = px.bent;
-}
+};
 
 // ------------------------------------------------------------------------------------------------------------
-// Frame forms of the three kernels above (rrt_render_frame_aov, include/rrt.h): the feature buffers from the frame's own bounce-0 queue.
+// Frame forms of k_aov_shade and AovAcc (rrt_render_frame_aov, include/rrt.h): the feature buffers from the frame's own bounce-0 queue.
 // A frame's camera kernels run with the root cull: a live camera ray that misses the root box has weight[slot] > 0 and never enters the
 // queue, so "every live sample is in the queue" does not hold and nothing writes its rec_a - the slot keeps what an earlier pass left.
 // Such a sample is a miss. The shading kernel therefore stamps rec_a.w with {serial of the pass << 1 | hit bit}; the serial is non-zero and
 // used by no earlier pass that wrote into the handle's record buffers (the host counts it up, and the buffers are zeroed when allocated;
-// k_aov_shade's own flag words 0 and 1 carry serial 0), and the gather kernels read every other stamp as a miss. Kernels of their own, not
-// a template flag: the code rrt_render_aov launches stays what it is. The sums go through aov_rho, aov_add, aov_load, aov_store and
-// film_wide_weight, so the arithmetic per sample is the same expressions, in the same order.
+// k_aov_shade's own flag words 0 and 1 carry serial 0), and the gather reads every other stamp as a miss. The shading kernel is one of
+// its own, not a template flag on k_aov_shade: the code rrt_render_aov launches stays what it is. The gather is the skeletons' own loops around
+// AovFrameAcc, which differs from AovAcc in the rec_a read alone, so the arithmetic per sample is the same expressions, in the same order.
 // ------------------------------------------------------------------------------------------------------------
-// rec_a as a gather kernel of the frame form takes it: the record of this pass's own stamp, a miss otherwise
+// rec_a as the gather of the frame form takes it: the record of this pass's own stamp, a miss otherwise
 template <typename R>
 RRT_DEV typename Vec4T<R>::type aov_frame_rec(const typename Vec4T<R>::type* rec_a, uint32_t slot, uint32_t serial) {
   typename Vec4T<R>::type a = rec_a[slot];
@@ -2134,55 +2133,18 @@ __global__ void __launch_bounds__(kBlock) k_aov_shade_frame(SceneDev<R> s, Pools
   }
 }
 
-// k_aov_box over the leading pd.ns samples of a frame's pass (the host cuts pd.ns to the feature buffers' prefix)
+// AovAcc over the leading pd.ns samples of a frame's pass (the host cuts pd.ns to the feature buffers' prefix): rec_a read through the pass's stamp
 template <typename R>
-__global__ void __launch_bounds__(kBlock) k_aov_box_frame(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b, uint32_t serial) {
-  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pl >= pd.npix) return;
-  uint32_t px_, py_;
-  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
-  const size_t pix = (size_t)py_ * (size_t)s.xres + px_, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
-  AovPixel<R> px = aov_load(planes, plane_n, pix);
-  for (uint32_t sl = 0; sl < pd.ns; sl++) {
-    const uint32_t slot = sl * pd.npix + pl;
-    if (!(p.weight[slot] > R(0))) continue;   // dead sample
-    aov_add(px, R(1), aov_frame_rec<R>(rec_a, slot, serial), rec_b, slot);   // box filter table weight 1
-  }
-  aov_store(planes, plane_n, pix, px);
-}
-
-// k_aov_wide over the leading pd.ns samples of a frame's pass
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_aov_wide_frame(SceneDev<R> s, Pools<R> p, PassDesc pd, R* planes, const typename Vec4T<R>::type* rec_a, const typename Vec4T<R>::type* rec_b, uint32_t serial,
-                                                            int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint32_t)ew * (uint32_t)eh) return;
-  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
-  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x, plane_n = 4 * (size_t)s.xres * (size_t)s.yres;
-  AovPixel<R> px = aov_load(planes, plane_n, pix);
-  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
-    if (sy < 0 || sy >= ymax) continue;
-    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
-      uint32_t pl;
-      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
-      for (uint32_t sl = 0; sl < pd.ns; sl++) {
-        const uint32_t slot = sl * pd.npix + pl;
-        if (!(p.weight[slot] > R(0))) continue;
-        const typename Vec4T<R>::type cs = p.samp[slot];
-        R fw;
-        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
-        aov_add(px, fw, aov_frame_rec<R>(rec_a, slot, serial), rec_b, slot);
-      }
-    }
-  }
-  aov_store(planes, plane_n, pix, px);
-}
+struct AovFrameAcc : AovAcc<R> {
+  uint32_t serial;
+  RRT_DEV void add(typename AovAcc<R>::Pixel& px, R fw, uint32_t slot) const { aov_add(px, fw, aov_frame_rec<R>(this->rec_a, slot, serial), this->rec_b, slot); }
+};
 
 // ------------------------------------------------------------------------------------------------------------
 // Feature buffers through mirrors and glass (rrt_render_aov_follow, include/rrt.h): the record of the first non-specular surface along
 // the chain of perfectly specular bounces a camera ray starts. A kernel of its own, not a template flag on k_aov_shade: the code
 // rrt_render_aov and rrt_render_frame_aov launch stays what it is. The first hits' records are k_aov_shade's own, rho goes through aov_rho and
-// the planes through k_aov_box / k_aov_wide unchanged, so a chain of length 0 leaves rrt_render_aov's bits.
+// the planes through the gather over AovAcc unchanged, so a chain of length 0 leaves rrt_render_aov's bits.
 // ------------------------------------------------------------------------------------------------------------
 // The continuation of the chain at a hit, by the rules on the prototype: Mirror reflects about the shading normal; smooth Glass refracts
 // (reflection.rs:122-134, wo = -d, the normal turned towards wo) and reflects where there is no refracted direction or Kt is black. `m` has
@@ -2303,12 +2265,15 @@ __global__ void __launch_bounds__(kBlock) k_aov_follow(SceneDev<R> s, Pools<R> p
 
 // k_film_box with two more running sums per pixel: the same passes, the same sequential sample order in both of its paths, so neither the film
 // nor the moments depend on how the frame was cut into passes. S0 = S3 = the sample count, which the film's weight sum already is.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_film_box_moments(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, R* mom) {
+// LISTED: a listed pass (list_pixel over `list`, rrt_render_adaptive) instead of a rect's pixel group (pass_pixel; `list` is not read) - the
+// pixel decode is all that differs, so a pixel that a listed pass continues holds what a longer rect pass would have left in it.
+template <typename R, bool LISTED>
+__global__ void __launch_bounds__(kBlock) k_film_box_moments(SceneDev<R> s, Pools<R> p, PassDesc pd, const uint32_t* list, R* film, R* mom) {
   const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
   if (pl >= pd.npix) return;
   uint32_t px_, py_;
-  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
+  if constexpr (LISTED) list_pixel(pd, list, pd.pix_begin + pl, &px_, &py_);
+  else pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
   const uint32_t pix = py_ * (uint32_t)s.xres + px_;
   R* px = film + 4 * (size_t)pix;
   R* pm = mom + 4 * (size_t)pix;
@@ -2342,17 +2307,17 @@ __global__ void __launch_bounds__(kBlock) k_film_box_moments(SceneDev<R> s, Pool
 
 // k_film_wide with the four running sums of the pixel
 template <typename R>
-__global__ void __launch_bounds__(kBlock) k_film_wide_moments(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, R* mom, int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
+__global__ void __launch_bounds__(kBlock) k_film_wide_moments(SceneDev<R> s, Pools<R> p, PassDesc pd, R* film, R* mom, FilmWindow win) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint32_t)ew * (uint32_t)eh) return;
-  const int x = ex0 + (int)(t % (uint32_t)ew), y = ey0 + (int)(t / (uint32_t)ew);
+  if (t >= (uint32_t)win.ew * (uint32_t)win.eh) return;
+  const int x = win.ex0 + (int)(t % (uint32_t)win.ew), y = win.ey0 + (int)(t / (uint32_t)win.ew);
   R* px = film + 4 * ((size_t)y * (size_t)s.xres + (size_t)x);
   R* pm = mom + 4 * ((size_t)y * (size_t)s.xres + (size_t)x);
   R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];
   R s1 = pm[0], s2 = pm[1], s0 = pm[2], s3 = pm[3];
-  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
-    if (sy < 0 || sy >= ymax) continue;
-    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
+  for (int sy = y - win.reach_y; sy <= y + win.reach_y; sy++) {
+    if (sy < 0 || sy >= win.ymax) continue;
+    for (int sx = x - win.reach_x; sx <= x + win.reach_x; sx++) {
       uint32_t pl;
       if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
       for (uint32_t sl = 0; sl < pd.ns; sl++) {
@@ -2373,45 +2338,6 @@ __global__ void __launch_bounds__(kBlock) k_film_wide_moments(SceneDev<R> s, Poo
   }
   px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
   pm[0] = s1; pm[1] = s2; pm[2] = s0; pm[3] = s3;
-}
-
-// k_film_box_moments over a listed pass (list_pixel): the same running sums, added through the same functions in the same sample order in both of its
-// paths, so a pixel that a listed pass continues holds what a longer rect pass would have left in it.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_film_box_moments_list(SceneDev<R> s, Pools<R> p, PassDesc pd, const uint32_t* list, R* film, R* mom) {
-  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pl >= pd.npix) return;
-  uint32_t px_, py_;
-  list_pixel(pd, list, pd.pix_begin + pl, &px_, &py_);
-  const uint32_t pix = py_ * (uint32_t)s.xres + px_;
-  R* px = film + 4 * (size_t)pix;
-  R* pm = mom + 4 * (size_t)pix;
-  R cr = px[0], cg = px[1], cb = px[2], wsum = px[3];
-  R s1 = pm[0], s2 = pm[1];
-  constexpr uint32_t kBatch = 8;
-  auto add = [&](R w, const typename Vec4T<R>::type& l) {
-    film_box_add(s, cr, cg, cb, wsum, w, l);
-    const R y = film_sample_radiance(s, w, l).y() * w;
-    s1 += y; s2 += y * y;
-  };
-  uint32_t sl = 0;
-  if (pd.npix < (1u << 18))
-  for (; sl + kBatch <= pd.ns; sl += kBatch) {
-    R wb[kBatch];
-    typename Vec4T<R>::type lb[kBatch];
-#pragma unroll
-    for (uint32_t k = 0; k < kBatch; k++) { wb[k] = p.weight[(sl + k) * pd.npix + pl]; lb[k] = p.L[(sl + k) * pd.npix + pl]; }
-#pragma unroll
-    for (uint32_t k = 0; k < kBatch; k++) add(wb[k], lb[k]);
-  }
-  for (; sl < pd.ns; sl++) {
-    const R w = p.weight[sl * pd.npix + pl];
-    typename Vec4T<R>::type l = mk4<R>(R(0), R(0), R(0), R(0));
-    if (w > R(0)) l = p.L[sl * pd.npix + pl];
-    add(w, l);
-  }
-  px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum;
-  pm[0] = s1; pm[1] = s2; pm[2] = wsum; pm[3] = wsum;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2476,7 +2402,7 @@ static __global__ void __launch_bounds__(kSelBlock) k_tile_select(const uint32_t
 
 // ------------------------------------------------------------------------------------------------------------
 // ID mattes (rrt_render_mattes / rrt_matte_extract, include/rrt.h): per pixel a table of K (id, coverage) slots and a weight record. A pass of
-// its own beside the k_aov_* family - camera kernels, closest-hit launch, k_matte_ids, k_matte_box / k_matte_wide - around an internal table that
+// its own beside the k_aov_* family - camera kernels, closest-hit launch, k_matte_ids, the gather over MatteAcc - around an internal table that
 // lives across the pool passes of a call: k_matte_load copies the caller's table in before the first pass, k_matte_rank sorts it out after the last.
 // The internal table is slot-major (ids[k * npix + pix], cov[k * npix + pix]: a wave's loads of one slot are consecutive); the caller's is
 // [pixel][slot]. Nothing is ever evicted: a stored coverage is then the id's complete sum, and the overflow channel says how much is missing.
@@ -2541,58 +2467,24 @@ RRT_DEV void matte_add(const MatteLds<R>& t, uint32_t K, uint32_t& last, typenam
   else w.z += fw;   // overflow: K other ids hold the slots
 }
 
-// Gather form, as k_aov_box: one thread per pixel of the pass, its samples in sample order - the arrival order of the box filter.
+// Under the gather skeletons, launched with matte_lds_bytes of dynamic LDS: a pixel's state is its LDS column, its weight record and `last`. The
+// skeletons' sample order is the arrival order the table rule of rrt.h speaks of.
 template <typename R>
-__global__ void __launch_bounds__(kBlock) k_matte_box(SceneDev<R> s, Pools<R> p, PassDesc pd, MatteTab<R> tab, const uint2* rec) {
-  const uint32_t pl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pl >= pd.npix) return;
-  uint32_t px_, py_;
-  pass_pixel(pd, pd.pix_begin + pl, &px_, &py_);
-  const size_t pix = (size_t)py_ * (size_t)s.xres + px_;
-  const MatteLds<R> t = matte_lds<R>(tab.K);
-  matte_lds_load(tab, t, pix);
-  typename Vec4T<R>::type w = tab.weight[pix];
-  uint32_t last = 0;
-  for (uint32_t sl = 0; sl < pd.ns; sl++) {
-    const uint32_t slot = sl * pd.npix + pl;
-    if (!(p.weight[slot] > R(0))) continue;   // dead sample
-    matte_add(t, tab.K, last, w, R(1), rec[slot]);   // box filter table weight 1
+struct MatteAcc {
+  struct Pixel { MatteLds<R> t; typename Vec4T<R>::type w; uint32_t last; };
+  MatteTab<R> tab;
+  const uint2* rec;
+  RRT_DEV Pixel load(const SceneDev<R>&, size_t pix) const {
+    const MatteLds<R> t = matte_lds<R>(tab.K);
+    matte_lds_load(tab, t, pix);
+    return Pixel{t, tab.weight[pix], 0u};
   }
-  matte_lds_store(tab, t, pix);
-  tab.weight[pix] = w;
-}
-
-// Gather form, as k_aov_wide: one thread per film pixel within reach of the pass, the samples of every pass pixel within reach, the film's own
-// footprint test and table look-up (film_wide_weight).
-template <typename R>
-__global__ void __launch_bounds__(kBlock) k_matte_wide(SceneDev<R> s, Pools<R> p, PassDesc pd, MatteTab<R> tab, const uint2* rec,
-                                                        int ex0, int ey0, int ew, int eh, int reach_x, int reach_y, int ymax) {
-  const uint32_t tt = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tt >= (uint32_t)ew * (uint32_t)eh) return;
-  const int x = ex0 + (int)(tt % (uint32_t)ew), y = ey0 + (int)(tt / (uint32_t)ew);
-  const size_t pix = (size_t)y * (size_t)s.xres + (size_t)x;
-  const MatteLds<R> t = matte_lds<R>(tab.K);
-  matte_lds_load(tab, t, pix);
-  typename Vec4T<R>::type w = tab.weight[pix];
-  uint32_t last = 0;
-  for (int sy = y - reach_y; sy <= y + reach_y; sy++) {
-    if (sy < 0 || sy >= ymax) continue;
-    for (int sx = x - reach_x; sx <= x + reach_x; sx++) {
-      uint32_t pl;
-      if (sx < 0 || sx >= s.xres || !pass_pixel_inverse(pd, sx, sy, &pl)) continue;
-      for (uint32_t sl = 0; sl < pd.ns; sl++) {
-        const uint32_t slot = sl * pd.npix + pl;
-        if (!(p.weight[slot] > R(0))) continue;
-        const typename Vec4T<R>::type cs = p.samp[slot];
-        R fw;
-        if (!film_wide_weight(s, cs.x, cs.y, x, y, &fw)) continue;
-        matte_add(t, tab.K, last, w, fw, rec[slot]);
-      }
-    }
+  RRT_DEV void add(Pixel& px, R fw, uint32_t slot) const { matte_add(px.t, tab.K, px.last, px.w, fw, rec[slot]); }
+  RRT_DEV void store(const SceneDev<R>&, size_t pix, const Pixel& px) const {
+    matte_lds_store(tab, px.t, pix);
+    tab.weight[pix] = px.w;
   }
-  matte_lds_store(tab, t, pix);
-  tab.weight[pix] = w;
-}
+};
 
 // the caller's [pixel][slot] table into the internal slot-major one: one thread per (pixel, slot), reads consecutive
 template <typename R>

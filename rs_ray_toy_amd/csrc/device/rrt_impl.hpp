@@ -109,7 +109,7 @@ struct FrameRec {
 template <typename R>
 class Handle : public HandleBase {
   // ---- what the entry points below share: the argument checks, the pixel and sample counts of a call, the film window of a wide filter ---------
-  // The film kernels in their box form (k_film_box, k_aov_box, k_matte_box ...) are the closed form for the default box filter (radius exactly
+  // The film kernels in their box form (k_film_box, k_gather_box ...) are the closed form for the default box filter (radius exactly
   // 0.5: every sample lands in its own pixel with weight 1); a smaller radius leaves samples near the pixel borders in no pixel at all, a larger
   // one splats: both take the general (wide) kernels
   bool wide_filter() const {
@@ -139,14 +139,20 @@ class Handle : public HandleBase {
     const uint64_t nsamp = desc_.sampler.samples_per_pixel, n = nsamp > 1 ? nsamp - 1 : 0;
     return max_samples != 0 ? std::min(n, max_samples) : n;
   }
-  // the film pixels the samples of a rect can touch under a wide filter: the rect grown by ceil(r + 0.5), clipped to the film; n = ew x eh
-  struct FilmWindow { int ex0, ey0, ew, eh, reach_x, reach_y; size_t n; };
+  // the film pixels the samples of a rect can touch under a wide filter (FilmWindow): the rect grown by ceil(r + 0.5), clipped to the film
   FilmWindow film_window(const int32_t rect[4]) const {
     const rrt_film& f = desc_.film;
     const int reach_x = (int)std::ceil(f.filter_radius[0] + 0.5), reach_y = (int)std::ceil(f.filter_radius[1] + 0.5);
     const int ex0 = std::max(0, rect[0] - reach_x), ey0 = std::max(0, rect[1] - reach_y);
     const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
-    return {ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, (size_t)(ex1 - ex0) * (size_t)(ey1 - ey0)};
+    return {ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres};
+  }
+  // what the first-hit calls work out of their arguments once the checks have passed: this rank's bands of the rect, the samples of a pixel, the window
+  struct CallGeom { uint32_t band_h; size_t rw, rh, rpix; uint64_t s_total; FilmWindow win; };
+  CallGeom call_geom(const int32_t rect[4], int rank, int world, uint64_t max_samples) const {
+    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
+    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank);
+    return {band_h, rw, rh, rw * rh, frame_samples(max_samples), film_window(rect)};
   }
   // What launch_raygen sets for the pass it last ran for, put back when a first-hit call ends (a frame's tile-tree and film-record state is its
   // own), and the queue halves as the call found them (swapped: the follow levels have swapped them an odd number of times)
@@ -536,7 +542,7 @@ class Handle : public HandleBase {
   // ---- rrt_render_frame_aov: the moments frame and the feature buffers of rrt_render_aov from one camera pass --------------------------------------------
   // Which scenes take which route. A frame whose passes begin with a queued closest-hit launch over the camera rays - the Path integrator, and
   // DirectLighting / Debug on scenes without transmissive or textured materials (the level loop of run_pass) - is fused: run_pass shades the first
-  // hits from the bounce-0 queue (k_aov_shade_frame) and gathers them beside the moments film kernel (k_aov_box_frame / k_aov_wide_frame). A frame
+  // hits from the bounce-0 queue (k_aov_shade_frame) and gathers them beside the moments film kernel (the gather skeletons over AovFrameAcc). A frame
   // that runs no such launch - the AO integrator, a Path integrator of depth 0, and DirectLighting / Debug on transmissive or textured scenes
   // (k_direct_tree: one thread per camera sample, no queue) - renders as a moments frame and render_aov's own pass follows it. Both routes add the
   // same bits.
@@ -897,14 +903,14 @@ class Handle : public HandleBase {
       }
       else if (!wide) {
         const dim3 fg((uint32_t)((npix + kBlock - 1) / kBlock));
-        if (list) hipLaunchKernelGGL((k_film_box_moments_list<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_dst, moments_.p);
-        else if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p);
+        if (list) hipLaunchKernelGGL((k_film_box_moments<R, true>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_dst, moments_.p);
+        else if (with_moments) hipLaunchKernelGGL((k_film_box_moments<R, false>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, list, film_dst, moments_.p);
         else hipLaunchKernelGGL((k_film_box<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst);
       }
       else {
-        const dim3 fg((uint32_t)((win.n + kBlock - 1) / kBlock));
-        if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p, win.ex0, win.ey0, win.ew, win.eh, win.reach_x, win.reach_y, f.yres);
-        else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, win.ex0, win.ey0, win.ew, win.eh, win.reach_x, win.reach_y, f.yres);
+        const dim3 fg((uint32_t)((win.n() + kBlock - 1) / kBlock));
+        if (with_moments) hipLaunchKernelGGL((k_film_wide_moments<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, moments_.p, win);
+        else hipLaunchKernelGGL((k_film_wide<R>), fg, dim3(kBlock), 0, st_, scene_, pool_, pd, film_dst, win);
       }
     }
     pool_.L = frame_L;
@@ -944,18 +950,17 @@ class Handle : public HandleBase {
   }
   // second half, beside the moments film kernel: the pass's PassDesc with ns cut to the feature buffers' samples, gathered into the internal planes
   void launch_aov_gather_frame(PassDesc pd, uint32_t aov_ns, const FilmWindow& w) {
-    using V4 = typename Vec4T<R>::type;
     pd.ns = aov_ns;
-    if (!wide_filter()) hipLaunchKernelGGL((k_aov_box_frame<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_);
-    else hipLaunchKernelGGL((k_aov_wide_frame<R>), dim3((uint32_t)((w.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p, aov_serial_,
-                            w.ex0, w.ey0, w.ew, w.eh, w.reach_x, w.reach_y, desc_.film.yres);
+    launch_gather(AovFrameAcc<R>{aov_acc(), aov_serial_}, pd, w);
   }
-  // the gather of the first-hit calls (render_aov, render_aov_follow): every sample of the pass, the records k_aov_shade / k_aov_follow left
-  void launch_aov_gather(const PassDesc& pd, const FilmWindow& w) {
-    using V4 = typename Vec4T<R>::type;
-    if (!wide_filter()) hipLaunchKernelGGL((k_aov_box<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p);
-    else hipLaunchKernelGGL((k_aov_wide<R>), dim3((uint32_t)((w.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, aov_planes_.p, (const V4*)aov_rec_a_.p, (const V4*)aov_rec_b_.p,
-                            w.ex0, w.ey0, w.ew, w.eh, w.reach_x, w.reach_y, desc_.film.yres);
+  // the accumulator of the first-hit calls (render_aov, render_aov_follow): the internal planes, the records k_aov_shade / k_aov_follow left
+  AovAcc<R> aov_acc() const { return {aov_planes_.p, aov_rec_a_.p, aov_rec_b_.p}; }
+  // One gather of a pass into a pixel state `acc` describes (dkernels.hpp, the gather skeletons): the box form over the pass's pixels under the
+  // default box filter, the wide form over the window's otherwise. lds_bytes: the dynamic LDS the accumulator asks for.
+  template <class Acc>
+  void launch_gather(const Acc& acc, const PassDesc& pd, const FilmWindow& w, size_t lds_bytes = 0) {
+    if (!wide_filter()) hipLaunchKernelGGL((k_gather_box<R, Acc>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), lds_bytes, st_, scene_, pool_, pd, acc);
+    else hipLaunchKernelGGL((k_gather_wide<R, Acc>), dim3((uint32_t)((w.n() + kBlock - 1) / kBlock)), dim3(kBlock), lds_bytes, st_, scene_, pool_, pd, acc, w);
   }
   // the per-slot records of the first-hit shading kernels, sized like the pools; rec_a - the flag words - zeroed when allocated, so that a slot no
   // kernel has written yet carries no pass's stamp (k_aov_shade_frame)
@@ -967,16 +972,20 @@ class Handle : public HandleBase {
   }
   // the internal feature planes added to the caller's non-NULL planes (+=)
   void aov_merge_out(const rrt_aov* out) {
+    void* const user[3] = {out->albedo, out->normal, out->depth};
+    merge_planes(aov_planes_.p, 3, user, out->mem);
+  }
+  // n internal W x H x 4 planes, one after the other, each added to the caller's plane of the same number where that is not NULL (+=)
+  void merge_planes(const R* planes, int n, void* const* user, int mem) {
     const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
-    void* user[3] = {out->albedo, out->normal, out->depth};
-    if (out->mem == RRT_MEM_DEVICE) {
-      for (int k = 0; k < 3; k++)
-        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)(aov_planes_.p + k * plane_n), (R*)user[k], plane_n);
+    if (mem == RRT_MEM_DEVICE) {
+      for (int k = 0; k < n; k++)
+        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, planes + k * plane_n, (R*)user[k], plane_n);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipStreamSynchronize(st_));
     } else {
-      for (int k = 0; k < 3; k++)
-        if (user[k]) add_to_host(aov_planes_.p + k * plane_n, (R*)user[k], plane_n);
+      for (int k = 0; k < n; k++)
+        if (user[k]) add_to_host(planes + k * plane_n, (R*)user[k], plane_n);
     }
   }
   // a device plane added to a host array (+=): staged, one synchronisation of the stream
@@ -1126,7 +1135,7 @@ class Handle : public HandleBase {
   // One body: rrt_render_aov is rrt_render_aov_follow with max_follow = 0 under its own name. shade: k_aov_shade for the first hits' records, then
   // per level k_aov_follow, the queue rotation and a closest-hit launch over the device-side count of followed entries - no host read-back
   // between levels, launches sized by the pass like the path loop's; with max_follow = 0 the level loop ends before its first launch. gather:
-  // k_aov_box / k_aov_wide into the handle's internal planes, which aov_merge_out adds to the caller's. The guard also puts the queue halves back
+  // the skeletons over AovAcc into the handle's internal planes, which aov_merge_out adds to the caller's. The guard also puts the queue halves back
   // that the levels swap.
   void render_aov(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_aov* out) override {
     aov_passes("render_aov", rect, rank, world, max_samples, 0, out);
@@ -1142,21 +1151,18 @@ class Handle : public HandleBase {
     check_renderable();
     check_no_crop();
     check_rect((who + ": rect outside the film").c_str(), rect);
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
     const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank), rpix = rw * rh;
-    const uint64_t s_total = frame_samples(max_samples);
-    if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
+    const CallGeom g = call_geom(rect, rank, world, max_samples);
+    if (g.rpix == 0 || g.s_total == 0) return;   // nothing to add to the caller's planes
     if (!has_specular_) max_follow = 0;   // no surface of the scene is followed: every chain ends on its first hit, and no level is launched to find that out
     RaygenStateGuard guard(this);
 
     if (aov_planes_.n != 3 * plane_n) aov_planes_.alloc(3 * plane_n);
     HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
-    ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+    ensure_pools(std::min(max_paths_, std::max<size_t>(g.rpix * (size_t)g.s_total, 64)));
     ensure_aov_recs();
-    const FilmWindow win = film_window(rect);
-    first_hit_passes(rect, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, s_total,
+    first_hit_passes(rect, g.band_h, (uint32_t)world, (uint32_t)rank, g.rw, g.rh, g.s_total,
       [&](const PassDesc&, uint32_t grid) {
         const dim3 sg(std::min(grid, 16384u));
         // level 0's records are k_aov_shade's own (see k_aov_follow)
@@ -1173,11 +1179,11 @@ class Handle : public HandleBase {
           launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, false, nullptr, nullptr, nullptr, grid, /*camera_rays=*/false);
         }
       },
-      [&](const PassDesc& pd) { launch_aov_gather(pd, win); });
+      [&](const PassDesc& pd) { launch_gather(aov_acc(), pd, g.win); });
     aov_merge_out(out);   // into the caller's planes (+=)
     check_device_errors();
   }
-  // ---- ambient occlusion and bent normals (rrt_render_ao): first_hit_passes with shade = the draw rounds, gather = k_ao_box / k_ao_wide -----------------
+  // ---- ambient occlusion and bent normals (rrt_render_ao): first_hit_passes with shade = the draw rounds, gather = the skeletons over AoAcc ----------
   // Round i of a pass handles draw i of every hit of the pass: k_ao_gen pushes one hemisphere ray per hit into the pool's shadow queue (never more
   // entries than the camera queue, so no queue exceeds the pool), the any-hit launch over that queue adds the free rays' records into the per-slot
   // accumulators (Pools::L points at them for the call). A slot occurs once per round and the rounds follow each other on the stream: the sums need
@@ -1210,11 +1216,9 @@ class Handle : public HandleBase {
     HIP_CHECK(hipSetDevice(dev_));
     check_renderable();
     check_no_crop();
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
     const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank), rpix = rw * rh;
-    const uint64_t s_total = frame_samples(max_samples);
-    if (rpix == 0 || s_total == 0) return;   // nothing to add to the caller's planes
+    const CallGeom g = call_geom(rect, rank, world, max_samples);
+    if (g.rpix == 0 || g.s_total == 0) return;   // nothing to add to the caller's planes
     RaygenStateGuard guard(this);
     // what the rounds borrow of the pool: L (the accumulators' place) and the first shadow queue, put back on every way out
     struct PoolGuard {
@@ -1226,16 +1230,15 @@ class Handle : public HandleBase {
     if (ao_planes_.n != 2 * plane_n) ao_planes_.alloc(2 * plane_n);
     HIP_CHECK(hipMemsetAsync(ao_planes_.p, 0, 2 * plane_n * sizeof(R), st_));
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
-    ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+    ensure_pools(std::min(max_paths_, std::max<size_t>(g.rpix * (size_t)g.s_total, 64)));
     if (ao_acc_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); ao_acc_.alloc(cap_); }
     PoolGuard pool_guard(pool_);
     pool_.L = ao_acc_.p;
     pool_.sray_o = shadow_buf_[0][0]; pool_.sray_d = shadow_buf_[0][1]; pool_.sld = shadow_buf_[0][2];
     pool_.shadow_count = counters_.p + C_SHADOW;
-    const FilmWindow win = film_window(rect);
     const uint32_t n_draws = (uint32_t)prm.n_samples;
     const int cos_sample = prm.cos_sample ? 1 : 0;
-    first_hit_passes(rect, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, s_total,
+    first_hit_passes(rect, g.band_h, (uint32_t)world, (uint32_t)rank, g.rw, g.rh, g.s_total,
       [&](const PassDesc&, uint32_t grid) {
         for (uint32_t i = 0; i < n_draws; i++) {
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);   // the shadow queue and the work cursors start at 0
@@ -1243,25 +1246,12 @@ class Handle : public HandleBase {
           launch_ao_any(grid);
         }
       },
-      [&](const PassDesc& pd) {
-        if (!wide_filter()) hipLaunchKernelGGL((k_ao_box<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, ao_planes_.p, (const V4*)ao_acc_.p);
-        else hipLaunchKernelGGL((k_ao_wide<R>), dim3((uint32_t)((win.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, pool_, pd, ao_planes_.p, (const V4*)ao_acc_.p,
-                                win.ex0, win.ey0, win.ew, win.eh, win.reach_x, win.reach_y, desc_.film.yres);
-      });
-    // into the caller's planes (+=)
-    void* user[2] = {out->ao, out->bent};
-    if (out->mem == RRT_MEM_DEVICE) {
-      for (int k = 0; k < 2; k++)
-        if (user[k]) hipLaunchKernelGGL((k_aov_merge<R>), dim3((uint32_t)((plane_n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, (const R*)(ao_planes_.p + k * plane_n), (R*)user[k], plane_n);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipStreamSynchronize(st_));
-    } else {
-      for (int k = 0; k < 2; k++)
-        if (user[k]) add_to_host(ao_planes_.p + k * plane_n, (R*)user[k], plane_n);
-    }
+      [&](const PassDesc& pd) { launch_gather(AoAcc<R>{ao_planes_.p, ao_acc_.p}, pd, g.win); });
+    void* const user[2] = {out->ao, out->bent};
+    merge_planes(ao_planes_.p, 2, user, out->mem);   // into the caller's planes (+=)
     check_device_errors();
   }
-  // ---- ID mattes (rrt_render_mattes): first_hit_passes with shade = k_matte_ids and gather = k_matte_box / k_matte_wide into a (id, coverage) table -----
+  // ---- ID mattes (rrt_render_mattes): first_hit_passes with shade = k_matte_ids and gather = the skeletons over MatteAcc into a (id, coverage) table --
   // Per call: the ids of the entries of prim_order are built on the host and uploaded (they are the caller's, not the scene's: nothing of the scene
   // preparation knows them), the caller's table is copied into the internal slot-major one (k_matte_load; a host table is staged), the passes insert
   // into it, k_matte_rank sorts it out. Load, rank and the staging of a host table run over the whole W x H x K table whatever the rect - also for
@@ -1276,14 +1266,11 @@ class Handle : public HandleBase {
     check_renderable();
     check_no_crop();
     check_rect("render_mattes: rect outside the film", rect);
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
     const size_t NP = (size_t)desc_.film.xres * (size_t)desc_.film.yres;
     const uint32_t K = (uint32_t)out->n_slots;
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank), rpix = rw * rh;
-    const uint64_t s_total = frame_samples(max_samples);
+    const CallGeom g = call_geom(rect, rank, world, max_samples);
     using V4 = typename Vec4T<R>::type;
     RaygenStateGuard guard(this);
-
 
     // the id of every entry of prim_order
     const size_t n_ord = matte_order_.size();
@@ -1315,20 +1302,14 @@ class Handle : public HandleBase {
     HIP_CHECK(hipGetLastError());
 
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));   // also where no pass runs: check_device_errors below reads them
-    if (rpix > 0 && s_total > 0) {
-      ensure_pools(std::min(max_paths_, std::max<size_t>(rpix * (size_t)s_total, 64)));
+    if (g.rpix > 0 && g.s_total > 0) {
+      ensure_pools(std::min(max_paths_, std::max<size_t>(g.rpix * (size_t)g.s_total, 64)));
       if (matte_rec_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); matte_rec_.alloc(cap_); }
-      const bool wide = wide_filter();
-      const FilmWindow w = film_window(rect);
-      first_hit_passes(rect, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, s_total,
+      first_hit_passes(rect, g.band_h, (uint32_t)world, (uint32_t)rank, g.rw, g.rh, g.s_total,
         [&](const PassDesc&, uint32_t grid) {
           hipLaunchKernelGGL((k_matte_ids<R>), dim3(std::min(grid, 16384u)), dim3(kBlock), 0, st_, pool_, (const uint32_t*)matte_id_dev_.p, (uint32_t)n_ord, matte_rec_.p);
         },
-        [&](const PassDesc& pd) {
-          if (!wide) hipLaunchKernelGGL((k_matte_box<R>), dim3((uint32_t)((pd.npix + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p);
-          else hipLaunchKernelGGL((k_matte_wide<R>), dim3((uint32_t)((w.n + kBlock - 1) / kBlock)), dim3(kBlock), lds, st_, scene_, pool_, pd, tab, (const uint2*)matte_rec_.p,
-                                  w.ex0, w.ey0, w.ew, w.eh, w.reach_x, w.reach_y, desc_.film.yres);
-        });
+        [&](const PassDesc& pd) { launch_gather(MatteAcc<R>{tab, matte_rec_.p}, pd, g.win, lds); });
     }
     // ranked, into the caller's table
     hipLaunchKernelGGL((k_matte_rank<R>), dim3(pix_grid), dim3(kBlock), lds, st_, tab, host ? matte_stage_ids_.p : out->ids, host ? matte_stage_cov_.p : (R*)out->coverage);

@@ -367,7 +367,7 @@ def test_pass_cutting_changes_no_bit(prec, workdir):
 @PRECS
 @pytest.mark.parametrize("min_samples,batch", [(4, 8), (2, 10)], ids=["8", "8+2"])
 def test_listed_passes_of_eight_samples_or_more(min_samples, batch, prec, workdir):
-    """A listed pass of fewer than 2^18 pixels and 8 samples or more takes k_film_box_moments_list's batched-by-8 loop (batch 8: exactly one batch;
+    """A listed pass of fewer than 2^18 pixels and 8 samples or more takes the batched-by-8 loop of k_film_box_moments in its listed form (batch 8: exactly one batch;
     batch 10: a batch and the tail of 2) - the loop the default batch of 16 runs. Threshold 0: the moments frame's bits; threshold 0.95: the tiles
     that stopped at min_samples and those that went on to K, each equal to the shorter frame."""
     r = Renderer(_scene("A", workdir), 0, prec)

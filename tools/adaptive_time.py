@@ -159,7 +159,7 @@ def kernel_split(reps):
     f = sorted(glob.glob(out_dir + "/**/*kernel_stats.csv", recursive=True))[0]
     split = {}
     for row in csv.DictReader(open(f)):
-        m = re.search(r"(k_tile_error|k_tile_select|k_film_box_moments_list|k_film_box_moments|k_pixel_offsets_list|k_pixel_offsets)\b", row["Name"])
+        m = re.search(r"(k_tile_error|k_tile_select|k_film_box_moments<\w+, true>|k_film_box_moments|k_pixel_offsets_list|k_pixel_offsets)", row["Name"])
         if m: split[m.group(1)] = dict(calls=int(row["Calls"]), avg_us=float(row["AverageNs"]) / 1e3, min_us=float(row["MinNs"]) / 1e3)
     return split
 

@@ -5,7 +5,7 @@ option frame_stats on (any_queries / ms_any: what `bench.py --full` reports one 
 
 The per-kernel split comes from a run of its own: this script starts `rocprofv3 --kernel-trace --stats` (no counters) over a child process of itself
 that makes the rrt_render_ao call reps + 1 times (the warm-up included), and reads k_ao_gen, the any-hit launches (the k_trace_* instantiations whose
-first template argument is true) and k_ao_box from the stats table; any-hit rays per second = hit samples x draws / any-hit kernel time.
+first template argument is true) and k_gather_box (the gather over AoAcc) from the stats table; any-hit rays per second = hit samples x draws / any-hit kernel time.
 --no-profile skips it.
 
 Prints one JSON line; RRT_RESULTS_DIR=<dir> also keeps it as <dir>/ao_time.json.
@@ -122,7 +122,7 @@ def main():
         split = kernel_split(reps)
         out["kernel_split_us"] = split
         any_us = sum(e["total_us"] for k, e in split.items() if k.endswith("<any>"))
-        out["ao_kernels_ms_per_call"] = {k: split[k]["total_us"] / 1e3 / (reps + 1) for k in ("k_ao_gen", "k_ao_box") if k in split}
+        out["ao_kernels_ms_per_call"] = {k: split[k]["total_us"] / 1e3 / (reps + 1) for k in ("k_ao_gen", "k_gather_box") if k in split}
         out["ao_kernels_ms_per_call"]["any_hit"] = any_us / 1e3 / (reps + 1)
         out["ao_any_rays_per_s"] = hit_samples * DRAWS * (reps + 1) / (any_us * 1e-6) if any_us > 0 else None
     line = json.dumps(out)

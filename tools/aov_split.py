@@ -14,7 +14,7 @@ rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 first = [i for i, r in enumerate(rows) if "k_pixel_offsets" in r["Kernel_Name"] or "k_raygen<" in r["Kernel_Name"]][-1]
 FAMILIES = (("camera", ("k_pixel_offsets", "k_raygen")), ("traversal", ("k_trace_", "k_closest", "k_tt_snapshot")), ("k_aov_shade", ("k_aov_shade",)),
-            ("film", ("k_aov_box", "k_aov_wide")), ("merge", ("k_aov_merge",)))
+            ("film", ("k_gather_box", "k_gather_wide")), ("merge", ("k_aov_merge",)))
 total = {}
 for r in rows[first:]:
     name = r["Kernel_Name"]

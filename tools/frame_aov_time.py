@@ -31,7 +31,7 @@ def split(trace_dir):
     before = [i for i, r in enumerate(rows) if i < shade[-1] and ("k_aov_merge" in r["Kernel_Name"] or "k_film_add" in r["Kernel_Name"])]
     first = before[-1] + 1 if before else 0
     per_call = len([i for i in shade if i >= first])
-    families = (("k_aov_shade_frame", ("k_aov_shade_frame",)), ("gather", ("k_aov_box_frame", "k_aov_wide_frame")), ("merge", ("k_aov_merge", "k_film_add")),
+    families = (("k_aov_shade_frame", ("k_aov_shade_frame",)), ("gather", ("k_gather_box", "k_gather_wide")), ("merge", ("k_aov_merge", "k_film_add")),
                 ("camera", ("k_pixel_offsets", "k_raygen")), ("traversal", ("k_trace_", "k_closest", "k_tt_snapshot")), ("shading", ("k_shade_",)),
                 ("film", ("k_film_",)))
     total = {}
