@@ -106,6 +106,21 @@ struct FrameRec {
   FrameRec& operator=(const FrameRec&) = delete;
 };
 
+// ---- launch dispatch: run-time facts into template arguments. A launcher writes its kernel's launch once, in a generic lambda, and takes the
+// flags as arguments: `MIXED()` inside it is a constant. Only what a launcher asks for is instantiated ("Traversal launches").
+template <bool B> using Flag = std::integral_constant<bool, B>;
+constexpr Flag<true> kYes{};
+constexpr Flag<false> kNo{};
+template <class F> void with_flag(bool b, F&& f) { if (b) f(kYes); else f(kNo); }
+// What an any-hit launch does with a free ray: the frame's L (film), the pending radiance of a rrt_render_passes frame (the kernels' PASSES),
+// or the accumulators of a rrt_render_ao round (their AO). No kernel has PASSES and AO together: f(PASSES, AO) sees the three that exist.
+enum class AnySink { film, passes, ao };
+template <class F> void with_sink(AnySink s, F&& f) {
+  if (s == AnySink::ao) f(kNo, kYes);
+  else if (s == AnySink::passes) f(kYes, kNo);
+  else f(kNo, kNo);
+}
+
 template <typename R>
 class Handle : public HandleBase {
   // ---- what the entry points below share: the argument checks, the pixel and sample counts of a call, the film window of a wide filter ---------
@@ -297,10 +312,7 @@ class Handle : public HandleBase {
     if (rays->mem != RRT_MEM_DEVICE) { occ.alloc(n); dst = occ.p; }
     const uint32_t grid = (uint32_t)((n + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 3);
-    if (use_persistent()) launch_persistent(true, nullptr, nullptr, (uint32_t)n, grid, dst);
-    else if (deep_) hipLaunchKernelGGL((k_any_public<R, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, (uint32_t)n, dst, deep_stack_.p, (uint32_t)cap_);
-    else hipLaunchKernelGGL((k_any_public<R, false>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, (uint32_t)n, dst, (uint32_t*)nullptr, 0u);
-    HIP_CHECK(hipGetLastError());
+    launch_any(grid, st_, /*ao=*/false, (uint32_t)n, dst);
     if (rays->mem != RRT_MEM_DEVICE) HIP_CHECK(hipMemcpyAsync(occluded, occ.p, n, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
   }
@@ -773,13 +785,25 @@ class Handle : public HandleBase {
     for (uint32_t k = 0; k < passes_n_; k++) HIP_CHECK(hipMemsetAsync(pool_.pass_L + (size_t)k * pool_.pass_stride, 0, nslots * sizeof(typename Vec4T<R>::type), st_));
     tock(fr, e);
   }
+  // One closest-hit round of an integrator over the active queue. first: the queue is the one the camera kernels of this pass filled (tile trees
+  // where the pass has them; the first hits that rrt_render_frame_aov keeps)
+  void closest_step(const PassDesc& pd, uint32_t aov_ns, uint32_t grid, bool first, FrameRec& fr) {
+    hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
+    const size_t e = tick(fr, 1);
+    launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, first);
+    tock(fr, e); fr.n_closest_launch++;
+    if (first && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr.n_tile_launch++;
+    if (first && aov_ns > 0) launch_aov_shade_frame(pd, aov_ns, grid);
+  }
+  // the shadow rays of the queue that shading has just filled, on `stream`
+  void shadow_step(uint32_t grid, hipStream_t stream, FrameRec& fr) {
+    hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, stream, pool_.shadow_count, totals_.p);
+    const size_t e = tick(fr, 2, stream);
+    launch_any(grid, stream);
+    tock(fr, e, stream); fr.n_any_launch++; if (use_shadow_lists()) fr.n_list_launch++;
+  }
   // second part: the integrator's launches over the queue the first part left, until every slot's L is final. aov_ns: see run_pass
-  void pass_integrate(const PassDesc& pd, uint32_t aov_ns, FrameRec& fr_ref) {
-    FrameRec* const fr = &fr_ref;
-    auto tick = [&](int cat, hipStream_t stream = nullptr) { return this->tick(fr_ref, cat, stream); };
-    auto tock = [&](size_t id, hipStream_t stream = nullptr) { this->tock(fr_ref, id, stream); };
-    uint64_t& n_closest_launch = fr->n_closest_launch;
-    uint64_t& n_any_launch = fr->n_any_launch;
+  void pass_integrate(const PassDesc& pd, uint32_t aov_ns, FrameRec& fr) {
     const int integ = desc_.integrator.type;
     const int max_depth = desc_.integrator.max_depth;
     const size_t nslots = (size_t)pd.npix * pd.ns;
@@ -796,38 +820,27 @@ class Handle : public HandleBase {
         if (passes_n_ > 0) pool_.smask = pass_smask_[k].p;
       };
       for (int b = 0; b < max_depth; b++) {
-        hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
-        e = tick(1);
-        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, b == 0);
-        tock(e); n_closest_launch++;
-        if (b == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
-        if (b == 0 && aov_ns > 0) launch_aov_shade_frame(pd, aov_ns, grid);
+        closest_step(pd, aov_ns, grid, b == 0, fr);
         if (overlap) {
           use_shadow_queue(b & 1);
           if (b > 1) HIP_CHECK(hipStreamWaitEvent(st_, ev_shadow_[b & 1], 0));   // shading refills the queue the shadow launch of bounce b - 2 read
         }
         scene_.use_shadow_tabs = use_shadow_lists() ? 1u : 0u;
         scene_.horizon = (horizon_on_ && horizon_.n) ? horizon_.p : nullptr; scene_.hz_tau = horizon_tau_.p; scene_.hz_axis = hz_axis_;   // (counting frames too: the cull is geometry, not a kernel's arithmetic - their node counters then hold the rays that are traced)
-        e = tick(3);
+        e = tick(fr, 3);
         if (passes_n_ > 0) launch_shade_path<true>(nslots, sgrid); else launch_shade_path<false>(nslots, sgrid);
-        tock(e);
+        tock(fr, e);
         if (scene_.horizon) hipLaunchKernelGGL(k_accumulate_sky, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
         if (overlap) {
           HIP_CHECK(hipEventRecord(ev_shade_, st_));
           HIP_CHECK(hipStreamWaitEvent(st2_, ev_shade_, 0));
-          hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st2_, pool_.shadow_count, totals_.p);
-          e = tick(2, st2_);
-          launch_shadow(grid, st2_);
-          tock(e, st2_); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
+          shadow_step(grid, st2_, fr);
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st2_, counters_.p, 6 + (b & 1));   // this shadow queue + the any-hit work counter
           HIP_CHECK(hipEventRecord(ev_shadow_[b & 1], st2_));
           swap_queues();
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 5);    // active <- next, closest work counter
         } else {
-          hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st_, pool_.shadow_count, totals_.p);
-          e = tick(2);
-          launch_shadow(grid);
-          tock(e); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
+          shadow_step(grid, st_, fr);
           swap_queues();
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);
         }
@@ -838,7 +851,7 @@ class Handle : public HandleBase {
       }
     } else if (integ == RRT_INT_DIRECT || integ == RRT_INT_DEBUG) {
       if (has_transmissive_ || tex_depth_ > 0) {   // binary recursion with depth-first sampler dimensions / inherited ray differentials: one thread per camera sample
-        size_t e2 = tick(3);
+        e = tick(fr, 3);
         // frames below level kTreeMax of the per-sample recursion live in a strided global array, sized for this pass
         TreeFrame<R>* deep = nullptr;
         if (max_depth > kTreeMax) {
@@ -846,36 +859,27 @@ class Handle : public HandleBase {
           if (tree_deep_.n < need) { HIP_CHECK(hipStreamSynchronize(st_)); tree_deep_.alloc(need); }
           deep = tree_deep_.p;
         }
-        if (tex_depth_ > 0) hipLaunchKernelGGL((k_direct_tree<R, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots);
-        else hipLaunchKernelGGL((k_direct_tree<R, false>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots);
-        tock(e2);
+        with_flag(tex_depth_ > 0, [&](auto TEX) { hipLaunchKernelGGL((k_direct_tree<R, TEX()>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, totals_.p, deep, (uint32_t)nslots); });
+        tock(fr, e);
       } else {
       const bool all = integ == RRT_INT_DEBUG || desc_.integrator.light_strategy == RRT_STRATEGY_ALL;
       // level k handles reference depth k+1; specular recursion while depth + 1 < max_depth
       for (int level = 0; level < std::max(1, max_depth - 1); level++) {
-        hipLaunchKernelGGL(k_accumulate_counts, dim3(1), dim3(1), 0, st_, counters_.p, totals_.p);
-        e = tick(1);
-        launch_closest(nullptr, &counters_.p[C_ACTIVE], 0, count_traversal_, nullptr, nullptr, count_traversal_ ? totals_.p : nullptr, grid, level == 0);
-        tock(e); n_closest_launch++;
-        if (level == 0 && tt_pass_ok_ && !count_traversal_ && use_persistent()) fr->n_tile_launch++;
-        if (level == 0 && aov_ns > 0) launch_aov_shade_frame(pd, aov_ns, grid);
+        closest_step(pd, aov_ns, grid, level == 0, fr);
         if (desc_.n_lights > 0) {
           const int nl = all ? (int)desc_.n_lights : 1;
           for (int j = 0; j < nl; j++) {
             hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);
             scene_.use_shadow_tabs = use_shadow_lists() ? 1u : 0u;
-            e = tick(3);
+            e = tick(fr, 3);
             hipLaunchKernelGGL((k_shade_nee<R>), dim3(sgrid), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_, all ? j : -1, j == 0 ? 1 : 0);
-            tock(e);
-            hipLaunchKernelGGL(k_accumulate_shadow, dim3(1), dim3(1), 0, st_, pool_.shadow_count, totals_.p);
-            e = tick(2);
-            launch_shadow(grid);
-            tock(e); n_any_launch++; if (use_shadow_lists()) fr->n_list_launch++;
+            tock(fr, e);
+            shadow_step(grid, st_, fr);
           }
         }
-        e = tick(3);
+        e = tick(fr, 3);
         hipLaunchKernelGGL((k_shade_specular<R>), dim3(sgrid), dim3(ShadeBlock<R>::n), 0, st_, scene_, pool_, (desc_.n_lights == 0 && integ == RRT_INT_DEBUG) ? 1 : 0);
-        tock(e);
+        tock(fr, e);
         swap_queues();
         hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);
       }
@@ -945,8 +949,7 @@ class Handle : public HandleBase {
     aov_serial_++;
     const uint32_t slot_end = aov_ns * pd.npix;
     const dim3 sg(std::min(grid, 16384u));
-    if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade_frame<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, aov_serial_, slot_end);
-    else hipLaunchKernelGGL((k_aov_shade_frame<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, aov_serial_, slot_end);
+    with_flag(tex_depth_ > 0, [&](auto TEX) { hipLaunchKernelGGL((k_aov_shade_frame<R, TEX()>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, aov_serial_, slot_end); });
   }
   // second half, beside the moments film kernel: the pass's PassDesc with ns cut to the feature buffers' samples, gathered into the internal planes
   void launch_aov_gather_frame(PassDesc pd, uint32_t aov_ns, const FilmWindow& w) {
@@ -1166,13 +1169,11 @@ class Handle : public HandleBase {
       [&](const PassDesc&, uint32_t grid) {
         const dim3 sg(std::min(grid, 16384u));
         // level 0's records are k_aov_shade's own (see k_aov_follow)
-        if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_shade<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
-        else hipLaunchKernelGGL((k_aov_shade<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p);
+        with_flag(tex_depth_ > 0, [&](auto TEX) { hipLaunchKernelGGL((k_aov_shade<R, TEX()>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p); });
         for (uint32_t k = 0; k <= max_follow; k++) {
           const int level0 = k == 0 ? 1 : 0, may_follow = k < max_follow ? 1 : 0;
           if (level0 && !may_follow) break;   // max_follow = 0: the first hits are the planes
-          if (tex_depth_ > 0) hipLaunchKernelGGL((k_aov_follow<R, true>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
-          else hipLaunchKernelGGL((k_aov_follow<R, false>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow);
+          with_flag(tex_depth_ > 0, [&](auto TEX) { hipLaunchKernelGGL((k_aov_follow<R, TEX()>), sg, dim3(kBlock), 0, st_, scene_, pool_, aov_rec_a_.p, aov_rec_b_.p, level0, may_follow); });
           if (!may_follow) break;
           swap_queues(); guard.swapped = !guard.swapped;
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 0);   // active <- next
@@ -1193,14 +1194,6 @@ class Handle : public HandleBase {
     const bool ao = desc_.integrator.type == RRT_INT_AO;
     p->n_samples = ao ? desc_.integrator.n_samples : 64;
     p->cos_sample = ao ? (desc_.integrator.cos_sample ? 1 : 0) : 1;
-  }
-  void launch_ao_any(uint32_t grid) {
-    if (use_persistent()) { launch_persistent(true, nullptr, pool_.shadow_count, 0, grid, nullptr, st_, false, /*ao=*/true); return; }
-    uint32_t* ds = deep_ ? deep_stack_.p : nullptr;
-    const uint32_t stride = deep_ ? (uint32_t)cap_ : 0u;
-    if (deep_) hipLaunchKernelGGL((k_shadow<R, true, false, false, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, (unsigned long long*)nullptr);
-    else hipLaunchKernelGGL((k_shadow<R, false, false, false, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, (unsigned long long*)nullptr);
-    HIP_CHECK(hipGetLastError());
   }
   void render_ao(const int32_t rect[4], int rank, int world, uint64_t max_samples, const rrt_ao_params* params, const rrt_ao* out) override {
     using V4 = typename Vec4T<R>::type;
@@ -1243,7 +1236,7 @@ class Handle : public HandleBase {
         for (uint32_t i = 0; i < n_draws; i++) {
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);   // the shadow queue and the work cursors start at 0
           hipLaunchKernelGGL((k_ao_gen<R>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, i, n_draws, cos_sample);
-          launch_ao_any(grid);
+          launch_any(grid, st_, /*ao=*/true);
         }
       },
       [&](const PassDesc& pd) { launch_gather(AoAcc<R>{ao_planes_.p, ao_acc_.p}, pd, g.win); });
@@ -1472,6 +1465,7 @@ class Handle : public HandleBase {
   bool deep_ = false, count_traversal_ = false, persistent_ = true;
   bool pairs_ok_ = false;
   bool mixed_ = false;   // the tree has kSpecialLeaf leaves (spheres, kept instances): the MIXED instantiations of the pair-node kernels
+  int n_cus_ = 0;           // compute units of dev_ (resident_grid)
   uint32_t trav_grid_ = 0, pt_grid_ = 0, pt_grid_quad_ = 0;
   int rg_spb_ = 8;          // option "rg_spb": samples per workgroup of the dense camera kernel (the workgroup's 512 threads = 512 / spb pixels x spb samples)
   bool tile_order_ = true;  // option "tile_order": pixels of a pass enumerated tile by tile (PassDesc::tiled)
@@ -1841,18 +1835,15 @@ class Handle : public HandleBase {
   void launch_closest(const uint32_t* queue, const uint32_t* count, uint32_t n_fixed, bool counting, uint32_t* cn, uint32_t* cp,
                       unsigned long long* totals, uint32_t grid_override = 0, bool camera_rays = false) {
     const uint32_t grid = grid_override ? grid_override : (uint32_t)((n_fixed + kBlock - 1) / kBlock);
-    if (!counting && use_persistent()) { launch_persistent(false, queue, count, n_fixed, grid, nullptr, nullptr, camera_rays && tt_pass_ok_ && count != nullptr); return; }
-    uint32_t* ds = deep_ ? deep_stack_.p : nullptr;
-    const uint32_t stride = deep_ ? (uint32_t)cap_ : 0u;
-    if (deep_) {
-      if (counting) hipLaunchKernelGGL((k_closest<R, true, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, queue, count, n_fixed, ds, stride, cn, cp, totals);
-      else hipLaunchKernelGGL((k_closest<R, true, false>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, queue, count, n_fixed, ds, stride, cn, cp, totals);
-    } else {
-      if (counting) hipLaunchKernelGGL((k_closest<R, false, true>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, queue, count, n_fixed, ds, stride, cn, cp, totals);
-      else hipLaunchKernelGGL((k_closest<R, false, false>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, queue, count, n_fixed, ds, stride, cn, cp, totals);
-    }
+    if (!counting && use_persistent()) { launch_persistent(TravJob{false, AnySink::film, queue, count, n_fixed, nullptr, st_}, grid, camera_rays && tt_pass_ok_ && count != nullptr); return; }
+    with_flag(deep_, [&](auto DEEP) { with_flag(counting, [&](auto COUNT) {
+      hipLaunchKernelGGL((k_closest<R, DEEP(), COUNT()>), dim3(grid), dim3(kBlock), 0, st_, scene_, pool_, queue, count, n_fixed, deep_stack(), deep_stride(), cn, cp, totals);
+    }); });
     HIP_CHECK(hipGetLastError());
   }
+  // the per-slot stacks of the generic kernels' DEEP instantiations (trees deeper than 64 levels)
+  uint32_t* deep_stack() const { return deep_ ? deep_stack_.p : nullptr; }
+  uint32_t deep_stride() const { return deep_ ? (uint32_t)cap_ : 0u; }
   // camera ray generation: the dense lean-arithmetic kernels in fp32 (dtraverse_f32.hpp), the generic two-stage kernels (main trace, auxiliary traces; the
   // reference's operation order) in f64 and for what the dense ones do not cover
   // for_render: the queue feeds the integrator (camera rays that miss the root box may be answered here); otherwise every survivor's ray is wanted (rrt_camera_samples)
@@ -1870,10 +1861,7 @@ class Handle : public HandleBase {
       }
     }
     if constexpr (std::is_same<R, float>::value) {
-      // the dense fp32 kernels cover Halton scenes with lenses of up to 32 interfaces on films below 65 536 px per side; everything else
-      // (StratifiedSampler, longer lens tables) takes the generic kernels below, which have no such limits
-      const bool pt_ok = scene_.n_lens <= 32 && scene_.sampler_type == RRT_SAMPLER_HALTON && scene_.xres < 65536 && scene_.yres < 65536;
-      if (raygen_lean_ && pt_ok) {
+      if (raygen_lean_ && dense_raygen_ok()) {   // everything else takes the generic kernels below, which have no such limits
         const uint32_t total = pd.npix * pd.ns;
         if (pix_off_.n < 2 * (size_t)pd.npix) { HIP_CHECK(hipStreamSynchronize(st_)); pix_off_.alloc(2 * (size_t)pd.npix); }
         pool_.pix_off = pix_off_.p;
@@ -1920,34 +1908,98 @@ class Handle : public HandleBase {
     hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 4);   // q_next was only a staging queue
     HIP_CHECK(hipGetLastError());
   }
+  // the dense fp32 camera kernels cover Halton scenes with lenses of up to 32 interfaces on films below 65 536 px per side (StratifiedSampler and
+  // longer lens tables are the generic kernels'); the tile-tree census asks the same question, so that it and the frame take the same camera kernels
+  bool dense_raygen_ok() const { return scene_.n_lens <= 32 && scene_.sampler_type == RRT_SAMPLER_HALTON && scene_.xres < 65536 && scene_.yres < 65536; }
   // fp32 production traversal (dtraverse_f32.hpp): 64 B pair nodes, LDS stack with global overflow
   bool use_persistent() const { return std::is_same<R, float>::value && persistent_ && pairs_ok_; }
-  void launch_persistent(bool any, const uint32_t* queue, const uint32_t* count, uint32_t n_fixed, uint32_t grid, uint8_t* occluded, hipStream_t stream = nullptr, bool tiles = false, bool ao = false) {
-    if constexpr (std::is_same<R, float>::value) {
-      if (!stream) stream = st_;
-      const uint32_t grid_in = grid;
-      if (trav_grid_ == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_));
-        if (mixed_) HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_trace_pairs_f32<false, true>), kTravBlock, 0));
-        else HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_trace_pairs_f32<false, false>), kTravBlock, 0));
-        trav_grid_ = (uint32_t)(std::max(1, per_cu) * std::max(1, cus));
-        if (scene_.stack_depth > (uint32_t)kStackLds) {   // any-hit launches have their own columns: they may run beside a closest-hit launch
-          overflow_.alloc((size_t)(scene_.stack_depth - kStackLds) * (size_t)trav_grid_ * kTravBlock * 2);
-          overflow_any_.alloc((size_t)(scene_.stack_depth - kStackLds) * (size_t)trav_grid_ * kTravBlock * 2);
-        }
+  // one traversal launch over a queue: closest-hit, or any-hit with its sink. occluded: rrt_trace_any's answers, else NULL
+  struct TravJob { bool any; AnySink sink; const uint32_t *queue, *count; uint32_t n_fixed; uint8_t* occluded; hipStream_t stream; };
+  // the workgroups of `kernel` that the chip holds at once: the grid of a persistent launch
+  template <class K>
+  uint32_t resident_grid(K kernel, int block, int* per_cu_out = nullptr) {
+    if (n_cus_ == 0) HIP_CHECK(hipDeviceGetAttribute(&n_cus_, hipDeviceAttributeMultiprocessorCount, dev_));
+    int per_cu = 0;
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0));
+    if (per_cu_out) *per_cu_out = per_cu;
+    return (uint32_t)(std::max(1, per_cu) * std::max(1, n_cus_));
+  }
+  // Run once per kernel, at the first launch that needs it: the resident grids of the three traversal kernels and the overflow stacks sized by them
+  void size_traversal(bool tiles) {
+    if (trav_grid_ == 0) {
+      with_flag(mixed_, [&](auto MIXED) { trav_grid_ = resident_grid(k_trace_pairs_f32<false, MIXED()>, kTravBlock); });
+      if (scene_.stack_depth > (uint32_t)kStackLds) {   // any-hit launches have their own columns: they may run beside a closest-hit launch
+        overflow_.alloc((size_t)(scene_.stack_depth - kStackLds) * (size_t)trav_grid_ * kTravBlock * 2);
+        overflow_any_.alloc((size_t)(scene_.stack_depth - kStackLds) * (size_t)trav_grid_ * kTravBlock * 2);
       }
-      trav_.overflow = any ? overflow_any_.p : overflow_.p;
-      trav_.overflow_stride = trav_grid_ * kTravBlock;   // one column per resident thread of the persistent grid
-      // persistent workgroups: grid-stride over the queue (slots / kBlock thread blocks were requested by the caller)
-      const uint32_t need = (uint32_t)(((size_t)grid * kBlock + kTravBlock - 1) / kTravBlock);
-      grid = std::max(1u, std::min(need, trav_grid_));
+    }
+    if (trav_mode_ == 1) return;   // grid-stride only
+    if (tiles && tt_grid_ == 0) {
+      int per_cu = 0;
+      tt_grid_ = resident_grid(k_trace_tiles_f32<false>, kTtBlock, &per_cu);
+      if (scene_.stack_depth > (uint32_t)kTtStack) tt_overflow_.alloc((size_t)(scene_.stack_depth - kTtStack) * (size_t)tt_grid_ * kTtBlock * 2);
+      if (getenv("RRT_DEBUG")) fprintf(stderr, "[rrt] tile trees: %d workgroup(s) of %d threads per CU, grid %u\n", per_cu, kTtBlock, tt_grid_);
+    }
+    if (!tiles && pt_grid_ == 0) {
+      int per_cu = 0, per_cu_q = 0;
+      with_flag(mixed_, [&](auto MIXED) { pt_grid_ = resident_grid(k_trace_pt_f32<false, MIXED()>, kPtBlock, &per_cu); });
+      if (quads_.n) {   // the two-levels-per-fetch kernel has its own register count, and pushes up to three entries per two levels
+        pt_grid_quad_ = resident_grid(k_trace_pt_f32<false, false, true>, kPtBlock, &per_cu_q);
+        if (getenv("RRT_DEBUG")) fprintf(stderr, "[rrt] quad nodes: %zu nodes, %d workgroup(s) per CU (pair-node kernel: %d)\n", quads_.n, per_cu_q, per_cu);
+      }
+      const uint32_t quad_depth = quads_.n ? 3u * ((scene_.stack_depth + 1u) / 2u) + 3u : 0u;   // deepest stack of a quad walk
+      const uint32_t depth_cl = std::max(scene_.stack_depth, quad_depth);
+      if (pairs_ok_ && depth_cl > (uint32_t)kPtStack) pt_overflow_.alloc((size_t)(depth_cl - kPtStack) * (size_t)std::max(pt_grid_, pt_grid_quad_) * kPtBlock * 2);
+      if (pairs_ok_ && scene_.stack_depth > (uint32_t)kPtStackAny) pt_overflow_any_.alloc((size_t)(scene_.stack_depth - kPtStackAny) * (size_t)pt_grid_ * kPtBlock * 2);
+    }
+  }
+  // the grid-stride kernel: persistent workgroups over the queue, one overflow column per resident thread of the persistent grid
+  void launch_pairs(const TravJob& j, uint32_t grid, uint32_t hi_gs) {
+    TravScene t = trav_;
+    t.overflow = j.any ? overflow_any_.p : overflow_.p;
+    t.overflow_stride = trav_grid_ * kTravBlock;
+    auto go = [&](auto ANY, auto MIXED, auto PASSES, auto AO) {
+      hipLaunchKernelGGL((k_trace_pairs_f32<ANY(), MIXED(), PASSES(), AO()>), dim3(grid), dim3(kTravBlock), 0, j.stream, t, pool_, j.queue, j.count, j.n_fixed, j.occluded, 0u, hi_gs);
+    };
+    with_flag(mixed_, [&](auto MIXED) {
+      if (j.any) with_sink(j.sink, [&](auto PASSES, auto AO) { go(kYes, MIXED, PASSES, AO); });
+      else go(kNo, MIXED, kNo, kNo);
+    });
+  }
+  // the persistent-thread kernel; closest-hit launches over all-triangle trees with quad nodes (option quad_nodes) take its QUAD form, which has its own grid
+  void launch_pt(const TravJob& j, uint32_t grid, uint32_t lo_pt) {
+    const bool quad = !j.any && !mixed_ && quad_on_ && quads_.n && pt_grid_quad_;
+    TravScene t = trav_;
+    t.overflow = j.any ? pt_overflow_any_.p : pt_overflow_.p;
+    t.overflow_stride = (j.any ? pt_grid_ : std::max(pt_grid_, pt_grid_quad_)) * kPtBlock;
+    const uint32_t g = std::max(1u, std::min(grid, quad ? pt_grid_quad_ : pt_grid_));
+    uint32_t* work = &counters_.p[j.any ? C_WORK8_SHADOW : C_WORK8_CLOSEST];   // 8 cursors, one 128-B line each
+    auto go = [&](auto ANY, auto MIXED, auto QUAD, auto PASSES, auto AO) {
+      hipLaunchKernelGGL((k_trace_pt_f32<ANY(), MIXED(), QUAD(), PASSES(), AO()>), dim3(g), dim3(kPtBlock), 0, j.stream, t, pool_, j.queue, j.count, j.n_fixed, work, j.occluded, lo_pt, 0xffffffffu);
+    };
+    if (quad) go(kNo, kNo, kYes, kNo, kNo);
+    else with_flag(mixed_, [&](auto MIXED) {
+      if (j.any) with_sink(j.sink, [&](auto PASSES, auto AO) { go(kYes, MIXED, kNo, PASSES, AO); });
+      else go(kNo, MIXED, kNo, kNo, kNo);
+    });
+  }
+  // camera rays of a pass with chunk records: k_trace_tiles_f32 in the persistent-thread kernel's place
+  void launch_tiles(const TravJob& j, uint32_t lo_pt) {
+    TravScene t = trav_;
+    t.pairs = tt_pairs_.p; t.root_id = 0u;   // slot 0 of every local copy is the root
+    t.overflow = tt_overflow_.p;
+    t.overflow_stride = tt_grid_ * kTtBlock;
+    hipLaunchKernelGGL((k_trace_tiles_f32<false>), dim3(tt_grid_), dim3(kTtBlock), 0, j.stream, t, pool_, j.count, &counters_.p[C_WORK8_CLOSEST], tt_pass_, lo_pt, 0xffffffffu);
+  }
+  // grid: slots / kBlock thread blocks, as the caller of a generic kernel would ask for. tiles: the queue is a camera queue with chunk records
+  void launch_persistent(const TravJob& j, uint32_t grid, bool tiles = false) {
+    if constexpr (std::is_same<R, float>::value) {
+      size_traversal(tiles);
       // Two kernels, two queue-size regimes (decided on the device from the queue counter): large queues go to the
       // persistent-thread kernel (lane refill keeps the VALUs busy), small ones to the grid-stride kernel (its fixed
       // cost — the latency chain of the longest ray — is lower). trav_mode_: 1 = grid-stride only, 2 = persistent
       // only, 3 = both by regime.
-      const uint32_t split = any ? pt_split_any_ : pt_split_closest_;
-      const bool ps = passes_n_ > 0 && occluded == nullptr;   // the shadow launch of a passes frame: add_pending<float, true> (rrt_trace_any hands in `occluded`)
+      const uint32_t split = j.any ? pt_split_any_ : pt_split_closest_;
       const uint32_t lo_pt = trav_mode_ == 2 ? 0u : (trav_mode_ == 1 ? 0xffffffffu : split);
       const uint32_t hi_gs = trav_mode_ == 1 ? 0xffffffffu : (trav_mode_ == 2 ? 0u : split);
       // The grid-stride kernel goes FIRST. Both kernels are launched for every queue and the one whose regime it is not returns at once - but
@@ -1956,72 +2008,11 @@ class Handle : public HandleBase {
       // 1 waiting 3.5 ms for the any-hit launch of bounce 0 to drain, on the critical path of a frame rendered alone. In front, it is
       // dispatched while the chip is still filling. Its grid is no larger than its regime needs.
       if (trav_mode_ != 2) {
-        if (trav_mode_ == 3) grid = std::max(1u, std::min(grid, (split + kTravBlock - 1) / kTravBlock));
-        if (mixed_) {
-          if (any && ao) hipLaunchKernelGGL((k_trace_pairs_f32<true, true, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-          else if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-          else if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-          else hipLaunchKernelGGL((k_trace_pairs_f32<false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-        } else {
-          if (any && ao) hipLaunchKernelGGL((k_trace_pairs_f32<true, false, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-          else if (any && ps) hipLaunchKernelGGL((k_trace_pairs_f32<true, false, true>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-          else if (any) hipLaunchKernelGGL((k_trace_pairs_f32<true, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-          else hipLaunchKernelGGL((k_trace_pairs_f32<false, false>), dim3(grid), dim3(kTravBlock), 0, stream, trav_, pool_, queue, count, n_fixed, occluded, 0u, hi_gs);
-        }
+        uint32_t g = std::max(1u, std::min((uint32_t)(((size_t)grid * kBlock + kTravBlock - 1) / kTravBlock), trav_grid_));
+        if (trav_mode_ == 3) g = std::max(1u, std::min(g, (split + kTravBlock - 1) / kTravBlock));
+        launch_pairs(j, g, hi_gs);
       }
-      if (trav_mode_ != 1 && tiles) {   // camera rays of a pass with chunk records: k_trace_tiles_f32 in the persistent kernel's place
-        if (tt_grid_ == 0) {
-          int per_cu = 0, cus = 0;
-          HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_));
-          HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_trace_tiles_f32<false>), kTtBlock, 0));
-          tt_grid_ = (uint32_t)(std::max(1, per_cu) * std::max(1, cus));
-          if (scene_.stack_depth > (uint32_t)kTtStack) tt_overflow_.alloc((size_t)(scene_.stack_depth - kTtStack) * (size_t)tt_grid_ * kTtBlock * 2);
-          if (getenv("RRT_DEBUG")) fprintf(stderr, "[rrt] tile trees: %d workgroup(s) of %d threads per CU, grid %u\n", per_cu, kTtBlock, tt_grid_);
-        }
-        TravScene t2 = trav_;
-        t2.pairs = tt_pairs_.p; t2.root_id = 0u;   // slot 0 of every local copy is the root
-        t2.overflow = tt_overflow_.p;
-        t2.overflow_stride = tt_grid_ * kTtBlock;
-        uint32_t* work = &counters_.p[C_WORK8_CLOSEST];
-        hipLaunchKernelGGL((k_trace_tiles_f32<false>), dim3(tt_grid_), dim3(kTtBlock), 0, stream, t2, pool_, count, work, tt_pass_, lo_pt, 0xffffffffu);
-      } else if (trav_mode_ != 1) {
-        if (pt_grid_ == 0) {
-          int per_cu = 0, cus = 0;
-          HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_));
-          if (mixed_) HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_trace_pt_f32<false, true>), kPtBlock, 0));
-          else HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_trace_pt_f32<false, false>), kPtBlock, 0));
-          pt_grid_ = (uint32_t)(std::max(1, per_cu) * std::max(1, cus));
-          if (quads_.n) {   // the two-levels-per-fetch kernel has its own register count, and pushes up to three entries per two levels
-            int per_cu_q = 0;
-            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_q, (k_trace_pt_f32<false, false, true>), kPtBlock, 0));
-            pt_grid_quad_ = (uint32_t)(std::max(1, per_cu_q) * std::max(1, cus));
-            if (getenv("RRT_DEBUG")) fprintf(stderr, "[rrt] quad nodes: %zu nodes, %d workgroup(s) per CU (pair-node kernel: %d)\n", quads_.n, per_cu_q, per_cu);
-          }
-          const uint32_t quad_depth = quads_.n ? 3u * ((scene_.stack_depth + 1u) / 2u) + 3u : 0u;   // deepest stack of a quad walk
-          const uint32_t depth_cl = std::max(scene_.stack_depth, quad_depth);
-          if (pairs_ok_ && depth_cl > (uint32_t)kPtStack) pt_overflow_.alloc((size_t)(depth_cl - kPtStack) * (size_t)std::max(pt_grid_, pt_grid_quad_) * kPtBlock * 2);
-          if (pairs_ok_ && scene_.stack_depth > (uint32_t)kPtStackAny) pt_overflow_any_.alloc((size_t)(scene_.stack_depth - kPtStackAny) * (size_t)pt_grid_ * kPtBlock * 2);
-        }
-        TravScene t2 = trav_;
-        t2.overflow = any ? pt_overflow_any_.p : pt_overflow_.p;
-        t2.overflow_stride = (any ? pt_grid_ : std::max(pt_grid_, pt_grid_quad_)) * kPtBlock;
-        const uint32_t g2 = std::max(1u, std::min(grid_in, pt_grid_));
-        uint32_t* work = &counters_.p[any ? C_WORK8_SHADOW : C_WORK8_CLOSEST];   // 8 cursors, one 128-B line each
-        if (!any && !mixed_ && quad_on_ && quads_.n && pt_grid_quad_) {
-          const uint32_t gq = std::max(1u, std::min(grid_in, pt_grid_quad_));
-          hipLaunchKernelGGL((k_trace_pt_f32<false, false, true>), dim3(gq), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-        } else if (mixed_) {
-          if (any && ao) hipLaunchKernelGGL((k_trace_pt_f32<true, true, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-          else if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, true, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-          else if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-          else hipLaunchKernelGGL((k_trace_pt_f32<false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-        } else {
-          if (any && ao) hipLaunchKernelGGL((k_trace_pt_f32<true, false, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-          else if (any && ps) hipLaunchKernelGGL((k_trace_pt_f32<true, false, false, true>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-          else if (any) hipLaunchKernelGGL((k_trace_pt_f32<true, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-          else hipLaunchKernelGGL((k_trace_pt_f32<false, false>), dim3(g2), dim3(kPtBlock), 0, stream, t2, pool_, queue, count, n_fixed, work, occluded, lo_pt, 0xffffffffu);
-        }
-      }
+      if (trav_mode_ != 1) { if (tiles) launch_tiles(j, lo_pt); else launch_pt(j, grid, lo_pt); }
       HIP_CHECK(hipGetLastError());
     }
   }
@@ -2041,8 +2032,7 @@ class Handle : public HandleBase {
         if (tris_.n) HIP_CHECK(hipMemcpy(tris_host_.data(), tris_.p, tris_.n * sizeof(Tri<float>), hipMemcpyDeviceToHost));
       }
       const size_t n_int = pairs_host_.size();
-      const bool pt_ok = scene_.n_lens <= 32 && scene_.sampler_type == RRT_SAMPLER_HALTON && scene_.xres < 65536 && scene_.yres < 65536;
-      if (!use_persistent() || mixed_ || !pt_ok || !raygen_lean_ || n_int <= kTtNodes || trav_.root_id != 0u || (uint64_t)n_int * 64u + kTtLocalBytes >= kIdle) return;
+      if (!use_persistent() || mixed_ || !dense_raygen_ok() || !raygen_lean_ || n_int <= kTtNodes || trav_.root_id != 0u || (uint64_t)n_int * 64u + kTtLocalBytes >= kIdle) return;
       const uint64_t s_total = desc_.sampler.samples_per_pixel > 1 ? desc_.sampler.samples_per_pixel - 1 : 0;
       if (s_total == 0 || cap_ == 0) return;
       const auto t_begin = std::chrono::steady_clock::now();
@@ -2104,32 +2094,38 @@ class Handle : public HandleBase {
   }
   // (the shading kernels that feed the shadow queue - k_shade_path, k_shade_nee - store the light table with the ray's start triangle)
   bool use_shadow_lists() const { return std::is_same<R, float>::value && shadow_lists_ok_ && shadow_lists_on_ && !count_traversal_ && use_persistent(); }
-  void launch_shadow(uint32_t grid, hipStream_t stream = nullptr) {
-    if (!stream) stream = st_;
+  // The sink of an any-hit launch, decided here for every kernel family. Precedence: a rrt_render_ao round is AO whatever else is set; then the
+  // shadow launch of a passes frame adds to the pending planes (add_pending<R, true>) - not rrt_trace_any's launch, which hands in `occluded`
+  // and touches no radiance; everything else is the film's. A closest-hit launch has no sink.
+  AnySink any_sink(bool ao, const uint8_t* occluded) const { return ao ? AnySink::ao : (passes_n_ > 0 && !occluded) ? AnySink::passes : AnySink::film; }
+  // Every any-hit launch: the pool's shadow queue for an integrator or (ao) a rrt_render_ao round, or rrt_trace_any's n_fixed rays answered into
+  // `occluded`. Shadow candidate lists are per light: the integrators' launches only. A counting frame's shadow rays keep the generic kernels;
+  // AO rounds and rrt_trace_any count nothing.
+  void launch_any(uint32_t grid, hipStream_t stream, bool ao = false, uint32_t n_fixed = 0, uint8_t* occluded = nullptr) {
+    const AnySink sink = any_sink(ao, occluded);
+    const bool shadow = !ao && !occluded;
     if constexpr (std::is_same<R, float>::value) {
-      if (use_shadow_lists()) {   // (the shading kernel stored the light table with the ray's start triangle: scene_.use_shadow_tabs)
+      if (shadow && use_shadow_lists()) {   // (the shading kernel stored the light table with the ray's start triangle: scene_.use_shadow_tabs)
         const uint32_t g = std::max(1u, std::min((uint32_t)(((size_t)grid * kBlock + kSlBlock - 1) / kSlBlock), (uint32_t)sl_grid_cap_));
-        if (passes_n_ > 0) hipLaunchKernelGGL((k_shadow_lists_f32<true>), dim3(g), dim3(kSlBlock), 0, stream, trav_, sl_dev_, pool_, pool_.shadow_count);
-        else hipLaunchKernelGGL((k_shadow_lists_f32<false>), dim3(g), dim3(kSlBlock), 0, stream, trav_, sl_dev_, pool_, pool_.shadow_count);
+        with_flag(sink == AnySink::passes, [&](auto PASSES) {
+          hipLaunchKernelGGL((k_shadow_lists_f32<PASSES()>), dim3(g), dim3(kSlBlock), 0, stream, trav_, sl_dev_, pool_, pool_.shadow_count);
+        });
         HIP_CHECK(hipGetLastError());
         return;
       }
     }
-    if (!count_traversal_ && use_persistent()) { launch_persistent(true, nullptr, pool_.shadow_count, 0, grid, nullptr, stream); return; }
-    uint32_t* ds = deep_ ? deep_stack_.p : nullptr;
-    const uint32_t stride = deep_ ? (uint32_t)cap_ : 0u;
-    unsigned long long* tot = count_traversal_ ? totals_.p + 5 : nullptr;
-    if (deep_) {
-      if (count_traversal_ && passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, true, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-      else if (count_traversal_) hipLaunchKernelGGL((k_shadow<R, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-      else if (passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, true, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-      else hipLaunchKernelGGL((k_shadow<R, true, false>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-    } else {
-      if (count_traversal_ && passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, false, true, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-      else if (count_traversal_) hipLaunchKernelGGL((k_shadow<R, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-      else if (passes_n_ > 0) hipLaunchKernelGGL((k_shadow<R, false, false, true>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-      else hipLaunchKernelGGL((k_shadow<R, false, false>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, pool_.shadow_count, ds, stride, tot);
-    }
+    const uint32_t* count = occluded ? nullptr : pool_.shadow_count;
+    if (use_persistent() && !(shadow && count_traversal_)) { launch_persistent(TravJob{true, sink, nullptr, count, n_fixed, occluded, stream}, grid); return; }
+    const bool counting = shadow && count_traversal_;
+    auto go = [&](auto DEEP, auto COUNT, auto PASSES, auto AO) {
+      hipLaunchKernelGGL((k_shadow<R, DEEP(), COUNT(), PASSES(), AO()>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, (const uint32_t*)nullptr, count, deep_stack(), deep_stride(),
+                         counting ? totals_.p + 5 : nullptr);
+    };
+    with_flag(deep_, [&](auto DEEP) {
+      if (occluded) hipLaunchKernelGGL((k_any_public<R, DEEP()>), dim3(grid), dim3(kBlock), 0, stream, scene_, pool_, n_fixed, occluded, deep_stack(), deep_stride());
+      else if (ao) go(DEEP, kNo, kNo, kYes);
+      else with_flag(counting, [&](auto COUNT) { with_flag(sink == AnySink::passes, [&](auto PASSES) { go(DEEP, COUNT, PASSES, kNo); }); });
+    });
     HIP_CHECK(hipGetLastError());
   }
 };

@@ -153,12 +153,13 @@ def _reference(name, n, cos, workdir):
     return _refs[key]
 
 
-def _device(name, n, cos, workdir, prec, options=(), max_paths="case"):
+def _device(name, n, cos, workdir, prec, options=(), max_paths="case", set_options=None):
     sc, c = _scene(name, workdir), CASES[name]
     r = Renderer(sc, 0, prec)
     if max_paths == "case": max_paths = c["max_paths"]
     if max_paths: r.set_option("max_paths", max_paths)
     for k in options: r.set_option(k, 0)
+    for k, v in (set_options or {}).items(): r.set_option(k, v)
     total = None
     for part in c["parts"]:
         p = r.render_ao(n_samples=n, cos_sample=cos, **_part_args(part))
@@ -289,9 +290,9 @@ def _fp32_stats(plane, got, ref):
     return float((d >= 1e-4).mean()), float(d.mean()), float(d.max())
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name,n,cos", RUNS, ids=_ids)
-def test_fp32_planes_close_to_reference(name, n, cos, workdir):
+def check_fp32_planes(name, n, cos, workdir, set_options=None):
+    """test_fp32_planes_close_to_reference's comparison (module docstring) of the fp32 pass rendered under `set_options` (option -> value; None: the
+    default handle). The baseline is always the default handle's trace_any."""
     ref = _reference(name, n, cos, workdir)
     sc = _scene(name, workdir)
     spp = int(sc.desc.sampler.samples_per_pixel) - 1
@@ -311,7 +312,7 @@ def test_fp32_planes_close_to_reference(name, n, cos, workdir):
         p = AO.planes_of(sc, s, a, b)
         base = p if base is None else {k: base[k] + p[k] for k in ("ao", "bent")}
     r.close()
-    got = _device(name, n, cos, workdir, RRT_F32)
+    got = _device(name, n, cos, workdir, RRT_F32, set_options=set_options)
     live, live_ref = float(got["ao"][..., 3].astype(np.float64).sum()), float(ref["ao"][..., 3].sum())
     print(f"{name} N {n}: fp32 live weight {live} against {live_ref}")
     failures = []
@@ -329,6 +330,12 @@ def test_fp32_planes_close_to_reference(name, n, cos, workdir):
         if not g_max <= max(1.5 * b_max, 3e-2 * 256 / spp): failures.append((plane, "max", g_max, b_max))
     assert abs(live - live_ref) <= 2e-5 * live_ref, (live, live_ref)
     assert not failures, failures
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,n,cos", RUNS, ids=_ids)
+def test_fp32_planes_close_to_reference(name, n, cos, workdir):
+    check_fp32_planes(name, n, cos, workdir)
 
 
 def _sum_parts(r, parts, **kw):
