@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -100,6 +101,9 @@ struct FrameRec {
   uint64_t n_closest_launch = 0, n_any_launch = 0, n_tile_launch = 0, n_list_launch = 0, camera_samples = 0;
   bool timing = false;
   hipEvent_t make() { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreate(&e)); all.push_back(e); return e; }
+  // the frame's own two events, where its timing is wanted: made and the first recorded before the first pass, the second recorded after the last
+  void begin(bool want_timing, hipStream_t st) { timing = want_timing; if (timing) { ev_begin = make(); ev_end = make(); HIP_CHECK(hipEventRecord(ev_begin, st)); } }
+  void end(hipStream_t st) { if (timing) HIP_CHECK(hipEventRecord(ev_end, st)); }
   ~FrameRec() { for (hipEvent_t e : all) (void)hipEventDestroy(e); }   // on every way out (a panic / HIP error thrown mid-frame included)
   FrameRec() = default;
   FrameRec(const FrameRec&) = delete;
@@ -123,7 +127,7 @@ template <class F> void with_sink(AnySink s, F&& f) {
 
 template <typename R>
 class Handle : public HandleBase {
-  // ---- what the entry points below share: the argument checks, the pixel and sample counts of a call, the film window of a wide filter ---------
+  // ---- what the entry points below share: the call preamble, the pixels and samples of a call (CallGeom), the film window of a wide filter ------
   // The film kernels in their box form (k_film_box, k_gather_box ...) are the closed form for the default box filter (radius exactly
   // 0.5: every sample lands in its own pixel with weight 1); a smaller radius leaves samples near the pixel borders in no pixel at all, a larger
   // one splats: both take the general (wide) kernels
@@ -162,12 +166,32 @@ class Handle : public HandleBase {
     const int ex1 = std::min(f.xres, rect[2] + reach_x), ey1 = std::min(f.yres, rect[3] + reach_y);
     return {ex0, ey0, ex1 - ex0, ey1 - ey0, reach_x, reach_y, f.yres};
   }
-  // what the first-hit calls work out of their arguments once the checks have passed: this rank's bands of the rect, the samples of a pixel, the window
-  struct CallGeom { uint32_t band_h; size_t rw, rh, rpix; uint64_t s_total; FilmWindow win; };
-  CallGeom call_geom(const int32_t rect[4], int rank, int world, uint64_t max_samples) const {
-    const uint32_t band_h = world > 1 ? 16u : 1u << 30;
+  // The call preamble, first half: what a call refuses of its arguments before any device work, in the one order every call has it - a frame in
+  // flight (idle), a struct of the other precision (prec: the "plane", "table" or "ray" struct the caller filled), rank / world, the rect. A
+  // call passes what it checks; each message begins with the call's own name.
+  struct Prec { const char* what; int precision; };
+  struct Ranks { int rank, world; };
+  static constexpr bool kWhenIdle = true, kAnyTime = false;   // (not "kIdle": a member of that name would hide the traversal kernels' word in build_tile_trees)
+  void check_args(const std::string& who, bool idle, std::optional<Prec> prec = {}, std::optional<Ranks> ranks = {}, const int32_t* rect = nullptr) const {
+    if (idle && pending_) throw std::invalid_argument(who + ": a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
+    if (prec && prec->precision != precision()) throw std::invalid_argument(who + ": " + prec->what + " precision must match the handle");
+    if (ranks && (ranks->world < 1 || ranks->rank < 0 || ranks->rank >= ranks->world)) throw std::invalid_argument(who + ": bad rank/world");
+    if (rect) check_rect((who + ": rect outside the film").c_str(), rect);
+  }
+  // second half: the device, and what the kernels do not render (film: the call adds to film pixels, which a crop window would cut)
+  void device_prologue(bool film = true) {
+    HIP_CHECK(hipSetDevice(dev_));
+    check_renderable();
+    if (film) check_no_crop();
+  }
+  // The pixels and samples of a call, worked out once when check_args has passed: the rect, this rank's rows of its interleaved band_h-row bands
+  // (rh: their number, so rpix counts this rank's pixels), the samples of a pixel, the film window. Every pass of the call is cut from it.
+  struct CallGeom { int32_t rect[4]; uint32_t band_h, n_ranks, rank; size_t rw, rh, rpix; uint64_t s_total; FilmWindow win; };
+  static constexpr uint32_t kBandH = 16, kNoBands = 1u << 30;
+  static uint32_t bands_of(int world) { return world > 1 ? kBandH : kNoBands; }   // every call but rrt_render_bands, which has bands at world 1 too
+  CallGeom call_geom(const int32_t rect[4], uint32_t band_h, int rank, int world, uint64_t max_samples = 0) const {
     const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, (uint32_t)world, (uint32_t)rank);
-    return {band_h, rw, rh, rw * rh, frame_samples(max_samples), film_window(rect)};
+    return {{rect[0], rect[1], rect[2], rect[3]}, band_h, (uint32_t)world, (uint32_t)rank, rw, rh, rw * rh, frame_samples(max_samples), film_window(rect)};
   }
   // What launch_raygen sets for the pass it last ran for, put back when a first-hit call ends (a frame's tile-tree and film-record state is its
   // own), and the queue halves as the call found them (swapped: the follow levels have swapped them an odd number of times)
@@ -318,8 +342,7 @@ class Handle : public HandleBase {
   }
 
   void camera_samples(const int32_t rect[4], uint64_t s0, uint64_t s1, double* dims5, double* ray_od6, double* weight) override {
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
+    device_prologue(/*film=*/false);
     check_rect("camera_samples: rect outside the film", rect, /*allow_empty=*/true);
     if (s1 < s0 || s1 > desc_.sampler.samples_per_pixel) throw std::invalid_argument("camera_samples: sample range outside [0, samples_per_pixel]");
     const size_t npix = (size_t)(rect[2] - rect[0]) * (size_t)(rect[3] - rect[1]), ns = (size_t)(s1 - s0), n = npix * ns;
@@ -386,12 +409,6 @@ class Handle : public HandleBase {
     in.pixel = (const uint32_t*)words[0]; in.sample_num = (const uint32_t*)words[1];
     return in;
   }
-  // what both calls refuse before any device work
-  void check_ray_samples(const char* who, const rrt_ray_samples* rays) const {
-    const std::string w(who);
-    if (pending_) throw std::invalid_argument(w + ": a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (rays->precision != precision()) throw std::invalid_argument(w + ": ray precision must match the handle");
-  }
   void launch_ingest(const PassDesc& pd, RaySamples<R> in, int check_only) {
     // workgroup shape (RaySamples::pb_log2): the next power of two >= min(ns, 32) samples, the rest of the 256 threads pixels
     uint32_t sb = 1;
@@ -413,7 +430,7 @@ class Handle : public HandleBase {
   }
   void radiance(const rrt_ray_samples* rays, size_t n, void* rgb4) override {
     using V4 = typename Vec4T<R>::type;
-    check_ray_samples("rrt_radiance", rays);
+    check_args("rrt_radiance", kWhenIdle, Prec{"ray", rays->precision});
     const rrt_film& f = desc_.film;
     const uint64_t nsamp = desc_.sampler.samples_per_pixel;
     const bool host = rays->mem != RRT_MEM_DEVICE;
@@ -424,8 +441,7 @@ class Handle : public HandleBase {
         if (sn < 1 || sn >= nsamp) throw std::invalid_argument("rrt_radiance: sample_num outside 1 .. nsamp-1 (ray " + std::to_string(i) + ")");
       }
     }
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
+    device_prologue(/*film=*/false);
     RaysPassState guard(this);
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
     if (totals_.n == 0) totals_.alloc(12);
@@ -462,30 +478,28 @@ class Handle : public HandleBase {
     check_device_errors();
   }
   void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_user, int film_mem, rrt_render_stats* stats) override {
-    check_ray_samples("rrt_render_rays", rays);
-    check_rect("rrt_render_rays: rect outside the film", rect);
+    check_args("rrt_render_rays", kWhenIdle, Prec{"ray", rays->precision}, {}, rect);
     if (s0 < 1 || s1 > desc_.sampler.samples_per_pixel || s0 >= s1) throw std::invalid_argument("rrt_render_rays: sample range outside [1, nsamp) or empty");
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
-    check_no_crop();
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = (size_t)(rect[3] - rect[1]), rpix = rw * rh, ns_all = (size_t)(s1 - s0);
+    device_prologue();
+    const CallGeom g = call_geom(rect, kNoBands, 0, 1);
+    const size_t ns_all = (size_t)(s1 - s0);
     RaysPassState guard(this);
-    frame_setup(false, rpix * ns_all, /*tile_trees=*/false);
+    frame_setup(false, g.rpix * ns_all, /*tile_trees=*/false);
     RayStage stage;
-    RaySamples<R> in = ray_samples_device(rays, p_film, rpix * ns_all, false, stage);
+    RaySamples<R> in = ray_samples_device(rays, p_film, g.rpix * ns_all, false, stage);
     in.s0 = (uint32_t)s0; in.ns_all = (uint32_t)ns_all;
     FrameRec fr;
-    fr.timing = stats != nullptr; fr.camera_samples = (uint64_t)rpix * ns_all;
-    if (fr.timing) { fr.ev_begin = fr.make(); fr.ev_end = fr.make(); HIP_CHECK(hipEventRecord(fr.ev_begin, st_)); }
-    for_each_pass(rect, 1u << 30, 1, 0, rw, rh, s0 - 1, s1 - 1, cap_, [&](const PassDesc& pd) {
+    fr.camera_samples = (uint64_t)g.rpix * ns_all;
+    fr.begin(stats != nullptr, st_);
+    for_each_pass(g, s0 - 1, s1 - 1, cap_, [&](const PassDesc& pd) {
       hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
       const size_t e = tick(fr, 0);
       launch_ingest(pd, in, 0);
       tock(fr, e);
       pass_integrate(pd, 0u, fr);
-      pass_film(pd, nullptr, rect, false, 0u, fr);
+      pass_film(pd, nullptr, g, false, 0u, fr);
     });
-    if (fr.timing) HIP_CHECK(hipEventRecord(fr.ev_end, st_));
+    fr.end(st_);
     merge_out(film_user, nullptr, film_mem, true);
     HIP_CHECK(hipStreamSynchronize(st2_));
     check_device_errors();
@@ -494,7 +508,8 @@ class Handle : public HandleBase {
 
   // ---- the frame: SamplerIntegrator::si_render (integrator/mod.rs:48-139) over a pixel rect -------------------
   void render_rect(const int32_t rect[4], void* film_user, int film_mem, rrt_render_stats* stats) override {
-    render_impl(rect, 1u << 30, 1, 0, film_user, film_mem, stats);
+    check_rect("render rect outside the film", rect);   // (the frame's own refusal: its text is older than the calls' names)
+    render_impl(call_geom(rect, kNoBands, 0, 1), film_user, film_mem, stats);
   }
   // rows of the interleaved 16-row bands b with b % world == rank (partition.py), as ONE pixel set
   // the main stream carries the critical path (closest-hit -> shade); shadow rays fill what it leaves idle
@@ -538,18 +553,16 @@ class Handle : public HandleBase {
     if (err & ERR_KIND_SET) throw DeviceError("internal: a material produced a BxDF outside the kind set its shading kernel was selected for (shade_spec())");
   }
   void render_bands(int rank, int world, void* film_user, int film_mem, rrt_render_stats* stats) override {
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_bands: bad rank/world");
+    check_args("render_bands", kAnyTime, {}, Ranks{rank, world});
     const int32_t full[4] = {0, 0, desc_.film.xres, desc_.film.yres};
-    render_impl(full, 16, (uint32_t)world, (uint32_t)rank, film_user, film_mem, stats);
+    render_impl(call_geom(full, kBandH, rank, world), film_user, film_mem, stats);
   }
   // ---- rrt_render_moments: the frame of render_rect / render_bands, and the sample-variance plane beside it ----------------------------------
   // render_impl in its moments mode: the passes of a frame with film_records off (per-slot layout), k_film_box_moments / k_film_wide_moments in
   // place of the film kernels, a second internal W x H x 4 running-sum buffer merged into the caller's plane by k_aov_merge (a plain +=).
   void render_moments(const int32_t rect[4], int rank, int world, void* film_user, void* moments_user, int mem, rrt_render_stats* stats) override {
-    if (pending_) throw std::invalid_argument("render_moments: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_moments: bad rank/world");
-    check_rect("render_moments: rect outside the film", rect);
-    render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user);
+    check_args("render_moments", kWhenIdle, {}, Ranks{rank, world}, rect);
+    render_impl(call_geom(rect, bands_of(world), rank, world), film_user, mem, stats, moments_user);
   }
   // ---- rrt_render_frame_aov: the moments frame and the feature buffers of rrt_render_aov from one camera pass --------------------------------------------
   // Which scenes take which route. A frame whose passes begin with a queued closest-hit launch over the camera rays - the Path integrator, and
@@ -559,14 +572,11 @@ class Handle : public HandleBase {
   // (k_direct_tree: one thread per camera sample, no queue) - renders as a moments frame and render_aov's own pass follows it. Both routes add the
   // same bits.
   void render_frame_aov(const int32_t rect[4], int rank, int world, void* film_user, void* moments_user, int mem, uint64_t aov_max_samples, const rrt_aov* aov, rrt_render_stats* stats) override {
-    if (pending_) throw std::invalid_argument("render_frame_aov: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (aov->precision != precision()) throw std::invalid_argument("render_frame_aov: plane precision must match the handle");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_frame_aov: bad rank/world");
-    check_rect("render_frame_aov: rect outside the film", rect);
+    check_args("render_frame_aov", kWhenIdle, Prec{"plane", aov->precision}, Ranks{rank, world}, rect);
     const int integ = desc_.integrator.type;
     const bool queued = (integ == RRT_INT_PATH && desc_.integrator.max_depth > 0) || ((integ == RRT_INT_DIRECT || integ == RRT_INT_DEBUG) && !(has_transmissive_ || tex_depth_ > 0));
     FrameAov fa{aov, queued ? frame_samples(aov_max_samples) : 0};
-    render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, moments_user, &fa);
+    render_impl(call_geom(rect, bands_of(world), rank, world), film_user, mem, stats, moments_user, &fa);
     if (!queued) render_aov(rect, rank, world, aov_max_samples, aov);
   }
   // ---- rrt_render_passes: the frame, and beside it the films of its next-event terms split by light group and path vertex --------------------------------
@@ -577,9 +587,7 @@ class Handle : public HandleBase {
     const uint32_t nl = (uint32_t)desc_.n_lights;
     if (light_group) for (uint32_t i = 0; i < nl; i++)
       if (light_group[i] >= 32) throw std::invalid_argument("render_passes: light_group[" + std::to_string(i) + "] = " + std::to_string((int)light_group[i]) + ": a group is 0 .. 31");
-    if (pending_) throw std::invalid_argument("render_passes: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_passes: bad rank/world");
-    check_rect("render_passes: rect outside the film", rect);
+    check_args("render_passes", kWhenIdle, {}, Ranks{rank, world}, rect);
     const rrt_film& f = desc_.film;
     if (desc_.integrator.type != RRT_INT_PATH)
       throw UnsupportedError("render_passes: the passes are the Path integrator's next-event terms; DirectLighting, AO and Debug frames have no passes");
@@ -597,7 +605,7 @@ class Handle : public HandleBase {
         if (b >= passes[k].bounce_lo && (passes[k].bounce_hi <= 0 || b < passes[k].bounce_hi)) pass_tab_host_[nl + (size_t)b] |= 1u << k;
     }
     const PassesReq pq{passes, n_passes};
-    render_impl(rect, world > 1 ? 16u : 1u << 30, (uint32_t)world, (uint32_t)rank, film_user, mem, stats, nullptr, nullptr, &pq);
+    render_impl(call_geom(rect, bands_of(world), rank, world), film_user, mem, stats, nullptr, nullptr, &pq);
   }
   struct PassesReq { const rrt_pass* passes; int n; };
   // rrt_combine_passes: one kernel over the pixels; films in host memory are staged
@@ -630,22 +638,17 @@ class Handle : public HandleBase {
   struct FrameAov { const rrt_aov* out; uint64_t prefix; };
   // moments_user: the caller's sample-variance plane (same memory kind as the film) = the frame's moments mode; NULL = a plain frame, unless `fa` asks
   // for a moments-mode frame whose plane is not handed out
-  void render_impl(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, void* film_user, int film_mem, rrt_render_stats* stats, void* moments_user = nullptr,
-                   const FrameAov* fa = nullptr, const PassesReq* pq = nullptr) {
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
+  void render_impl(const CallGeom& g, void* film_user, int film_mem, rrt_render_stats* stats, void* moments_user = nullptr, const FrameAov* fa = nullptr,
+                   const PassesReq* pq = nullptr) {
+    device_prologue();
     const rrt_film& f = desc_.film;
-    check_no_crop();
-    check_rect("render rect outside the film", rect);
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = band_rows(rect, band_h, n_ranks, rank), rpix = rw * rh;
-    const uint64_t s_total = frame_samples();
-    if (rpix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }   // a rank that owns no band (world > yres / 16): nothing to add to the caller's film
+    if (g.rpix == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }   // a rank that owns no band (world > yres / 16): nothing to add to the caller's film
 
     const bool with_moments = moments_user != nullptr || fa != nullptr;
     // run_pass, rect_passes and frame_setup work for a passes frame while passes_n_ > 0; the pools' passes members are null in every other frame
     struct PassesOff { Handle* h; ~PassesOff() { h->passes_n_ = 0; h->pool_.smask = nullptr; h->pool_.pass_L = nullptr; h->pool_.pass_stride = 0; h->pool_.pass_tab = nullptr; } } passes_off{this};
     passes_n_ = pq ? (uint32_t)pq->n : 0u;
-    frame_setup(with_moments, rpix * (size_t)std::max<uint64_t>(s_total, 1));
+    frame_setup(with_moments, g.rpix * (size_t)std::max<uint64_t>(g.s_total, 1));
     struct AovOff { Handle* h; ~AovOff() { h->aov_prefix_ = 0; } } aov_off{this};   // run_pass shades first hits for this frame only
     aov_prefix_ = fa ? fa->prefix : 0;
     if (aov_prefix_ > 0) {   // (setup, not the pass loop: frame_setup has sized the pools)
@@ -654,12 +657,11 @@ class Handle : public HandleBase {
       HIP_CHECK(hipMemsetAsync(aov_planes_.p, 0, 3 * plane_n * sizeof(R), st_));
       ensure_aov_recs();
     }
-    const bool timing = stats != nullptr || (defer_ && frame_stats_);
     auto fr = std::make_unique<FrameRec>();
-    fr->timing = timing; fr->camera_samples = (uint64_t)rpix * s_total;
-    if (timing) { fr->ev_begin = fr->make(); fr->ev_end = fr->make(); HIP_CHECK(hipEventRecord(fr->ev_begin, st_)); }
-    rect_passes(rect, band_h, n_ranks, rank, rw, rh, 0, s_total, with_moments, *fr);
-    if (timing) HIP_CHECK(hipEventRecord(fr->ev_end, st_));
+    fr->camera_samples = (uint64_t)g.rpix * g.s_total;
+    fr->begin(stats != nullptr || (defer_ && frame_stats_), st_);
+    rect_passes(g, 0, g.s_total, with_moments, *fr);
+    fr->end(st_);
     // merge into the caller's film (+=)
     const bool wait = !(film_mem == RRT_MEM_DEVICE && defer_) || pq != nullptr;
     if (pq) {   // each pass's internal film into its caller's film, as the frame's own below
@@ -732,27 +734,30 @@ class Handle : public HandleBase {
     pass_cap_ = P;
     pool_.pass_L = pass_planes_.p; pool_.pass_stride = P; pool_.pass_tab = pass_tab_.p; pool_.smask = pass_smask_[0].p;
   }
-  // the passes of sample numbers 1 + s_lo .. s_hi of a rect's (or its bands') rw x rh pixels: pixel groups and sample chunks from what the pools hold
-  void rect_passes(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_lo, uint64_t s_hi, bool with_moments, FrameRec& fr) {
-    for_each_pass(rect, band_h, n_ranks, rank, rw, rh, s_lo, s_hi, passes_n_ > 0 ? pass_cap_ : cap_, [&](const PassDesc& pd) { run_pass(pd, nullptr, rect, with_moments, fr); });
+  // the passes of sample numbers 1 + s_lo .. s_hi of a call's pixels: pixel groups and sample chunks from what the pools hold
+  void rect_passes(const CallGeom& g, uint64_t s_lo, uint64_t s_hi, bool with_moments, FrameRec& fr) {
+    for_each_pass(g, s_lo, s_hi, passes_n_ > 0 ? pass_cap_ : cap_, [&](const PassDesc& pd) { run_pass(pd, nullptr, g, with_moments, fr); });
   }
-  // the cutter: sample numbers 1 + s_lo .. s_hi of rw x rh pixels as passes of at most cap slots - pixel groups outermost, sample chunks inside
+  // The cutter: sample numbers 1 + s_lo .. s_hi of n_units units of unit_px pixels each (1: the call's pixels; kTileW * kTileH: the tiles of a
+  // list) as passes of at most cap slots - unit groups outermost, sample chunks inside. fn(pixel offset, pixels, s_begin, samples) makes the PassDesc.
   template <class F>
-  void for_each_pass(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_lo, uint64_t s_hi, size_t cap, F&& fn) {
-    const size_t rpix = rw * rh;
-    if (rpix == 0 || s_hi <= s_lo) return;
-    const size_t group = std::min(rpix, cap);                            // pixels per group
-    const uint64_t s_chunk = std::max<uint64_t>(1, cap / group);          // samples per pass
-    // tile order of the pixels (PassDesc::tiled) where the rect allows it: whole kTileW x kTileH tiles
-    const uint32_t tiled = (tile_order_ && rw % kTileW == 0 && rh % kTileH == 0) ? 1u : 0u;
-    for (size_t g0 = 0; g0 < rpix; g0 += group) {
-      const size_t npix = std::min(group, rpix - g0);
-      for (uint64_t sb = s_lo; sb < s_hi; sb += s_chunk) {
-        const uint64_t ns = std::min<uint64_t>(s_chunk, s_hi - sb);
-        PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)g0, (uint32_t)npix, (uint32_t)(1 + sb), (uint32_t)ns, band_h, n_ranks, rank, tiled};
-        fn(pd);
-      }
+  static void cut_passes(size_t n_units, size_t unit_px, uint64_t s_lo, uint64_t s_hi, size_t cap, F&& fn) {
+    if (n_units == 0 || s_hi <= s_lo) return;
+    const size_t group = std::max<size_t>(1, std::min(n_units, cap / unit_px));          // units per group
+    const uint64_t s_chunk = std::max<uint64_t>(1, cap / (group * unit_px));             // samples per pass
+    for (size_t u0 = 0; u0 < n_units; u0 += group) {
+      const size_t nu = std::min(group, n_units - u0);
+      for (uint64_t sb = s_lo; sb < s_hi; sb += s_chunk)
+        fn((uint32_t)(u0 * unit_px), (uint32_t)(nu * unit_px), (uint32_t)(1 + sb), (uint32_t)std::min<uint64_t>(s_chunk, s_hi - sb));
     }
+  }
+  // the passes of a call's own pixel grid, in tile order (PassDesc::tiled) where the rect allows it: whole kTileW x kTileH tiles
+  template <class F>
+  void for_each_pass(const CallGeom& g, uint64_t s_lo, uint64_t s_hi, size_t cap, F&& fn) {
+    const uint32_t tiled = (tile_order_ && g.rw % kTileW == 0 && g.rh % kTileH == 0) ? 1u : 0u;
+    cut_passes(g.rpix, 1, s_lo, s_hi, cap, [&](uint32_t p0, uint32_t npix, uint32_t s_begin, uint32_t ns) {
+      fn(PassDesc{g.rect[0], g.rect[1], (int32_t)g.rw, p0, npix, s_begin, ns, g.band_h, g.n_ranks, g.rank, tiled});
+    });
   }
   // HIP events around a launch of a frame whose statistics are wanted (FrameRec::timing), under the category frame_stats() adds it to
   size_t tick(FrameRec& fr, int cat, hipStream_t stream = nullptr) {
@@ -766,13 +771,13 @@ class Handle : public HandleBase {
   // one pass: camera kernels, the integrator's launches, the film kernel. list: the tiles of a listed pass (list_pixel; box filter of radius 0.5 and
   // moments only, no tile trees, no film records), NULL for a pass over the rect's own pixel grid. The three parts meet in pool state only (q_active,
   // counters[C_ACTIVE], ray_o / ray_d, path, L, weight, samp, rdx_*): rrt_radiance and rrt_render_rays put k_ingest_rays in place of the first part.
-  void run_pass(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, FrameRec& fr) {
+  void run_pass(const PassDesc& pd, const uint32_t* list, const CallGeom& g, bool with_moments, FrameRec& fr) {
     // rrt_render_frame_aov: the leading samples of this pass that the feature buffers take (a pass that begins beyond the prefix: none)
     const uint64_t s_off = (uint64_t)pd.s_begin - 1;
     const uint32_t aov_ns = (!list && aov_prefix_ > s_off) ? (uint32_t)std::min<uint64_t>(pd.ns, aov_prefix_ - s_off) : 0u;
     pass_camera(pd, list, with_moments, fr);
     pass_integrate(pd, aov_ns, fr);
-    pass_film(pd, list, rect, with_moments, aov_ns, fr);
+    pass_film(pd, list, g, with_moments, aov_ns, fr);
   }
   // first part: the camera kernels fill the pools
   void pass_camera(const PassDesc& pd, const uint32_t* list, bool with_moments, FrameRec& fr) {
@@ -888,10 +893,10 @@ class Handle : public HandleBase {
     HIP_CHECK(hipGetLastError());
   }
   // third part: the film kernel reads L, weight and samp by slot
-  void pass_film(const PassDesc& pd, const uint32_t* list, const int32_t rect[4], bool with_moments, uint32_t aov_ns, FrameRec& fr) {
+  void pass_film(const PassDesc& pd, const uint32_t* list, const CallGeom& g, bool with_moments, uint32_t aov_ns, FrameRec& fr) {
     const rrt_film& f = desc_.film;
     const bool wide = wide_filter();
-    const FilmWindow win = film_window(rect);
+    const FilmWindow& win = g.win;
     const size_t npix = pd.npix;
     const uint64_t ns = pd.ns;
     const size_t e = tick(fr, 4);
@@ -1033,30 +1038,25 @@ class Handle : public HandleBase {
   // zeroed once and run on across the rounds; a pixel's sums are added in sample order whatever the pass, so a tile that stopped at k holds the bits
   // of a k-sample frame.
   void render_adaptive(const int32_t rect[4], const rrt_adaptive_params* ap, void* film_user, void* moments_user, uint32_t* tile_samples_user, int mem, rrt_render_stats* stats) override {
-    if (pending_) throw std::invalid_argument("render_adaptive: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
+    check_args("render_adaptive", kWhenIdle, {}, {}, rect);
+    device_prologue();
     const rrt_film& f = desc_.film;
     if (desc_.sampler.type == RRT_SAMPLER_STRATIFIED)
       throw UnsupportedError("render_adaptive: StratifiedSampler (the first k samples of a stratified pixel are not a k-sample stratified pixel; use the HaltonSampler)");
     if (wide_filter())
       throw UnsupportedError("render_adaptive: pixel filters other than the box filter of radius 0.5 (a wider filter splats across tiles with different sample counts)");
-    check_no_crop();
-    check_rect("render_adaptive: rect outside the film", rect);
-    const uint64_t K = frame_samples(ap->max_samples), k0 = std::min<uint64_t>(ap->min_samples, K);
-    const size_t rw = (size_t)(rect[2] - rect[0]), rh = (size_t)(rect[3] - rect[1]), rpix = rw * rh;
-    const uint32_t tiles_x = (uint32_t)(rw / kTileW), n_tiles = tiles_x * (uint32_t)(rh / kTileH);
+    const CallGeom g = call_geom(rect, kNoBands, 0, 1, ap->max_samples);
+    const uint64_t K = g.s_total, k0 = std::min<uint64_t>(ap->min_samples, K);
+    const uint32_t tiles_x = (uint32_t)(g.rw / kTileW), n_tiles = tiles_x * (uint32_t)(g.rh / kTileH);
     const auto kind = mem == RRT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (ad_samples_.n < n_tiles) { ad_list_[0].alloc(n_tiles); ad_list_[1].alloc(n_tiles); ad_err_.alloc(n_tiles); ad_samples_.alloc(n_tiles); }
     if (ad_count_.n == 0) ad_count_.alloc(1);
     HIP_CHECK(hipMemsetAsync(ad_samples_.p, 0, n_tiles * sizeof(uint32_t), st_));
-    frame_setup(true, rpix * (size_t)std::max<uint64_t>(K, 1));
-    const bool timing = stats != nullptr;
+    frame_setup(true, g.rpix * (size_t)std::max<uint64_t>(K, 1));
     FrameRec fr;
-    fr.timing = timing;
-    if (timing) { fr.ev_begin = fr.make(); fr.ev_end = fr.make(); HIP_CHECK(hipEventRecord(fr.ev_begin, st_)); }
-    rect_passes(rect, 1u << 30, 1u, 0u, rw, rh, 0, k0, true, fr);
-    fr.camera_samples = (uint64_t)rpix * k0;
+    fr.begin(stats != nullptr, st_);
+    rect_passes(g, 0, k0, true, fr);
+    fr.camera_samples = (uint64_t)g.rpix * k0;
     const uint32_t* list_in = nullptr;   // (round 0 took every tile)
     uint32_t n_active = n_tiles;
     int cur = 0;
@@ -1073,22 +1073,15 @@ class Handle : public HandleBase {
       if (n_next == 0) break;
       if (n_next > n_active) throw DeviceError("internal: k_tile_select kept more tiles than it was given");
       const uint64_t nb = std::min<uint64_t>(ap->batch, K - k);
-      // listed passes: groups of whole tiles and sample chunks from what the pools hold, as rect_passes cuts a rect
-      const size_t group = std::max<size_t>(1, std::min<size_t>(n_next, cap_ / (kTileW * kTileH)));         // tiles per group
-      const uint64_t s_chunk = std::max<uint64_t>(1, cap_ / (group * kTileW * kTileH));                   // samples per pass
-      for (size_t g0 = 0; g0 < n_next; g0 += group) {
-        const size_t nt = std::min(group, (size_t)n_next - g0);
-        for (uint64_t sb = 0; sb < nb; sb += s_chunk) {
-          const uint64_t ns = std::min<uint64_t>(s_chunk, nb - sb);
-          PassDesc pd{rect[0], rect[1], (int32_t)rw, (uint32_t)(g0 * kTileW * kTileH), (uint32_t)(nt * kTileW * kTileH), (uint32_t)(1 + k + sb), (uint32_t)ns, 1u << 30, 1u, 0u, 1u};
-          run_pass(pd, ad_list_[cur].p, rect, true, fr);
-        }
-      }
+      // listed passes: the list's tiles as the cutter's units, always in tile order
+      cut_passes(n_next, kTileW * kTileH, k, k + nb, cap_, [&](uint32_t p0, uint32_t npix, uint32_t s_begin, uint32_t ns) {
+        run_pass(PassDesc{rect[0], rect[1], (int32_t)g.rw, p0, npix, s_begin, ns, g.band_h, g.n_ranks, g.rank, 1u}, ad_list_[cur].p, g, true, fr);
+      });
       fr.camera_samples += (uint64_t)n_next * (kTileW * kTileH) * nb;
       k += nb;
       list_in = ad_list_[cur].p; n_active = n_next; cur ^= 1;
     }
-    if (timing) HIP_CHECK(hipEventRecord(fr.ev_end, st_));
+    fr.end(st_);
     if (tile_samples_user) HIP_CHECK(hipMemcpyAsync(tile_samples_user, ad_samples_.p, n_tiles * sizeof(uint32_t), kind, st_));
     merge_out(film_user, moments_user, mem, true);
     check_device_errors();
@@ -1096,8 +1089,7 @@ class Handle : public HandleBase {
   }
   // ---- rrt_tile_error: k_tile_error over every tile of the rect, on the caller's plane --------------------------------------------------------------------
   void tile_error(const void* moments, int mem, const int32_t rect[4], double* out) override {
-    if (pending_) throw std::invalid_argument("tile_error: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    check_rect("tile_error: rect outside the film", rect);
+    check_args("tile_error", kWhenIdle, {}, {}, rect);
     const rrt_film& f = desc_.film;
     HIP_CHECK(hipSetDevice(dev_));
     using V4 = typename Vec4T<R>::type;
@@ -1123,8 +1115,8 @@ class Handle : public HandleBase {
   // state is kept changed: the internal film, the statistics' totals and the tile-tree state are not touched, and a RaygenStateGuard of the
   // call puts back what launch_raygen sets per pass. The caller sizes the pools and its records before.
   template <class Shade, class Gather>
-  void first_hit_passes(const int32_t rect[4], uint32_t band_h, uint32_t n_ranks, uint32_t rank, size_t rw, size_t rh, uint64_t s_total, Shade&& shade, Gather&& gather) {
-    for_each_pass(rect, band_h, n_ranks, rank, rw, rh, 0, s_total, cap_, [&](const PassDesc& pd) {
+  void first_hit_passes(const CallGeom& g, Shade&& shade, Gather&& gather) {
+    for_each_pass(g, 0, g.s_total, cap_, [&](const PassDesc& pd) {
       const uint32_t grid = (uint32_t)(((size_t)pd.npix * pd.ns + kBlock - 1) / kBlock);
       hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
       launch_raygen(pd, grid, nullptr, 1, /*for_render=*/false);   // no root cull, no film records: every survivor is queued, weight[slot] is per slot
@@ -1147,15 +1139,10 @@ class Handle : public HandleBase {
     aov_passes("render_aov_follow", rect, rank, world, max_samples, max_follow, out);
   }
   void aov_passes(const std::string& who, const int32_t rect[4], int rank, int world, uint64_t max_samples, uint32_t max_follow, const rrt_aov* out) {
-    if (pending_) throw std::invalid_argument(who + ": a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (out->precision != precision()) throw std::invalid_argument(who + ": plane precision must match the handle");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument(who + ": bad rank/world");
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
-    check_no_crop();
-    check_rect((who + ": rect outside the film").c_str(), rect);
+    check_args(who, kWhenIdle, Prec{"plane", out->precision}, Ranks{rank, world}, rect);
+    device_prologue();
     const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
-    const CallGeom g = call_geom(rect, rank, world, max_samples);
+    const CallGeom g = call_geom(rect, bands_of(world), rank, world, max_samples);
     if (g.rpix == 0 || g.s_total == 0) return;   // nothing to add to the caller's planes
     if (!has_specular_) max_follow = 0;   // no surface of the scene is followed: every chain ends on its first hit, and no level is launched to find that out
     RaygenStateGuard guard(this);
@@ -1165,7 +1152,7 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
     ensure_pools(std::min(max_paths_, std::max<size_t>(g.rpix * (size_t)g.s_total, 64)));
     ensure_aov_recs();
-    first_hit_passes(rect, g.band_h, (uint32_t)world, (uint32_t)rank, g.rw, g.rh, g.s_total,
+    first_hit_passes(g,
       [&](const PassDesc&, uint32_t grid) {
         const dim3 sg(std::min(grid, 16384u));
         // level 0's records are k_aov_shade's own (see k_aov_follow)
@@ -1200,17 +1187,12 @@ class Handle : public HandleBase {
     rrt_ao_params prm;
     if (params) prm = *params; else ao_defaults(&prm);
     if (prm.n_samples < 1 || prm.n_samples > 256) throw std::invalid_argument("render_ao: n_samples must be 1..256 (draw i reads sampler dimensions 5 + 2i and 6 + 2i, and the permutation tables end at 1000)");
-    if (pending_) throw std::invalid_argument("render_ao: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (out->precision != precision()) throw std::invalid_argument("render_ao: plane precision must match the handle");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_ao: bad rank/world");
-    check_rect("render_ao: rect outside the film", rect);
+    check_args("render_ao", kWhenIdle, Prec{"plane", out->precision}, Ranks{rank, world}, rect);
     // the StratifiedSampler's draws past `dimension` are the [-1, 1) generator (Q25): no scene means a hemisphere sample drawn from those
     if (desc_.sampler.type == RRT_SAMPLER_STRATIFIED) throw UnsupportedError("render_ao under the StratifiedSampler (its 2D draws past `dimension` are not in [0, 1))");
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
-    check_no_crop();
+    device_prologue();
     const size_t plane_n = (size_t)desc_.film.xres * (size_t)desc_.film.yres * 4;
-    const CallGeom g = call_geom(rect, rank, world, max_samples);
+    const CallGeom g = call_geom(rect, bands_of(world), rank, world, max_samples);
     if (g.rpix == 0 || g.s_total == 0) return;   // nothing to add to the caller's planes
     RaygenStateGuard guard(this);
     // what the rounds borrow of the pool: L (the accumulators' place) and the first shadow queue, put back on every way out
@@ -1231,7 +1213,7 @@ class Handle : public HandleBase {
     pool_.shadow_count = counters_.p + C_SHADOW;
     const uint32_t n_draws = (uint32_t)prm.n_samples;
     const int cos_sample = prm.cos_sample ? 1 : 0;
-    first_hit_passes(rect, g.band_h, (uint32_t)world, (uint32_t)rank, g.rw, g.rh, g.s_total,
+    first_hit_passes(g,
       [&](const PassDesc&, uint32_t grid) {
         for (uint32_t i = 0; i < n_draws; i++) {
           hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 1);   // the shadow queue and the work cursors start at 0
@@ -1250,18 +1232,13 @@ class Handle : public HandleBase {
   // into it, k_matte_rank sorts it out. Load, rank and the staging of a host table run over the whole W x H x K table whatever the rect - also for
   // a rank without rows or a call without samples, which runs no pass: a frame cut into n calls moves the table n times.
   void render_mattes(const int32_t rect[4], int rank, int world, uint64_t max_samples, const uint32_t* prim_id, size_t n_prim_id, const rrt_mattes* out) override {
-    if (pending_) throw std::invalid_argument("render_mattes: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
     if (prim_id && n_prim_id != desc_.n_prims)
       throw std::invalid_argument("render_mattes: n_prim_id = " + std::to_string(n_prim_id) + ", the scene has " + std::to_string(desc_.n_prims) + " primitives (one id per entry of rrt_scene_desc.prims)");
-    if (out->precision != precision()) throw std::invalid_argument("render_mattes: table precision must match the handle");
-    if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("render_mattes: bad rank/world");
-    HIP_CHECK(hipSetDevice(dev_));
-    check_renderable();
-    check_no_crop();
-    check_rect("render_mattes: rect outside the film", rect);
+    check_args("render_mattes", kWhenIdle, Prec{"table", out->precision}, Ranks{rank, world}, rect);
+    device_prologue();
     const size_t NP = (size_t)desc_.film.xres * (size_t)desc_.film.yres;
     const uint32_t K = (uint32_t)out->n_slots;
-    const CallGeom g = call_geom(rect, rank, world, max_samples);
+    const CallGeom g = call_geom(rect, bands_of(world), rank, world, max_samples);
     using V4 = typename Vec4T<R>::type;
     RaygenStateGuard guard(this);
 
@@ -1298,7 +1275,7 @@ class Handle : public HandleBase {
     if (g.rpix > 0 && g.s_total > 0) {
       ensure_pools(std::min(max_paths_, std::max<size_t>(g.rpix * (size_t)g.s_total, 64)));
       if (matte_rec_.n < cap_) { HIP_CHECK(hipStreamSynchronize(st_)); matte_rec_.alloc(cap_); }
-      first_hit_passes(rect, g.band_h, (uint32_t)world, (uint32_t)rank, g.rw, g.rh, g.s_total,
+      first_hit_passes(g,
         [&](const PassDesc&, uint32_t grid) {
           hipLaunchKernelGGL((k_matte_ids<R>), dim3(std::min(grid, 16384u)), dim3(kBlock), 0, st_, pool_, (const uint32_t*)matte_id_dev_.p, (uint32_t)n_ord, matte_rec_.p);
         },
@@ -1317,8 +1294,7 @@ class Handle : public HandleBase {
   }
   // rrt_matte_extract: one kernel over the pixels; a table in host memory is staged through the buffers render_mattes stages through
   void matte_extract(const rrt_mattes* m, const uint32_t* ids, int n_ids, void* alpha) override {
-    if (pending_) throw std::invalid_argument("matte_extract: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (m->precision != precision()) throw std::invalid_argument("matte_extract: table precision must match the handle");
+    check_args("matte_extract", kWhenIdle, Prec{"table", m->precision});
     HIP_CHECK(hipSetDevice(dev_));
     using V4 = typename Vec4T<R>::type;
     const size_t NP = (size_t)desc_.film.xres * (size_t)desc_.film.yres;
@@ -1359,8 +1335,7 @@ class Handle : public HandleBase {
     hipLaunchKernelGGL((k_dn_atrous<R, S>), grid, block, 0, st_, cin, cout, dn_g_.p, dn_p_.p, k);
   }
   void denoise(const void* film, const rrt_aov* aov, const void* moments, const rrt_denoise_params* p, void* film_out) override {
-    if (pending_) throw std::invalid_argument("denoise: a frame is in flight (rrt_render_bands_begin without rrt_render_end)");
-    if (aov->precision != precision()) throw std::invalid_argument("denoise: plane precision must match the handle");
+    check_args("denoise", kWhenIdle, Prec{"plane", aov->precision});
     HIP_CHECK(hipSetDevice(dev_));
     using V4 = typename Vec4T<R>::type;
     const size_t W = (size_t)desc_.film.xres, H = (size_t)desc_.film.yres, npix = W * H;

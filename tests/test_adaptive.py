@@ -363,6 +363,45 @@ def test_pass_cutting_changes_no_bit(prec, workdir):
         assert getattr(st, key) == getattr(want[3], key), key
 
 
+def _cut(n_units, unit_px, n_samples, cap):
+    """(groups, sample chunks per group) of the driver's cutter for n_units units of unit_px pixels and n_samples samples in pools of cap slots"""
+    group = max(1, min(n_units, cap // unit_px))
+    s_chunk = max(1, cap // (group * unit_px))
+    return -(-n_units // group), -(-n_samples // s_chunk)
+
+
+@pytest.mark.gpu
+@PRECS
+@pytest.mark.parametrize("side,max_paths,batch,listed_cut", [(8, 256, 8, (1, 2)), (16, 128, 2, (2, 2))], ids=["one-group-two-chunks", "two-groups-one-sample-chunks"])
+def test_listed_cut_corners_change_no_bit(side, max_paths, batch, listed_cut, prec, workdir):
+    """The two other corners of the listed cut, beside test_pass_cutting_changes_no_bit's groups of four tiles and single-sample chunks. Threshold 0 is
+    met by no tile, so every tile stays listed until K = 12 (min_samples 4).
+    Rect 8 x 8 (one tile), max_paths 256, batch 8: one listed round of one group and two chunks of four samples.
+    Rect 16 x 16 (four tiles), max_paths 128, batch 2: four listed rounds of two groups of two tiles and two single-sample chunks.
+    Film, moments and tile_samples are those of the same call at max_paths = 2**28, bit for bit.
+    The pool capacity is not rounded: a fresh handle's pools hold min(max_paths, the call's pixels x samples) slots exactly (768 and 3072 wanted
+    here), so the cuts are computed from max_paths itself; the frame's closest-hit launch count - max_depth = 5 per pass of the Path integrator -
+    shows that they happened."""
+    rect, T = (0, 0, side, side), dict(PARAMS, batch=batch, threshold=0.0)
+    out = {}
+    for cap in (max_paths, 2 ** 28):
+        r = Renderer(_scene("A", workdir), 0, prec)
+        r.set_option("max_paths", cap)
+        out[cap] = r.render_adaptive(rect, stats=True, **T)
+        r.close()
+    (film, mom, samples, st), want = out[max_paths], out[2 ** 28]
+    n_tiles, rounds = (side // 8) ** 2, (K - T["min_samples"]) // batch
+    groups, chunks = _cut(n_tiles, 64, batch, max_paths)
+    assert (groups, chunks) == listed_cut
+    g0, c0 = _cut(side * side, 1, T["min_samples"], max_paths)
+    print(f"rect {side} x {side}, max_paths {max_paths}: round 0 {g0} x {c0} passes, {rounds} listed rounds of {groups} x {chunks}; closest launches {st.closest_launches}, {want[3].closest_launches} uncut")
+    assert st.closest_launches == 5 * (g0 * c0 + rounds * groups * chunks) and want[3].closest_launches == 5 * (1 + rounds)
+    assert np.all(samples == K) and film[..., :3].max() > 0
+    assert np.array_equal(samples, want[2]) and np.array_equal(film, want[0]) and np.array_equal(mom, want[1])
+    for key in STATS + ("camera_samples",):
+        assert getattr(st, key) == getattr(want[3], key), key
+
+
 @pytest.mark.gpu
 @PRECS
 @pytest.mark.parametrize("min_samples,batch", [(4, 8), (2, 10)], ids=["8", "8+2"])

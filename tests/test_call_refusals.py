@@ -1,0 +1,136 @@
+"""What the driver's entry points refuse of their arguments (device/rrt_impl.hpp, the call preamble): the exception class and the whole message.
+
+One table of (entry point, violated precondition) -> message, over every entry point of the handle that takes the precondition:
+  * a frame in flight (rrt_render_bands_begin without rrt_render_end, put in flight as tests/test_moments.py does it);
+  * a rank outside [0, world) and a world < 1;
+  * a rect beyond the film and an empty rect;
+  * a caller's struct of the other precision (the Python mirror fills its structs from Renderer.precision / Renderer.dtype, so the mirror is
+    told the other precision for the length of the call; the handle stays what it is).
+Each case violates one precondition only and every other argument is one the call takes. Not in the table because the C ABI refuses them before
+the handle sees them: the empty rect of rrt_render_adaptive and rrt_tile_error (whole 8 x 8 tiles), null pointers, bad memory kinds.
+
+rrt_render_rect and rrt_render_bands do not refuse a frame in flight: they are called while one is and must return. Afterwards the handle ends
+the frame, and one render() is a fresh handle's, bit for bit.
+
+Scene: test_moments.py's kind of scene (scenes.cfg3, Path) at 16 x 16, 3 samples per pixel, both precisions.
+"""
+import numpy as np
+import pytest
+
+from rs_ray_toy_amd import _abi as A
+from rs_ray_toy_amd import RRT_F32, RRT_F64, Renderer, RrtError, Scene, scenes
+
+W = H = 16
+FULL = (0, 0, W, H)
+IN_FLIGHT = "a frame is in flight (rrt_render_bands_begin without rrt_render_end)"
+
+
+def _planes(r, names):
+    return {k: np.zeros((H, W, 4), r.dtype) for k in names}
+
+
+def _mattes(r):
+    return dict(ids=np.zeros((H, W, 2), np.uint32), coverage=np.zeros((H, W, 2), r.dtype), weight=np.zeros((H, W, 4), r.dtype))
+
+
+def _rays(n):
+    o = np.zeros((n, 3)); d = np.tile([1.0, 0.0, 0.0], (n, 1))
+    return o, d
+
+
+def _n(rect):
+    return max(1, (rect[2] - rect[0]) * (rect[3] - rect[1]))
+
+
+# name -> (the message's prefix, the call with valid defaults); rect / rank / world are overridden by the cases that violate them
+CALLS = {
+    "render": ("render", lambda r, rect=FULL, rank=0, world=1: r.render(rect)),
+    "render_bands": ("render_bands", lambda r, rect=FULL, rank=0, world=1: r.render_bands(rank, world)),
+    "render_bands_begin": ("render_bands", lambda r, rect=FULL, rank=0, world=1: r.render_bands_begin(rank, world, r._frame.data_ptr())),
+    "camera_samples": ("camera_samples", lambda r, rect=FULL, rank=0, world=1: r.camera_samples(rect, 1, 2)),
+    "radiance": ("rrt_radiance", lambda r, rect=FULL, rank=0, world=1: r.radiance(*_rays(1), np.zeros((1, 2), np.int64), np.ones(1, np.int64))),
+    "render_rays": ("rrt_render_rays", lambda r, rect=FULL, rank=0, world=1: r.render_rays(rect, 1, 2, np.concatenate(_rays(_n(rect)), 1), None,
+                                                                                          np.full((_n(rect), 2), 0.5, r.dtype))),
+    "render_moments": ("render_moments", lambda r, rect=FULL, rank=0, world=1: r.render_moments(rect, rank, world)),
+    "render_frame_aov": ("render_frame_aov", lambda r, rect=FULL, rank=0, world=1: r.render_frame_aov(rect, rank, world)),
+    "render_passes": ("render_passes", lambda r, rect=FULL, rank=0, world=1: r.render_passes([(1, 0, 0)], rect=rect, rank=rank, world=world)),
+    "render_adaptive": ("render_adaptive", lambda r, rect=FULL, rank=0, world=1: r.render_adaptive(rect, min_samples=2, batch=1)),
+    "tile_error": ("tile_error", lambda r, rect=FULL, rank=0, world=1: r.tile_error(np.zeros((H, W, 4), r.dtype), rect)),
+    "render_aov": ("render_aov", lambda r, rect=FULL, rank=0, world=1: r.render_aov(rect, rank=rank, world=world)),
+    "render_aov_follow": ("render_aov_follow", lambda r, rect=FULL, rank=0, world=1: r.render_aov(rect, rank=rank, world=world, follow=2)),
+    "render_ao": ("render_ao", lambda r, rect=FULL, rank=0, world=1: r.render_ao(rect, rank=rank, world=world, n_samples=2)),
+    "render_mattes": ("render_mattes", lambda r, rect=FULL, rank=0, world=1: r.render_mattes(slots=2, rect=rect, rank=rank, world=world)),
+    "matte_extract": ("matte_extract", lambda r, rect=FULL, rank=0, world=1: r.matte_extract(_mattes(r), [1])),
+    "denoise": ("denoise", lambda r, rect=FULL, rank=0, world=1: r.denoise(np.zeros((H, W, 4), r.dtype), _planes(r, ("albedo", "normal", "depth")))),
+    "denoise_moments": ("denoise", lambda r, rect=FULL, rank=0, world=1: r.denoise(np.zeros((H, W, 4), r.dtype), _planes(r, ("albedo", "normal", "depth")),
+                                                                                  moments=np.zeros((H, W, 4), r.dtype))),
+    "trace_closest": ("", lambda r, rect=FULL, rank=0, world=1: r.trace_closest(*_rays(1), np.ones(1))),
+    "trace_any": ("", lambda r, rect=FULL, rank=0, world=1: r.trace_any(*_rays(1), np.ones(1))),
+}
+RANKED = ("render_bands", "render_bands_begin", "render_moments", "render_frame_aov", "render_passes", "render_aov", "render_aov_follow", "render_ao", "render_mattes")
+RECTS = ("render_rays", "render_moments", "render_frame_aov", "render_passes", "render_aov", "render_aov_follow", "render_ao", "render_mattes")
+TILED = ("render_adaptive", "tile_error")      # whole 8 x 8 tiles: only a rect beyond the film reaches the handle
+IDLE = ("radiance", "render_rays", "render_moments", "render_frame_aov", "render_passes", "render_adaptive", "tile_error", "render_aov", "render_aov_follow",
+        "render_ao", "render_mattes", "matte_extract", "denoise", "denoise_moments")
+PRECISION = {"radiance": "ray", "render_rays": "ray", "render_frame_aov": "plane", "render_aov": "plane", "render_aov_follow": "plane", "render_ao": "plane",
+             "render_mattes": "table", "matte_extract": "table", "denoise": "plane", "denoise_moments": "plane"}
+
+# (entry point, violated precondition) -> the whole message; the class is RrtError itself (RRT_EINVAL) in every case
+TABLE = {}
+for _name in RANKED:
+    TABLE[(_name, "rank")] = TABLE[(_name, "world")] = CALLS[_name][0] + ": bad rank/world"
+for _name in RECTS + TILED:
+    TABLE[(_name, "beyond")] = CALLS[_name][0] + ": rect outside the film"
+for _name in RECTS:
+    TABLE[(_name, "empty")] = CALLS[_name][0] + ": rect outside the film"
+TABLE[("render", "beyond")] = TABLE[("render", "empty")] = "render rect outside the film"
+TABLE[("camera_samples", "beyond")] = "camera_samples: rect outside the film"      # (an empty rect is camera_samples' empty answer)
+for _name, _what in PRECISION.items():
+    TABLE[(_name, "precision")] = f"{CALLS[_name][0]}: {_what} precision must match the handle"
+TABLE[("trace_closest", "precision")] = "ray/hit precision must match the handle"
+TABLE[("trace_any", "precision")] = "ray precision must match the handle"
+for _name in IDLE:
+    TABLE[(_name, "in flight")] = f"{CALLS[_name][0]}: {IN_FLIGHT}"
+TABLE[("render_bands_begin", "in flight")] = "render_bands_begin: the previous frame was not ended"
+
+VIOLATE = {"rank": dict(rank=2, world=2), "world": dict(rank=0, world=0), "beyond": dict(rect=(8, 8, 24, 24)), "empty": dict(rect=(4, 4, 4, 8)), "precision": {}, "in flight": {}}
+
+
+def _refused(r, name, what, message):
+    other = RRT_F64 if r.precision == RRT_F32 else RRT_F32
+    mine = r.precision, r.dtype
+    if what == "precision": r.precision, r.dtype = other, (np.float64 if other == RRT_F64 else np.float32)
+    try:
+        with pytest.raises(RrtError) as e:
+            CALLS[name][1](r, **VIOLATE[what])
+    finally:
+        r.precision, r.dtype = mine
+    assert type(e.value) is RrtError and str(e.value) == f"[{A.RRT_EINVAL}] {message}", (name, what, str(e.value))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", [RRT_F32, RRT_F64], ids=["f32", "f64"])
+def test_every_refusal_has_its_class_and_its_message(prec, workdir):
+    import torch
+    assert len(TABLE) == 2 * len(RANKED) + 2 * len(RECTS) + len(TILED) + 3 + len(PRECISION) + 2 + len(IDLE) + 1
+    sc = Scene.loads(*scenes.cfg3(workdir, xres=W, yres=H, nsamp=3, max_depth=5))
+    fresh = Renderer(sc, 0, prec)
+    want = fresh.render()
+    fresh.close()
+    assert want[..., :3].max() > 0
+
+    r = Renderer(sc, 0, prec)
+    r._frame = torch.zeros((H, W, 4), dtype=torch.float32 if prec == RRT_F32 else torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    for (name, what), message in TABLE.items():
+        if what != "in flight": _refused(r, name, what, message)
+    r.render_bands_begin(0, 1, r._frame.data_ptr())
+    for (name, what), message in TABLE.items():
+        if what == "in flight": _refused(r, name, what, message)
+    # the frame's own two calls take no notice of the frame in flight: they return
+    CALLS["render"][1](r)
+    CALLS["render_bands"][1](r)
+    r.render_end()
+    after = r.render()
+    r.close()
+    assert np.array_equal(after, want)

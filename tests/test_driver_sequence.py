@@ -2,8 +2,11 @@
 one guard for what a pass leaves set in the handle).
 
 The "handle is untouched" tests of test_aov.py, test_aov_follow.py, test_mattes.py and test_frame_aov.py each put one call between two frames. Here
-a frame, the feature buffers, the followed feature buffers, the mattes, the fused frame, the adaptive frame, the moments frame, a refused call and
-once more the followed buffers and the frame run on ONE handle, and each result is, bit for bit, what the same call gives on a fresh handle.
+a frame, the feature buffers, the followed feature buffers, the mattes, the fused frame, the adaptive frame, the moments frame, the passes frame,
+the ambient-occlusion planes, the frame and the radiance along caller-supplied rays, both ranks' bands, a refused call and once more the followed
+buffers and the frame run on ONE handle, and each result is, bit for bit, what the same call gives on a fresh handle. The caller-supplied rays are
+the scene's own camera samples of the whole film, taken once per precision from a handle of its own (camera_samples refuses more samples than
+max_paths slots) and read-only.
 
 Scene: aov_follow_scenes.mirror_floor at 32 x 24 (the mirror makes the follow levels run), Path integrator, Halton, 9 samples per pixel, under the
 box filter and under the Gaussian filter of test_aov_follow.py (the wide film window), both precisions. Every handle has max_paths = 1000 set
@@ -14,21 +17,28 @@ import numpy as np
 import pytest
 
 import aov_follow_scenes as FS
+import radiance_reference as RR
 from rs_ray_toy_amd import RRT_F32, RRT_F64, RRT_FIXED_BVH, Renderer, RrtError, Scene
 
 GAUSS = {"filter_type": "GaussianFilter", "radius": [1.5, 1.5], "alpha": 1.0}
 MAX_PATHS = 1000
 STAT_KEYS = ("camera_rays", "closest_queries", "any_queries", "tile_launches", "root_culled")
 
-# name -> the call; every call returns arrays (or nests of them) only
+# name -> the call on a handle r (s: the scene's own camera samples, radiance_reference.own_samples); every call returns arrays (or nests of them) only
 CALLS = {
-    "render": lambda r: r.render(),
-    "aov": lambda r: r.render_aov(),
-    "follow": lambda r: r.render_aov(follow=3),
-    "mattes": lambda r: r.render_mattes(ids="prim", slots=3),
-    "frame_aov": lambda r: r.render_frame_aov(),
-    "adaptive": lambda r: r.render_adaptive(min_samples=4, batch=2),
-    "moments": lambda r: r.render_moments(),
+    "render": lambda r, s: r.render(),
+    "aov": lambda r, s: r.render_aov(),
+    "follow": lambda r, s: r.render_aov(follow=3),
+    "mattes": lambda r, s: r.render_mattes(ids="prim", slots=3),
+    "frame_aov": lambda r, s: r.render_frame_aov(),
+    "adaptive": lambda r, s: r.render_adaptive(min_samples=4, batch=2),
+    "moments": lambda r, s: r.render_moments(),
+    "passes": lambda r, s: r.render_passes([(1, 0, 0), (1, 0, 1)]),      # the one light at every vertex, and at the first hit alone
+    "ao": lambda r, s: r.render_ao(n_samples=2),
+    "rays": lambda r, s: r.render_rays(RR.full_rect(r.scene), 1, RR.nsamp(r.scene), s["rays"], s["weight"], s["p_film"]),
+    "radiance": lambda r, s: r.radiance(s["rays"][:, :3], s["rays"][:, 3:], s["pixel"], s["sample_num"], weight=s["weight"]),
+    "bands0": lambda r, s: r.render_bands(0, 2),
+    "bands1": lambda r, s: r.render_bands(1, 2),
 }
 
 
@@ -61,24 +71,30 @@ def test_calls_in_sequence_are_calls_on_fresh_handles(prec, filt, workdir):
     sc = Scene.loads(cfg, root, flags=RRT_FIXED_BVH)
     names = [n for n in CALLS if not (n == "adaptive" and filt)]      # rrt_render_adaptive takes the box filter of radius 0.5 only
 
+    own = Renderer(sc, 0, prec)
+    s = RR.own_samples(own)
+    own.close()
+    for a in s.values(): a.setflags(write=False)
     want = {}
     for n in names:
         fresh = _handle(sc, prec)
-        want[n] = CALLS[n](fresh)
+        want[n] = CALLS[n](fresh, s)
         fresh.close()
     assert want["render"][..., :3].max() > 0 and want["aov"]["depth"][..., 2].max() > 0
     assert not np.array_equal(want["follow"]["depth"], want["aov"]["depth"])      # the follow levels ran
-    assert want["mattes"]["coverage"].max() > 0
+    assert want["mattes"]["coverage"].max() > 0 and want["ao"]["ao"].max() > 0 and want["radiance"].max() > 0 and want["rays"][..., :3].max() > 0
+    assert want["passes"][1][0][..., :3].max() > 0 and not np.array_equal(want["passes"][1][0], want["passes"][1][1])
+    assert want["bands0"][..., 3].max() > 0 and not np.array_equal(want["bands0"], want["bands1"])      # 24 rows: rank 0 has rows 0 .. 15, rank 1 the rest
 
     r = _handle(sc, prec)
     first, s_first = r.render(stats=True)
     assert s_first.closest_launches >= 8      # at least one launch per sample number: the pools hold max_paths slots
     _assert_equal("render", first, want["render"])
     for n in names[1:]:
-        _assert_equal(n, CALLS[n](r), want[n])
+        _assert_equal(n, CALLS[n](r, s), want[n])
     with pytest.raises(RrtError, match="render_aov: rect outside the film"):
         r.render_aov(rect=(0, 0, 33, 24))
-    _assert_equal("follow again", CALLS["follow"](r), want["follow"])
+    _assert_equal("follow again", CALLS["follow"](r, s), want["follow"])
     last, s_last = r.render(stats=True)
     r.close()
     _assert_equal("render again", last, want["render"])
