@@ -412,6 +412,62 @@ int rrt_radiance(rrt_handle*, const rrt_ray_samples* rays, size_t n, void* rgb4)
 int rrt_render_rays(rrt_handle*, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film,
                     void* film_xyzw, int film_mem, rrt_render_stats* stats /* may be NULL */);
 
+/* Irradiance and spherical-harmonic probes at caller-supplied points (no counterpart in the reference): what baking and probes consume - the
+ * irradiance at a surface point (a lightmap texel, a vertex, a sensor) or the SH projection of the radiance around a point in space - with
+ * the rays made on the device from each draw's own sampler stream and only sums leaving it. rrt_radiance hands out one Li per ray; here the
+ * caller ships 6 values per point instead of 6 per draw and gets 4 (or 4 + 27) per point back instead of 4 per draw.
+ *
+ * rrt_points: SoA, element type = the handle's precision, all arrays in `mem`.
+ *   px, py, pz: the points.
+ *   nx, ny, nz: RRT_IRR_COSINE: the surface normal, any non-zero finite length. RRT_IRR_SPHERE: the axis of the local frame; all three may
+ *               be NULL = the z axis. A point whose normal is zero or not finite is dead: all its draws add nothing.
+ *   pixel:      the sampler stream of point i, y << 16 | x inside the film; NULL: x = i % xres, y = (i / xres) % yres. Points may share a
+ *               pixel; they are then simply correlated.
+ * rrt_irr_params: NULL = {RRT_IRR_COSINE, offset 0}. offset is rounded to the handle's type.
+ *
+ * Draw j in [s0, s1), 1 <= s0 < s1 <= nsamp, of point i is the ray rrt_radiance would be given with (pixel_i, sample_num = j):
+ *   u    = the first two values of that stream, what rrt_camera_samples reports as dims5[0], dims5[1] of sample j of that pixel (the film
+ *          sample, which no point has a use for); the integrator continues at the dimensions past the camera's, so nothing is drawn twice
+ *   nn   = n / |n|,  (s, t) = coordinate_system(nn) (geometry.rs:1146-1161)
+ *   wl   = cosine_sample_hemisphere(u) (sampling.rs:270; a draw with wl.z == 0 is dead)  or  uniform_sample_sphere(u) (sampling.rs:233)
+ *   d    = normalize((s wl.x + t wl.y) + nn wl.z),  o = p + nn * offset,  t_max = inf, no start triangle, rx = ry = the ray
+ * and adds onto the caller's rows (handle precision, in points->mem; they start from what the buffers hold, draws in ascending j, plain adds):
+ *   sums4[4 i ..]         += { L_j.r, L_j.g, L_j.b, y_j^2 },  y = 0.212671 r + 0.715160 g + 0.072169 b
+ *   sh27[27 i + 3 k + c]  += L_j.c * Y_k(wl_j)   (RRT_IRR_SPHERE only, may be NULL), the real SH basis of bands 0 .. 2 at the LOCAL direction:
+ *     Y_0 = 0.28209479177387814          Y_1 = 0.4886025119029199 y        Y_2 = 0.4886025119029199 z
+ *     Y_3 = 0.4886025119029199 x         Y_4 = 1.0925484305920792 x y      Y_5 = 1.0925484305920792 y z
+ *     Y_6 = 0.31539156525252005 (3 z^2 - 1)   Y_7 = 1.0925484305920792 x z      Y_8 = 0.5462742152960396 (x^2 - y^2)
+ *   With n = NULL the local frame is coordinate_system of the z axis: local (x, y, z) = world (y, -x, z).
+ * So calls over [1, a) and [a, b) leave, bit for bit, what one call over [1, b) leaves, and the cut into pool-sized passes ("max_paths")
+ * changes no bit either. The caller scales: cosine mode E = pi / N * sums4[0..2], with sums4[3] the variance of its luminance follows;
+ * sphere mode coefficients 4 pi / N * sh27. AOIntegrator scenes add zeros, as rrt_radiance returns zeros there.
+ *
+ * rrt_irradiance_rays: the unit-test surface, as rrt_camera_samples is the camera's: od6[(i * (s1 - s0) + (j - s0)) * 6 ..] = {o, d} of every
+ * draw, handle precision, in points->mem; a dead draw writes six zeros. Nothing is traced.
+ *
+ * Both leave the handle as it was. Errors, the structs checked before the handle and everything the host can see before any device work:
+ * RRT_EINVAL for NULL arguments, a precision that is not the handle's, n == 0 or n > 2^31 - 1, a draw range outside [1, nsamp) or empty, a bad
+ * mode, a non-finite offset, sh27 given in cosine mode, NULL normals in cosine mode, a frame in flight, a pixel outside the film - for
+ * device-resident arrays that last check is made on the device before anything is traced, and nothing is written. RRT_EUNSUP for the
+ * StratifiedSampler (its first 2D value is a film sample inside its stratum, not an even cover of [0, 1)^2 by a pixel's draws); RRT_EUNSUP /
+ * RRT_EPANIC as rrt_render_rect gives for the scene.
+ * Not provided: a start-triangle exclusion per point (the offset is the tool), ray differentials, _begin / _end.
+ * Measured (tools/irradiance_time.py, profiles/irradiance_time.json; config 4, Path depth 8, fp32, 31 799 points x 64 cosine draws, everything in
+ * device memory, one MI355X): rrt_irradiance 2.71 ms against 4.58 ms for the same draws built in torch, sent through rrt_radiance and reduced in
+ * torch (0.59); rrt_radiance alone over those 2.04 M rays 2.63 ms (2.62 on the parent commit's build). k_irr_gen 42 us, k_irr_reduce 49 us. */
+enum { RRT_IRR_COSINE = 0, RRT_IRR_SPHERE = 1 };
+typedef struct rrt_points {
+  int32_t mem, precision;
+  const void *px, *py, *pz;
+  const void *nx, *ny, *nz;
+  const uint32_t *pixel;
+} rrt_points;
+typedef struct rrt_irr_params { int32_t mode; int32_t pad; double offset; } rrt_irr_params;
+int rrt_irradiance(rrt_handle*, const rrt_points* points, size_t n, uint64_t s0, uint64_t s1, const rrt_irr_params* params /* may be NULL */,
+                   void* sums4 /* n x 4 */, void* sh27 /* n x 27, RRT_IRR_SPHERE only, may be NULL */);
+int rrt_irradiance_rays(rrt_handle*, const rrt_points* points, size_t n, uint64_t s0, uint64_t s1, const rrt_irr_params* params /* may be NULL */,
+                        void* od6 /* [point][draw][6] */);
+
 /* Multi-GPU film partition: the same, for the rows of the interleaved 16-row tile bands b with
  * b % world == rank (tile height of integrator/mod.rs:55), rendered as one pixel set. Box filter: the ranks' films are
  * disjoint; wider filters: a sample's splat may land in a neighbour's rows of this rank's film. Either way summing

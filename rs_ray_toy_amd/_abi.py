@@ -148,6 +148,17 @@ class RaySamples(C.Structure):
                 + [(k, C.c_void_p * 3) for k in ("rxo", "rxd", "ryo", "ryd")] + [("pixel", C.c_void_p), ("sample_num", C.c_void_p)])
 
 
+RRT_IRR_COSINE, RRT_IRR_SPHERE = 0, 1
+
+
+class Points(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32)] + [(k, C.c_void_p) for k in ("px", "py", "pz", "nx", "ny", "nz", "pixel")]
+
+
+class IrrParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("pad", C.c_int32), ("offset", C.c_double)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("camera_samples", C.c_uint64), ("camera_rays", C.c_uint64), ("closest_queries", C.c_uint64),
                 ("any_queries", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
@@ -220,6 +231,8 @@ PROTOTYPES = {
     "rrt_radiance": (C.c_int, [C.c_void_p, C.POINTER(RaySamples), C.c_size_t, C.c_void_p]),
     "rrt_render_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, C.POINTER(RaySamples), C.c_void_p, C.c_void_p, C.c_int,
                                   C.POINTER(RenderStats)]),
+    "rrt_irradiance": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(IrrParams), C.c_void_p, C.c_void_p]),
+    "rrt_irradiance_rays": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(IrrParams), C.c_void_p]),
     "rrt_render_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_render_bands_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rrt_render_end": (C.c_int, [C.c_void_p]),

@@ -264,6 +264,70 @@ class Renderer:
         rs.pixel, rs.sample_num = pixel_ptr, sample_num_ptr
         _check(A.lib().rrt_radiance(self._h, C.byref(rs), n, rgb4_ptr))
 
+    # irradiance and SH probes at caller-supplied points (rrt_irradiance, rrt_irradiance_rays)
+    _IRR_MODES = {"cosine": A.RRT_IRR_COSINE, "sphere": A.RRT_IRR_SPHERE}
+
+    def _irr_params(self, mode, offset):
+        if mode not in self._IRR_MODES:
+            raise ValueError(f'irradiance: mode is "cosine" or "sphere", not {mode!r}')
+        return A.IrrParams(self._IRR_MODES[mode], 0, float(offset))
+
+    def _points(self, p, n, pixel):
+        """rrt_points over host arrays: p (m, 3); n (m, 3) or None; pixel None, (m, 2) of (x, y) or (m,) packed y << 16 | x. Returns the struct and
+        the arrays it points into (keep them alive for the call)."""
+        p = np.asarray(p)
+        keep = [np.ascontiguousarray(p[:, k], self.dtype) for k in range(3)]
+        if n is not None:
+            n = np.asarray(n)
+            keep += [np.ascontiguousarray(n[:, k], self.dtype) for k in range(3)]
+        pts = A.Points(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in keep])
+        if pixel is not None:
+            pixel = np.asarray(pixel)
+            if pixel.ndim == 2:
+                pixel = (pixel[:, 1].astype(np.uint32) << 16) | pixel[:, 0].astype(np.uint32)
+            keep.append(np.ascontiguousarray(pixel, np.uint32))
+            pts.pixel = keep[-1].ctypes.data
+        return pts, keep
+
+    def _draw_range(self, s0, s1):
+        return int(s0), int(self.scene.desc.sampler.samples_per_pixel if s1 is None else s1)
+
+    def irradiance(self, p, n, s0=1, s1=None, pixel=None, offset=0.0, mode="cosine", sums=None, sh=None):
+        """rrt_irradiance over host arrays: the sums of draws [s0, s1) (s1 None = nsamp) of the scene's integrator at points p (m, 3) with normals
+        n (m, 3; None in sphere mode = the z axis), rays made on the device. mode "cosine": returns sums (m, 4) = {sum L.rgb, sum y^2}; mode
+        "sphere": returns (sums, sh) with sh (m, 27) where sh is True or an array. `sums` / `sh` arrays of the renderer's dtype are added to
+        (+=, draw ranges can be split over calls); see resolve_irradiance and resolve_sh for the scaling."""
+        m = len(np.asarray(p))
+        s0, s1 = self._draw_range(s0, s1)
+        pts, keep = self._points(p, n, pixel)
+        prm = self._irr_params(mode, offset)
+        if sums is None:
+            sums = np.zeros((m, 4), self.dtype)
+        if sh is True:
+            sh = np.zeros((m, 27), self.dtype)
+        assert sums.dtype == self.dtype and sums.flags.c_contiguous and sums.shape == (m, 4)
+        assert sh is None or (sh.dtype == self.dtype and sh.flags.c_contiguous and sh.shape == (m, 27))
+        _check(A.lib().rrt_irradiance(self._h, C.byref(pts), m, s0, s1, C.byref(prm), sums.ctypes.data, None if sh is None else sh.ctypes.data))
+        return sums if sh is None else (sums, sh)
+
+    def irradiance_rays(self, p, n, s0=1, s1=None, pixel=None, offset=0.0, mode="cosine"):
+        """rrt_irradiance_rays: the rays rrt_irradiance traces, (m, s1 - s0, 6) origin + unit direction in the renderer's dtype; a dead draw is
+        six zeros."""
+        m = len(np.asarray(p))
+        s0, s1 = self._draw_range(s0, s1)
+        pts, keep = self._points(p, n, pixel)
+        prm = self._irr_params(mode, offset)
+        od = np.zeros((m, max(0, s1 - s0), 6), self.dtype)
+        _check(A.lib().rrt_irradiance_rays(self._h, C.byref(pts), m, s0, s1, C.byref(prm), od.ctypes.data))
+        return od
+
+    def irradiance_device(self, p_ptrs3, n_ptrs3, m, s0, s1, sums_ptr, sh_ptr=None, pixel_ptr=None, offset=0.0, mode="cosine"):
+        """rrt_irradiance on device-resident arrays (raw pointers): p_ptrs3 = px, py, pz; n_ptrs3 = nx, ny, nz or None; sums_ptr: m * 4 values,
+        sh_ptr: m * 27 values or None; both are added to."""
+        pts = A.Points(A.RRT_MEM_DEVICE, self.precision, *p_ptrs3, *(n_ptrs3 if n_ptrs3 is not None else (None, None, None)), pixel_ptr)
+        prm = self._irr_params(mode, offset)
+        _check(A.lib().rrt_irradiance(self._h, C.byref(pts), m, s0, s1, C.byref(prm), sums_ptr, sh_ptr))
+
     def render_rays_device(self, rect, s0, s1, ptrs6, weight_ptr, p_film_ptr, film_ptr, stats=True):
         """rrt_render_rays on device-resident samples into a device film (+=)."""
         rs = A.RaySamples(A.RRT_MEM_DEVICE, self.precision, *ptrs6, weight_ptr)
@@ -706,6 +770,26 @@ def write_ao_png(path, planes):
     rgba[..., :3] = np.clip(np.nan_to_num(grey) * 255.0 + 0.5, 0.0, 255.0).astype(np.uint8)[..., None]
     rgba[..., 3] = 255
     write_png(path, rgba)
+
+
+def resolve_irradiance(sums, n_draws):
+    """The sums of Renderer.irradiance (cosine mode) over n_draws draws per point -> dict(E (m, 3) = pi / N * sum L: the irradiance, stderr (m,):
+    the standard error of E's luminance, pi * sqrt((sum y^2 / N - mean_y^2) / (N - 1)) (0 where N < 2)). Dead draws count: they are draws
+    that carried nothing."""
+    s = np.asarray(sums, np.float64)
+    N = float(n_draws)
+    E = np.pi / N * s[..., :3]
+    mean_y = (s[..., :3] @ np.array([0.212671, 0.715160, 0.072169])) / N
+    var = np.maximum(0.0, s[..., 3] / N - mean_y * mean_y)
+    stderr = np.pi * np.sqrt(var / (N - 1.0)) if N >= 2 else np.zeros_like(mean_y)
+    return dict(E=E, stderr=stderr)
+
+
+def resolve_sh(sh, n_draws):
+    """The sh sums of Renderer.irradiance (sphere mode) over n_draws draws per point -> (m, 9, 3): the coefficients 4 pi / N * sum L Y_k of the
+    radiance around each point, bands 0 .. 2 in rrt.h's order, in the point's local frame."""
+    s = np.asarray(sh, np.float64)
+    return (4.0 * np.pi / float(n_draws)) * s.reshape(s.shape[:-1] + (9, 3))
 
 
 def resolve_moments(m):

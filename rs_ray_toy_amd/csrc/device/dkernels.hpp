@@ -837,6 +837,176 @@ __global__ void __launch_bounds__(kBlock) k_radiance_out(Pools<R> p, typename Ve
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Irradiance and SH probes at caller-supplied points (rrt_irradiance, rrt_irradiance_rays): the third producer of the pool state the integrators
+// consume - k_irr_gen makes the rays of a pass in registers from the points and the draws' own sampler streams - and the third consumer of L,
+// k_irr_reduce, which adds a point's draws up on the device.
+// ------------------------------------------------------------------------------------------------------------
+// rrt_points on the device (staged there for a host-memory call). Pixel pl of a pass is point base + pl, sample sl is draw pd.s_begin + sl.
+template <typename R>
+struct IrrPoints {
+  const R *p[3], *n[3];       // n all null (sphere mode): the z axis
+  const uint32_t* pixel;      // null: x = i % xres, y = (i / xres) % yres
+  uint64_t base;
+  R offset;
+  uint32_t mode;              // RRT_IRR_COSINE / RRT_IRR_SPHERE
+  uint32_t s0, ns_all;        // the call's first draw and its number of draws: the [point][draw] layout of rrt_irradiance_rays
+};
+// local direction of a draw from the first two values of its sampler stream (the camera sample's film dimensions, which no point has a use for)
+template <typename R>
+RRT_DEV V3<R> irr_local_dir(const SceneDev<R>& s, uint32_t mode, uint32_t index) {
+  const R u0 = to_real<R>(halton_dim(s, index, 0)), u1 = to_real<R>(halton_dim(s, index, 1));
+  return mode == 1u ? uniform_sample_sphere(u0, u1) : cosine_sample_hemisphere(u0, u1);
+}
+// One thread per point, points on the fast lanes: the point's six values (coalesced loads), its unit normal, frame and Halton offset are worked
+// out once and serve kIngestTiles consecutive draws, tile k of the workgroup = draw blockIdx.y * kIngestTiles + k of its 256 points. Slot layout
+// and queue reservation are k_ingest_rays' (slot = draw * npix + point; one atomic per workgroup for all its tiles, see there for what per-tile
+// atomics cost). od6 set (rrt_irradiance_rays): the rays are written out as [point][draw][6], a dead draw as zeros, and no pool is touched.
+// check_only: nothing but the range check of `pixel`, which is made in every launch - a point that fails it is dead.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_irr_gen(SceneDev<R> s, Pools<R> p, PassDesc pd, IrrPoints<R> in, int enqueue, int check_only, R* od6) {
+  const uint32_t pl = blockIdx.x * kBlock + threadIdx.x;
+  __shared__ uint32_t push_lds[kBlock / 64 + 2];
+  bool live = false;
+  uint32_t index0 = 0;
+  V3<R> org, nn(R(0), R(0), R(1)), sv, tv;
+  if (pl < pd.npix) {
+    const size_t i = (size_t)in.base + pl;
+    uint32_t px, py;
+    bool ok = true;
+    if (in.pixel) {
+      const uint32_t pw = in.pixel[i];
+      px = pw & 0xffffu; py = pw >> 16;
+      ok = px < (uint32_t)s.xres && py < (uint32_t)s.yres;
+      if (!ok) atomicOr(s.err, (uint32_t)ERR_INGEST);
+    } else {
+      px = (uint32_t)(i % (size_t)s.xres); py = (uint32_t)((i / (size_t)s.xres) % (size_t)s.yres);
+    }
+    if (!check_only && ok) {
+      live = true;
+      if (in.n[0]) {   // any non-zero finite length: a length whose square leaves the type's range is brought into it first
+        V3<R> nv(in.n[0][i], in.n[1][i], in.n[2][i]);
+        live = isfinite(nv.x) && isfinite(nv.y) && isfinite(nv.z);
+        R l2 = len2(nv);
+        if (live && !(l2 >= R(1e-30) && isfinite(l2))) {
+          const R m = rmax(rmax(rabs(nv.x), rabs(nv.y)), rabs(nv.z));
+          live = m > R(0);
+          nv = nv / m;
+        }
+        nn = nv / len(nv);
+      }
+      if (live) {
+        coordinate_system(nn, &sv, &tv);
+        org = V3<R>(in.p[0][i], in.p[1][i], in.p[2][i]) + nn * in.offset;
+        index0 = halton_pixel_offset(s, px, py);
+      }
+    }
+  }
+  if (check_only) return;
+  bool alive[kIngestTiles];
+  uint32_t slot[kIngestTiles], index[kIngestTiles], rank[kIngestTiles], total = 0;
+  V3<R> d[kIngestTiles];
+#pragma unroll
+  for (uint32_t k = 0; k < kIngestTiles; k++) {
+    const uint32_t sl = blockIdx.y * kIngestTiles + k;
+    alive[k] = false; slot[k] = 0; index[k] = 0;
+    if (pl < pd.npix && sl < pd.ns) {
+      slot[k] = sl * pd.npix + pl;
+      if (live) {
+        index[k] = index0 + (pd.s_begin + sl) * s.stride;   // as k_raygen forms it (HaltonSampler: the host refuses the StratifiedSampler)
+        const V3<R> wl = irr_local_dir(s, in.mode, index[k]);
+        alive[k] = in.mode == 1u || wl.z != R(0);
+        d[k] = vnormalize(V3<R>((sv.x * wl.x + tv.x * wl.y) + nn.x * wl.z, (sv.y * wl.x + tv.y * wl.y) + nn.y * wl.z, (sv.z * wl.x + tv.z * wl.y) + nn.z * wl.z));
+      }
+      if (od6) {
+        R* const r6 = od6 + 6 * (((size_t)in.base + pl) * in.ns_all + ((pd.s_begin + sl) - in.s0));
+        r6[0] = alive[k] ? org.x : R(0); r6[1] = alive[k] ? org.y : R(0); r6[2] = alive[k] ? org.z : R(0);
+        r6[3] = alive[k] ? d[k].x : R(0); r6[4] = alive[k] ? d[k].y : R(0); r6[5] = alive[k] ? d[k].z : R(0);
+      } else {
+        p.weight[slot[k]] = alive[k] ? R(1) : R(0);
+        if (alive[k]) {   // (a dead draw's index and radiance record are never read: the queue, k_irr_reduce)
+          p.hindex[slot[k]] = index[k];
+          p.L[slot[k]] = mk4<R>(R(0), R(0), R(0), R(0));
+          if (p.rdx_o) {   // no differentials: rx = ry = the ray
+            p.rdx_o[slot[k]] = mk4<R>(org.x, org.y, org.z, R(0)); p.rdx_d[slot[k]] = mk4<R>(d[k].x, d[k].y, d[k].z, R(0));
+            p.rdy_o[slot[k]] = mk4<R>(org.x, org.y, org.z, R(0)); p.rdy_d[slot[k]] = mk4<R>(d[k].x, d[k].y, d[k].z, R(0));
+          }
+        }
+      }
+    }
+    if (!od6) {   // (block-uniform) rank among the workgroup's live draws: tiles in turn, block order inside a tile
+      uint32_t n_tile;
+      rank[k] = total + block_rank(alive[k], push_lds, &n_tile);
+      total += n_tile;
+    }
+  }
+  if (od6) return;
+  uint32_t* const counter = &p.counters[enqueue ? C_ACTIVE : C_CAMERA_RAYS];
+  if (threadIdx.x == 0) push_lds[kBlock / 64 + 1] = total ? atomicAdd(counter, total) : 0u;
+  __syncthreads();
+  const uint32_t first = push_lds[kBlock / 64 + 1];
+  if (!enqueue) return;
+#pragma unroll
+  for (uint32_t k = 0; k < kIngestTiles; k++) {
+    if (!alive[k]) continue;
+    const uint32_t q = first + rank[k];
+    p.q_active[q] = QEnt{slot[k], s.cam_db, index[k], 0u};   // the camera's dimensions count as consumed, bounce 0
+    p.path[q] = mk4<R>(R(1), R(1), R(1), R(1));
+    store_ray<R>(p.ray_o, p.ray_d, q, org, V3<R>(), d[k], Const<R>::inf, -1);
+  }
+}
+
+// The nine real spherical harmonics of bands 0 .. 2 at a unit vector, in the order and with the constants rrt.h writes out
+template <typename R>
+RRT_DEV void sh9(V3<R> w, R y[9]) {
+  y[0] = R(0.28209479177387814);
+  y[1] = R(0.4886025119029199) * w.y;
+  y[2] = R(0.4886025119029199) * w.z;
+  y[3] = R(0.4886025119029199) * w.x;
+  y[4] = R(1.0925484305920792) * (w.x * w.y);
+  y[5] = R(1.0925484305920792) * (w.y * w.z);
+  y[6] = R(0.31539156525252005) * (R(3) * (w.z * w.z) - R(1));
+  y[7] = R(1.0925484305920792) * (w.x * w.z);
+  y[8] = R(0.5462742152960396) * (w.x * w.x - w.y * w.y);
+}
+// One thread per point of the pass: the caller's row, then the pass's draws of the point in draw order - L[draw * npix + point], one 128-bit
+// (f64: 256-bit) load per lane, contiguous across the wave - and the row written back: {sum r, sum g, sum b, sum y^2} with plain adds in the
+// handle's type, so a row holds the same bits however the draws were cut into passes and calls. sh27 set (sphere mode): the draw's local
+// direction again from its own stream, and 27 more sums held in registers. A dead draw (weight 0) adds nothing.
+// ISA (gfx950): no scratch in either precision - the 27 sums and the 9 basis values stay in registers (the loops over them are unrolled): 67 VGPRs
+// in fp32, 120 in f64, private segment 0 (k_irr_gen: 60 / 96 VGPRs, no scratch either).
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_irr_reduce(SceneDev<R> s, Pools<R> p, PassDesc pd, uint64_t base, R* sums4, R* sh27) {
+  const uint32_t pl = blockIdx.x * kBlock + threadIdx.x;
+  if (pl >= pd.npix) return;
+  R* const row = sums4 + 4 * ((size_t)base + pl);
+  R a0 = row[0], a1 = row[1], a2 = row[2], a3 = row[3];
+  R sh[27];
+  R* const shrow = sh27 ? sh27 + 27 * ((size_t)base + pl) : nullptr;
+  if (shrow) {
+#pragma unroll
+    for (int k = 0; k < 27; k++) sh[k] = shrow[k];
+  }
+  for (uint32_t sl = 0; sl < pd.ns; sl++) {
+    const uint32_t slot = sl * pd.npix + pl;
+    if (!(p.weight[slot] > R(0))) continue;
+    const typename Vec4T<R>::type l = p.L[slot];
+    const R y = Rgb<R>(l.x, l.y, l.z).y();
+    a0 += l.x; a1 += l.y; a2 += l.z; a3 += y * y;
+    if (shrow) {
+      R yk[9];
+      sh9(irr_local_dir(s, 1u, p.hindex[slot]), yk);
+#pragma unroll
+      for (int k = 0; k < 9; k++) { sh[3 * k] += l.x * yk[k]; sh[3 * k + 1] += l.y * yk[k]; sh[3 * k + 2] += l.z * yk[k]; }
+    }
+  }
+  row[0] = a0; row[1] = a1; row[2] = a2; row[3] = a3;
+  if (shrow) {
+#pragma unroll
+    for (int k = 0; k < 27; k++) shrow[k] = sh[k];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Shading
 // ------------------------------------------------------------------------------------------------------------
 template <typename R>

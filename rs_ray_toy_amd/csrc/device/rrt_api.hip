@@ -110,6 +110,45 @@ int rrt_radiance(rrt_handle* h, const rrt_ray_samples* rays, size_t n, void* rgb
   return guarded([&]() { h->impl->radiance(rays, n, rgb4); });
 }
 
+namespace {
+// rrt_irradiance and rrt_irradiance_rays: the caller's own structs first (wrong whichever handle they come with), everything the host can see
+// before any device work, each with its own message; then the handle's checks (precision, a frame in flight, the draw range, the pixels)
+int irradiance_entry(const char* fn, rrt_handle* h, const rrt_points* pts, size_t n, uint64_t s0, uint64_t s1, const rrt_irr_params* params, bool rays, void* sums4, void* sh27,
+                     void* od6) {
+  const std::string name(fn);
+  auto bad = [&](const char* what) { rrt::set_last_error(name + ": " + what); return (int)RRT_EINVAL; };
+  if (!pts) return bad("null point description (rrt_points)");
+  if (pts->mem != RRT_MEM_HOST && pts->mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (!pts->px || !pts->py || !pts->pz) return bad("null point array");
+  const int n_normals = (pts->nx != nullptr) + (pts->ny != nullptr) + (pts->nz != nullptr);
+  if (n_normals != 0 && n_normals != 3) return bad("normals partly set (all three arrays or none)");
+  const int mode = params ? params->mode : (int)RRT_IRR_COSINE;
+  const double offset = params ? params->offset : 0.0;
+  if (mode != RRT_IRR_COSINE && mode != RRT_IRR_SPHERE) return bad("bad mode (RRT_IRR_COSINE or RRT_IRR_SPHERE)");
+  if (!std::isfinite(offset)) return bad("offset must be finite");
+  if (mode == RRT_IRR_COSINE && n_normals == 0) return bad("null normals in cosine mode (the hemisphere needs its axis)");
+  if (rays) {
+    if (!od6) return bad("null output");
+  } else {
+    if (!sums4) return bad("null output (sums4)");
+    if (sh27 && mode != RRT_IRR_SPHERE) return bad("sh27 is a sphere-mode output (mode is RRT_IRR_COSINE)");
+  }
+  if (n == 0) return bad("n must be > 0");
+  if (n > 0x7fffffffu) return bad("batch too large");
+  if (s0 < 1 || s0 >= s1) return bad("draw range outside [1, nsamp) or empty");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->irradiance(fn, pts, n, s0, s1, mode, offset, sums4, sh27, od6); });
+}
+}  // namespace
+
+int rrt_irradiance(rrt_handle* h, const rrt_points* pts, size_t n, uint64_t s0, uint64_t s1, const rrt_irr_params* params, void* sums4, void* sh27) {
+  return irradiance_entry("rrt_irradiance", h, pts, n, s0, s1, params, false, sums4, sh27, nullptr);
+}
+
+int rrt_irradiance_rays(rrt_handle* h, const rrt_points* pts, size_t n, uint64_t s0, uint64_t s1, const rrt_irr_params* params, void* od6) {
+  return irradiance_entry("rrt_irradiance_rays", h, pts, n, s0, s1, params, true, nullptr, nullptr, od6);
+}
+
 int rrt_render_rays(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_xyzw, int film_mem,
                     rrt_render_stats* stats) {
   if (const int rc = ray_samples_check("rrt_render_rays", rays, false); rc != RRT_OK) return rc;

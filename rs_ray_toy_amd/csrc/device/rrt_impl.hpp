@@ -45,6 +45,8 @@ struct HandleBase {
   virtual void camera_samples(const int32_t rect[4], uint64_t s0, uint64_t s1, double* dims5, double* ray_od6, double* weight) = 0;
   virtual void render_rect(const int32_t rect[4], void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void radiance(const rrt_ray_samples* rays, size_t n, void* rgb4) = 0;
+  // rrt_irradiance (od6 NULL; sh27 may be NULL) and rrt_irradiance_rays (od6 set, sums4 and sh27 NULL) under the name `who`
+  virtual void irradiance(const char* who, const rrt_points* pts, size_t n, uint64_t s0, uint64_t s1, int mode, double offset, void* sums4, void* sh27, void* od6) = 0;
   virtual void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film, int film_mem, rrt_render_stats* stats) = 0;   // p_film in rays->mem
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
@@ -473,6 +475,97 @@ class Handle : public HandleBase {
       HIP_CHECK(hipGetLastError());
     }
     if (host) HIP_CHECK(hipMemcpyAsync(rgb4, out_stage.p, n * sizeof(V4), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    HIP_CHECK(hipStreamSynchronize(st2_));
+    check_device_errors();
+  }
+  // ---- irradiance and SH probes at caller-supplied points: rrt_irradiance, rrt_irradiance_rays ---------------------------------------------------
+  // radiance() with k_irr_gen in place of k_ingest_rays and k_irr_reduce in place of k_radiance_out: the rays are made on the device and only sums
+  // leave it. A pass holds whole draw ranges of as many points as the pools take, or, where one range exceeds the pools, a sub-range of one point's
+  // draws; the reducer adds a pass's draws onto the caller's row, so the cut changes no bit.
+  void launch_irr_gen(const PassDesc& pd, const IrrPoints<R>& in, int check_only, R* od6) {
+    const dim3 g((pd.npix + kBlock - 1) / kBlock, check_only ? 1u : (pd.ns + kIngestTiles - 1) / kIngestTiles);
+    const int enqueue = desc_.integrator.type != RRT_INT_AO ? 1 : 0;
+    hipLaunchKernelGGL((k_irr_gen<R>), g, dim3(kBlock), 0, st_, scene_, pool_, pd, in, enqueue, check_only, od6);
+    if (enqueue && !check_only && !od6) hipLaunchKernelGGL(k_ingest_count, dim3(1), dim3(1), 0, st_, counters_.p);
+    HIP_CHECK(hipGetLastError());
+  }
+  void irradiance(const char* who_c, const rrt_points* pts, size_t n, uint64_t s0, uint64_t s1, int mode, double offset, void* sums4, void* sh27, void* od6_user) override {
+    const std::string who(who_c);
+    check_args(who, kWhenIdle, Prec{"point", pts->precision});
+    const rrt_film& f = desc_.film;
+    if (s0 < 1 || s1 > desc_.sampler.samples_per_pixel || s0 >= s1) throw std::invalid_argument(who + ": draw range outside [1, nsamp) or empty");
+    // the StratifiedSampler's first 2D value is the film sample of its stratum, not a point of [0, 1)^2 that the draws of a pixel cover evenly
+    if (desc_.sampler.type == RRT_SAMPLER_STRATIFIED) throw UnsupportedError(who + " under the StratifiedSampler (a draw's direction is the stream's first 2D value: use the HaltonSampler)");
+    const bool host = pts->mem != RRT_MEM_DEVICE;
+    if (host && pts->pixel) {   // device-resident arrays: the same check by k_irr_gen, below
+      for (size_t i = 0; i < n; i++) {
+        const uint32_t pw = pts->pixel[i];
+        if ((int32_t)(pw & 0xffffu) >= f.xres || (int32_t)(pw >> 16) >= f.yres) throw std::invalid_argument(who + ": pixel outside the film (point " + std::to_string(i) + ")");
+      }
+    }
+    device_prologue(/*film=*/false);
+    RaysPassState guard(this);
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
+    if (totals_.n == 0) totals_.alloc(12);
+    HIP_CHECK(hipMemsetAsync(totals_.p, 0, 12 * sizeof(unsigned long long), st_));
+    const size_t ns_all = (size_t)(s1 - s0);
+    const size_t cap = pool_slots(n * ns_all);
+    if (!od6_user) ensure_pools(cap);
+    // the caller's arrays as the kernels take them: the pointers themselves for device memory, else copies
+    const void* arr[6] = {pts->px, pts->py, pts->pz, pts->nx, pts->ny, pts->nz};
+    const int n_arr = pts->nx ? 6 : 3;
+    const uint32_t* pixel = pts->pixel;
+    DevBuf<R> stage_r, stage_out;
+    DevBuf<uint32_t> stage_u;
+    if (host) {
+      stage_r.alloc((size_t)n_arr * n);
+      for (int k = 0; k < n_arr; k++) { HIP_CHECK(hipMemcpyAsync(stage_r.p + (size_t)k * n, arr[k], n * sizeof(R), hipMemcpyHostToDevice, st_)); arr[k] = stage_r.p + (size_t)k * n; }
+      if (pixel) { stage_u.alloc(n); HIP_CHECK(hipMemcpyAsync(stage_u.p, pixel, n * sizeof(uint32_t), hipMemcpyHostToDevice, st_)); pixel = stage_u.p; }
+    }
+    IrrPoints<R> in{};
+    for (int k = 0; k < 3; k++) { in.p[k] = (const R*)arr[k]; in.n[k] = n_arr == 6 ? (const R*)arr[3 + k] : nullptr; }
+    in.pixel = pixel; in.offset = (R)offset; in.mode = (uint32_t)mode; in.s0 = (uint32_t)s0; in.ns_all = (uint32_t)ns_all;
+    const PassDesc whole{0, 0, 1, 0u, (uint32_t)n, (uint32_t)s0, 1u, 1u << 30, 1u, 0u, 0u};
+    if (!host && pixel) {
+      launch_irr_gen(whole, in, 1, nullptr);
+      if (ingest_refused()) {
+        HIP_CHECK(hipMemsetAsync(counters_.p + C_ERROR, 0, sizeof(uint32_t), st_));
+        throw std::invalid_argument(who + ": a pixel outside the film");
+      }
+    }
+    // outputs: the caller's own rows in device memory, else copies that start from what the caller's rows hold
+    const size_t n_sums = od6_user ? 0 : 4 * n, n_sh = sh27 ? 27 * n : 0, n_od6 = od6_user ? 6 * n * ns_all : 0;
+    R *d_sums = (R*)sums4, *d_sh = (R*)sh27, *d_od6 = (R*)od6_user;
+    if (host) {
+      stage_out.alloc(n_sums + n_sh + n_od6);
+      d_sums = stage_out.p; d_sh = sh27 ? stage_out.p + n_sums : nullptr; d_od6 = od6_user ? stage_out.p : nullptr;
+      if (n_sums) HIP_CHECK(hipMemcpyAsync(d_sums, sums4, n_sums * sizeof(R), hipMemcpyHostToDevice, st_));
+      if (n_sh) HIP_CHECK(hipMemcpyAsync(d_sh, sh27, n_sh * sizeof(R), hipMemcpyHostToDevice, st_));
+    }
+    // draws per pass (the launch grid's second dimension counts kIngestTiles of them), points per pass
+    const size_t dpc = std::min<size_t>({ns_all, cap, (size_t)kIngestTiles * 65535u});
+    const size_t ppc = std::max<size_t>(1, std::min(n, cap / dpc));
+    FrameRec fr;   // no statistics: no events
+    for (size_t p0 = 0; p0 < n; p0 += ppc) {
+      for (uint64_t sb = s0; sb < s1; sb += dpc) {
+        PassDesc pd = whole;
+        pd.npix = (uint32_t)std::min(ppc, n - p0);
+        pd.s_begin = (uint32_t)sb; pd.ns = (uint32_t)std::min<uint64_t>(dpc, s1 - sb);
+        in.base = p0;
+        if (od6_user) { launch_irr_gen(pd, in, 0, d_od6); continue; }
+        hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 2);
+        launch_irr_gen(pd, in, 0, nullptr);
+        pass_integrate(pd, 0u, fr);
+        hipLaunchKernelGGL((k_irr_reduce<R>), dim3((pd.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, scene_, pool_, pd, (uint64_t)p0, d_sums, d_sh);
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    if (host) {
+      if (n_sums) HIP_CHECK(hipMemcpyAsync(sums4, d_sums, n_sums * sizeof(R), hipMemcpyDeviceToHost, st_));
+      if (n_sh) HIP_CHECK(hipMemcpyAsync(sh27, d_sh, n_sh * sizeof(R), hipMemcpyDeviceToHost, st_));
+      if (n_od6) HIP_CHECK(hipMemcpyAsync(od6_user, d_od6, n_od6 * sizeof(R), hipMemcpyDeviceToHost, st_));
+    }
     HIP_CHECK(hipStreamSynchronize(st_));
     HIP_CHECK(hipStreamSynchronize(st2_));
     check_device_errors();
