@@ -468,6 +468,68 @@ int rrt_irradiance(rrt_handle*, const rrt_points* points, size_t n, uint64_t s0,
 int rrt_irradiance_rays(rrt_handle*, const rrt_points* points, size_t n, uint64_t s0, uint64_t s1, const rrt_irr_params* params /* may be NULL */,
                         void* od6 /* [point][draw][6] */);
 
+/* Surface records and lightmap sites (no counterpart in the reference): where the surfaces are, and the world-space point, normal, tangent,
+ * texture coordinate and reflectance at a place on a primitive - the step before rrt_irradiance. rrt_trace_closest stops at (t, prim, u, v);
+ * these calls hand out the interaction the shading kernels rebuild from such a record (prim_order, Q13, kept and flattened instance
+ * transforms, get_uvs' defaults and a sphere's root branch are the library's business, not the caller's). The chain atlas -> sites -> records
+ * -> rrt_irradiance stays in device memory: px .. pz, nx .. nz of a record set ARE an rrt_points, and a dead record has a zero normal, which
+ * rrt_irradiance defines as "adds nothing", so nothing is compacted on the way.
+ *
+ * rrt_surface: SoA, element type = the handle's precision, all arrays in `mem`. The groups are {px, py, pz}, {nx, ny, nz}, {sx, sy, sz},
+ * {tu, tv}, {rho_r, rho_g, rho_b}, {t}, {prim, material}; each is all NULL (not produced, and not computed) or all set. Arrays are overwritten.
+ *   p:    the point shading starts its spawned rays from. RRT_F64: o + d t. RRT_F32: the barycentric point on the stored triangle
+ *         (p0 + ((p1 - p0) u + (p2 - p0) v), the unevaluated sum p_hi + p_lo of DESIGN.md rounded once), taken through the instance transform
+ *         where the handle kept one; a sphere's point is Sphere::intersect's.
+ *   n:    rrt_render_aov's n: the geometric normal after the instance transform, normalised, not turned towards anything, before any bump_map.
+ *   s:    normalize(GEOMETRIC dpdu) after the instance transform: the s of rrt_render_ao's frame.
+ *   uv:   the interaction's uv: the mesh uv or get_uvs' (0,0), (1,0), (1,1), interpolated; a sphere's own parameterisation.
+ *   rho:  rrt_render_aov's rho table, textured parameters evaluated at the point with zero differentials.
+ *   t:    rays form: what rrt_trace_closest reports (t_max unchanged on a miss); sites form: 0.
+ *   prim, material: index into prim_order as rrt_hits.prim / index into materials. A DEAD record (a miss, a site with prim == -1) has
+ *         prim = material = -1 and zeros everywhere else (t as above).
+ * rrt_surface_rays: the rays are packed and traced exactly as rrt_trace_closest does it (skip_prim and tmax included): t and prim are, bit for
+ * bit, what that call returns, and record i is the interaction of hit i. out->mem must equal rays->mem.
+ * rrt_surface_at: a site is (prim, b1, b2) with the barycentrics of rrt_hits.u / .v: p = p0 + ((p1 - p0) b1 + (p2 - p0) b2) in the space the
+ * handle stores the triangle in, then through the instance transform where the handle kept one; n, s, uv, rho and material as for a hit at those
+ * barycentrics. Barycentrics outside the triangle extrapolate its plane. prim == -1 is "no site": a dead record. Refused (RRT_EINVAL): any other
+ * index outside [0, n_prim_order), a sphere (its record needs the ray), a non-finite barycentric - host arrays are checked before any device
+ * work, device arrays by a checking launch over the whole batch before anything is written. out->mem must equal sites->mem.
+ * Both leave the handle as it was (a frame rendered before and after is the same frame). Errors, the structs checked before the handle:
+ * RRT_EINVAL for NULL arguments, a bad mem, a partly set group, all groups NULL, a precision that is not the handle's, n == 0 or n > 2^31 - 1, a
+ * frame in flight; RRT_EUNSUP / RRT_EPANIC as rrt_render_aov gives for the scene (primitives.rs:66, an ImageTexture lookup out of bounds).
+ *
+ * rrt_atlas_sites: which triangle, at which barycentrics, each texel of an aw x ah uv atlas shows. Texel (x, y), row-major y * aw + x, has the
+ * centre c = ((x + 0.5) / aw, (y + 0.5) / ah). The candidates are the entries `prims` (HOST array, n_list indices as rrt_hits.prim; NULL = every
+ * triangle entry of prim_order, ascending). Candidate k has the texture coordinates a, b, c3 of its vertices: its mesh uv, else get_uvs'
+ * (0,0), (1,0), (1,1) - the object's own, no transform touches them. In double, in both precision modes, uncontracted, with
+ * cross(p, q) = p.x q.y - p.y q.x:
+ *   A = cross(b - a, c3 - a) (A == 0 covers nothing),  beta1 = cross(c - a, c3 - a) / A,  beta2 = cross(b - a, c - a) / A,
+ *   covered iff beta1 >= 0 && beta2 >= 0 && beta1 + beta2 <= 1 (edges inclusive).
+ * The owner of a texel is the covering candidate with the smallest position in the list, so instances that share a chart and duplicated
+ * entries (Q26) resolve by the caller's order. site_prim = the owner's index or -1, b1 / b2 = its beta rounded once to the handle's type or 0:
+ * the three arrays (aw * ah each, in `mem`) are an rrt_sites. n_covered (host, may be NULL) = the number of owned texels. uv outside [0, 1)^2
+ * is not wrapped, and no gutter is made. Errors, before any device work: RRT_EINVAL for a NULL output, aw or ah outside 1 .. 16384, a bad mem,
+ * n_list == 0 with a list, a list entry out of range or naming a sphere, a frame in flight.
+ * Not provided: a follow-through-mirrors form, sphere sites, ray differentials or filtered rho, atlas dilation, a command-line form.
+ * Measured (tools/surface_time.py, profiles/surface_time.json; config 4, fp32, everything in device memory, one MI355X): over 319 652 rays
+ * rrt_surface_rays 0.266 ms with all groups against 0.248 ms for rrt_trace_closest (k_surface 6.9 us, at its streaming floor); 1024 x 1024 texels over
+ * 100 352 charted triangles: rrt_atlas_sites 0.53 ms, rrt_surface_at 0.068 ms, against 2.08 s + 0.16 s for the same two steps in numpy. */
+typedef struct rrt_surface {
+  int32_t mem, precision;
+  void *px, *py, *pz;
+  void *nx, *ny, *nz;
+  void *sx, *sy, *sz;
+  void *tu, *tv;
+  void *rho_r, *rho_g, *rho_b;
+  void *t;
+  int32_t *prim, *material;
+} rrt_surface;
+typedef struct rrt_sites { int32_t mem, precision; const int32_t* prim; const void *b1, *b2; } rrt_sites;
+int rrt_surface_rays(rrt_handle*, const rrt_rays* rays, size_t n, rrt_surface* out);
+int rrt_surface_at(rrt_handle*, const rrt_sites* sites, size_t n, rrt_surface* out);
+int rrt_atlas_sites(rrt_handle*, int32_t aw, int32_t ah, const int32_t* prims /* host, may be NULL */, size_t n_list, int mem, int32_t* site_prim /* aw * ah */,
+                    void* b1, void* b2 /* aw * ah, handle precision */, uint64_t* n_covered /* host, may be NULL */);
+
 /* Multi-GPU film partition: the same, for the rows of the interleaved 16-row tile bands b with
  * b % world == rank (tile height of integrator/mod.rs:55), rendered as one pixel set. Box filter: the ranks' films are
  * disjoint; wider filters: a sample's splat may land in a neighbour's rows of this rank's film. Either way summing

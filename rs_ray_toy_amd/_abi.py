@@ -159,6 +159,18 @@ class IrrParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("pad", C.c_int32), ("offset", C.c_double)]
 
 
+SURFACE_GROUPS = {"p": ("px", "py", "pz"), "n": ("nx", "ny", "nz"), "s": ("sx", "sy", "sz"), "uv": ("tu", "tv"), "rho": ("rho_r", "rho_g", "rho_b"),
+                  "t": ("t",), "prim": ("prim", "material")}
+
+
+class Surface(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32)] + [(k, C.c_void_p) for g in SURFACE_GROUPS.values() for k in g]
+
+
+class Sites(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32), ("prim", C.c_void_p), ("b1", C.c_void_p), ("b2", C.c_void_p)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("camera_samples", C.c_uint64), ("camera_rays", C.c_uint64), ("closest_queries", C.c_uint64),
                 ("any_queries", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
@@ -233,6 +245,9 @@ PROTOTYPES = {
                                   C.POINTER(RenderStats)]),
     "rrt_irradiance": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(IrrParams), C.c_void_p, C.c_void_p]),
     "rrt_irradiance_rays": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(IrrParams), C.c_void_p]),
+    "rrt_surface_rays": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(Surface)]),
+    "rrt_surface_at": (C.c_int, [C.c_void_p, C.POINTER(Sites), C.c_size_t, C.POINTER(Surface)]),
+    "rrt_atlas_sites": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rrt_render_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_render_bands_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rrt_render_end": (C.c_int, [C.c_void_p]),

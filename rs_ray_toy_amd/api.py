@@ -95,6 +95,15 @@ class Scene:
             raise ValueError(f'prim_ids: by is "material", "instance", "object" or "prim", not {by!r}')
         return np.ascontiguousarray(ids, np.uint32)
 
+    def prim_order(self):
+        """rrt_scene_desc.prim_order as an array: entry i (the index rrt_hits.prim, rrt_surface.prim and rrt_atlas_sites speak) -> index into prims,
+        so scene.prim_ids(by)[scene.prim_order()] selects list entries by object, instance or material."""
+        d = self.desc
+        n = int(d.n_prim_order)
+        if n == 0:
+            return np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(d.prim_order, shape=(n,)).copy()
+
     def __del__(self):
         try:
             if self._h:
@@ -327,6 +336,114 @@ class Renderer:
         pts = A.Points(A.RRT_MEM_DEVICE, self.precision, *p_ptrs3, *(n_ptrs3 if n_ptrs3 is not None else (None, None, None)), pixel_ptr)
         prm = self._irr_params(mode, offset)
         _check(A.lib().rrt_irradiance(self._h, C.byref(pts), m, s0, s1, C.byref(prm), sums_ptr, sh_ptr))
+
+    # surface records and lightmap sites (rrt_surface_rays, rrt_surface_at, rrt_atlas_sites)
+    SURFACE_FIELDS = tuple(A.SURFACE_GROUPS)
+
+    def _surface_out(self, m, fields):
+        """rrt_surface over fresh host arrays for the groups `fields` (names of A.SURFACE_GROUPS: "p", "n", "s", "uv", "rho", "t", "prim"); returns
+        the struct and {member name: array}."""
+        out = A.Surface(A.RRT_MEM_HOST, self.precision)
+        arrs = {}
+        for f in fields:
+            if f not in A.SURFACE_GROUPS:
+                raise ValueError(f"surface: fields are {', '.join(A.SURFACE_GROUPS)}, not {f!r}")
+            for k in A.SURFACE_GROUPS[f]:
+                arrs[k] = np.zeros(m, np.int32 if f == "prim" else self.dtype)
+                setattr(out, k, arrs[k].ctypes.data)
+        return out, arrs
+
+    @staticmethod
+    def _surface_dict(arrs):
+        """{member: (m,)} -> dict(p (m, 3), n, s, uv (m, 2), rho (m, 3), t (m,), prim, material) of the groups that were produced"""
+        res = {}
+        for f, members in A.SURFACE_GROUPS.items():
+            if members[0] not in arrs:
+                continue
+            if f == "prim":
+                res["prim"], res["material"] = arrs["prim"], arrs["material"]
+            elif f == "t":
+                res["t"] = arrs["t"]
+            else:
+                res[f] = np.stack([arrs[k] for k in members], 1)
+        return res
+
+    def surface(self, o, d, tmax=None, skip_prim=None, fields=SURFACE_FIELDS):
+        """rrt_surface_rays over host arrays: the rays o, d (m, 3), tmax (m,; None = inf), skip_prim (m,) or None, traced as trace_closest traces them;
+        returns a dict of the record groups `fields`: p, n, s, rho (m, 3), uv (m, 2), t (m,), prim and material (m,) int32 (-1 = a miss: a dead
+        record, zeros everywhere else but t)."""
+        o = np.asarray(o); d = np.asarray(d)
+        m = len(o)
+        tmax = np.full(m, np.inf) if tmax is None else tmax
+        soa = [np.ascontiguousarray(a, self.dtype) for a in (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2], tmax)]
+        skip = None if skip_prim is None else np.ascontiguousarray(skip_prim, np.int32)
+        rays = A.Rays(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in soa], None if skip is None else skip.ctypes.data)
+        out, arrs = self._surface_out(m, fields)
+        _check(A.lib().rrt_surface_rays(self._h, C.byref(rays), m, C.byref(out)))
+        return self._surface_dict(arrs)
+
+    def surface_at(self, prim, b1, b2, fields=SURFACE_FIELDS):
+        """rrt_surface_at over host arrays: the records of the sites (prim, b1, b2) - prim as rrt_hits.prim (-1 = no site: a dead record), b1, b2 the
+        barycentrics of rrt_hits.u / .v. Returns a dict as surface() does, t = 0."""
+        prim = np.ascontiguousarray(prim, np.int32)
+        b1 = np.ascontiguousarray(b1, self.dtype); b2 = np.ascontiguousarray(b2, self.dtype)
+        m = len(prim)
+        sites = A.Sites(A.RRT_MEM_HOST, self.precision, prim.ctypes.data, b1.ctypes.data, b2.ctypes.data)
+        out, arrs = self._surface_out(m, fields)
+        _check(A.lib().rrt_surface_at(self._h, C.byref(sites), m, C.byref(out)))
+        return self._surface_dict(arrs)
+
+    def atlas_sites(self, res, prims=None):
+        """rrt_atlas_sites into host arrays: res = (aw, ah); prims None = every triangle entry of prim_order, else the candidate list in the caller's
+        order (the first covering entry owns a texel). Returns dict(prim (ah, aw) int32 with -1 = uncovered, b1, b2 (ah, aw), covered: int)."""
+        aw, ah = int(res[0]), int(res[1])
+        n = max(0, aw) * max(0, ah)
+        prim = np.zeros(max(n, 1), np.int32); b1 = np.zeros(max(n, 1), self.dtype); b2 = np.zeros(max(n, 1), self.dtype)
+        lst = None if prims is None else np.ascontiguousarray(prims, np.int32)
+        covered = C.c_uint64(0)
+        _check(A.lib().rrt_atlas_sites(self._h, aw, ah, None if lst is None else lst.ctypes.data, 0 if lst is None else len(lst), A.RRT_MEM_HOST,
+                                       prim.ctypes.data, b1.ctypes.data, b2.ctypes.data, C.byref(covered)))
+        return dict(prim=prim[:n].reshape(ah, aw), b1=b1[:n].reshape(ah, aw), b2=b2[:n].reshape(ah, aw), covered=int(covered.value))
+
+    def _surface_device(self, ptrs):
+        """rrt_surface over device arrays: ptrs = {member name of rrt_surface: raw pointer}; members left out are NULL (their group is not produced)"""
+        out = A.Surface(A.RRT_MEM_DEVICE, self.precision)
+        for k, v in ptrs.items():
+            setattr(out, k, v)
+        return out
+
+    def surface_device(self, ptrs7, m, out_ptrs, skip_ptr=None):
+        """rrt_surface_rays on device-resident arrays (raw pointers): ptrs7 = ox, oy, oz, dx, dy, dz, tmax; out_ptrs = {member name of rrt_surface
+        ("px", ..., "rho_b", "t", "prim", "material"): pointer to m values}, whole groups."""
+        rays = A.Rays(A.RRT_MEM_DEVICE, self.precision, *ptrs7, skip_ptr)
+        out = self._surface_device(out_ptrs)
+        _check(A.lib().rrt_surface_rays(self._h, C.byref(rays), m, C.byref(out)))
+
+    def surface_at_device(self, prim_ptr, b1_ptr, b2_ptr, m, out_ptrs):
+        """rrt_surface_at on device-resident arrays (raw pointers); out_ptrs as surface_device takes them."""
+        sites = A.Sites(A.RRT_MEM_DEVICE, self.precision, prim_ptr, b1_ptr, b2_ptr)
+        out = self._surface_device(out_ptrs)
+        _check(A.lib().rrt_surface_at(self._h, C.byref(sites), m, C.byref(out)))
+
+    def atlas_sites_device(self, res, prim_ptr, b1_ptr, b2_ptr, prims=None):
+        """rrt_atlas_sites into device arrays of aw * ah values each (raw pointers; the candidate list stays a host array); returns the covered count."""
+        lst = None if prims is None else np.ascontiguousarray(prims, np.int32)
+        covered = C.c_uint64(0)
+        _check(A.lib().rrt_atlas_sites(self._h, int(res[0]), int(res[1]), None if lst is None else lst.ctypes.data, 0 if lst is None else len(lst), A.RRT_MEM_DEVICE,
+                                       prim_ptr, b1_ptr, b2_ptr, C.byref(covered)))
+        return int(covered.value)
+
+    def bake_irradiance(self, res, prims=None, s0=1, s1=None, offset=0.0, flip=False):
+        """A lightmap: atlas_sites -> surface_at -> irradiance composed over host arrays. res = (aw, ah), prims as atlas_sites takes it, draws
+        [s0, s1) (s1 None = nsamp), offset along the (flipped) normal. The record's normal is not turned towards anything: flip=True lights
+        the -n side. Returns dict(E (ah, aw, 3), stderr (ah, aw), covered (ah, aw) bool) through resolve_irradiance; uncovered texels are 0."""
+        aw, ah = int(res[0]), int(res[1])
+        sites = self.atlas_sites((aw, ah), prims)
+        rec = self.surface_at(sites["prim"].ravel(), sites["b1"].ravel(), sites["b2"].ravel(), fields=("p", "n"))
+        s0, s1 = self._draw_range(s0, s1)
+        sums = self.irradiance(rec["p"], -rec["n"] if flip else rec["n"], s0, s1, offset=offset)
+        out = resolve_irradiance(sums, s1 - s0)
+        return dict(E=out["E"].reshape(ah, aw, 3), stderr=out["stderr"].reshape(ah, aw), covered=sites["prim"] >= 0)
 
     def render_rays_device(self, rect, s0, s1, ptrs6, weight_ptr, p_film_ptr, film_ptr, stats=True):
         """rrt_render_rays on device-resident samples into a device film (+=)."""

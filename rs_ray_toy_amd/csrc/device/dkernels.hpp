@@ -29,7 +29,8 @@ template <typename R> struct ShadeBlock { static constexpr int n = 256; };
 template <> struct ShadeBlock<float> { static constexpr int n = RRT_SHADE_BLOCK; };
 enum { ERR_SHADING_NORMAL = 1, ERR_BETA = 4, ERR_NULL_BSDF = 8, ERR_MIPMAP = 16, ERR_HALTON_DIMS = 32, ERR_ST_DIMS = 64, ERR_NO_LIGHTS = 128,
        ERR_KIND_SET = 256 /* a material produced a lobe outside the shading kernel's kind set (dmath.hpp): host-side selection error */,
-       ERR_INGEST = 512 /* k_ingest_rays: a pixel or sample_num of rrt_ray_samples outside the film / outside 1 .. nsamp-1 */ };
+       ERR_INGEST = 512 /* k_ingest_rays: a pixel or sample_num of rrt_ray_samples outside the film / outside 1 .. nsamp-1 */,
+       ERR_SITE = 1024 /* k_sites_check: a site of rrt_sites that rrt_surface_at refuses */ };
 static_assert(ERR_ST_DIMS == kErrStDims, "error bit shared with dmath.hpp");
 static_assert(ERR_HALTON_DIMS == kErrHaltonDims, "error bit shared with dmath.hpp");
 
@@ -1024,25 +1025,31 @@ struct Surf {   // the parts of SurfaceInteraction (interaction.rs:95-181) the i
 // (fp32) triangle as an unevaluated sum p_hi + p_lo (TwoSum), and the triangle tests form (o_hi - p0) + o_lo:
 // o_hi - p0 is exact for nearby vertices, so the origin lies on its triangle to ~1e-9 and on the right side of every
 // neighbour. f64 mode: the reference expression, p_lo = 0.
-template <typename R>
+// SITE (rrt_surface_at): there is no ray; the point is the barycentric one in both precisions, p0 + ((p1 - p0) u + (p2 - p0) v), and in f64 p_lo = 0.
+template <typename R, bool SITE = false>
 RRT_DEV void spawn_point(V3<R> o, V3<R> d, R t, R u, R v, V3<R> p0, V3<R> p1, V3<R> p2, V3<R>* p, V3<R>* p_lo) {
+  if (!SITE) {
 #ifdef RRT_SPAWN_OLD
-  { *p = o + d * t; *p_lo = V3<R>(); return; }
+    { *p = o + d * t; *p_lo = V3<R>(); return; }
 #endif
-  if (sizeof(R) == 8) { *p = o + d * t; *p_lo = V3<R>(); return; }
+    if (sizeof(R) == 8) { *p = o + d * t; *p_lo = V3<R>(); return; }
+  }
   const V3<R> w = (p1 - p0) * u + (p2 - p0) * v;
   const V3<R> s = p0 + w;
+  if (SITE && sizeof(R) == 8) { *p = s; *p_lo = V3<R>(); return; }
   const V3<R> bb = s - p0;
   *p = s;
   *p_lo = (p0 - (s - bb)) + (w - bb);
 }
 
 // Triangle::intersect's SurfaceInteraction (shape/triangle.rs:267-390) rebuilt from (triangle, t, u, v)
-template <typename R>
+// SITE (rrt_surface_at): from (triangle, u, v) alone - o, d and t are not read, wo is not meaningful, and `prim` is a triangle (a sphere's
+// interaction needs the ray). Every other statement is the one the hit form runs.
+template <typename R, bool SITE = false>
 RRT_DEV Surf<R> build_surface(const SceneDev<R>& s, int prim, V3<R> o, V3<R> d, R t, R u, R v, SurfExt<R>* ext = nullptr) {
   Surf<R> si;
   const Tri<R> tr = s.tris[prim];
-  if (tr.plane == kSphereMark) {   // u = root branch recorded by the traversal (public API reports 0, 0 for spheres)
+  if (!SITE && tr.plane == kSphereMark) {   // u = root branch recorded by the traversal (public API reports 0, 0 for spheres)
     SphereSI<R> ss;
     sphere_surface(s.spheres[tr.shade], o, d, t, u, &ss, ext);
     si.ok = true;
@@ -1052,7 +1059,7 @@ RRT_DEV Surf<R> build_surface(const SceneDev<R>& s, int prim, V3<R> o, V3<R> d, 
     return si;
   }
   const bool inst = is_inst_tri(tr);
-  if (inst) {   // the triangle works with the ray TransformedPrimitive::intersect handed it (primitives.rs:124-127)
+  if (!SITE && inst) {   // the triangle works with the ray TransformedPrimitive::intersect handed it (primitives.rs:124-127)
     const InstDev<R>& I = s.insts[inst_of(tr)];
     o = aff_pt(I.mi, o); d = vnormalize(vnormalize(aff_vec(I.mi, d)));
   }
@@ -1080,7 +1087,7 @@ RRT_DEV Surf<R> build_surface(const SceneDev<R>& s, int prim, V3<R> o, V3<R> d, 
     V3<R> ng = cross(p2 - p0, p1 - p0);
     coordinate_system(vnormalize(ng), &dpdu, &dpdv);
   }
-  spawn_point(o, d, t, u, v, p0, p1, p2, &si.p, &si.p_lo);
+  spawn_point<R, SITE>(o, d, t, u, v, p0, p1, p2, &si.p, &si.p_lo);
   si.wo = -d;
   si.n = vnormalize(cross(dp02, dp12));
   si.sn = si.n;
@@ -2721,6 +2728,162 @@ __global__ void __launch_bounds__(kBlock) k_matte_extract(const uint32_t* ids, c
     if (in) sum += (double)c;
   }
   alpha[pix] = w0 != 0.0 ? (R)(sum / w0) : R(0);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Surface records (rrt_surface_rays, rrt_surface_at, include/rrt.h): the interaction k_aov_shade rebuilds, written out per record instead of
+// summed into planes. One thread per record; every produced array gets one element per lane, so a wave's store is one contiguous run. A group
+// whose pointers are NULL is a wave-uniform branch not taken: neither the tangent nor the texture context nor aov_rho is formed for it.
+// ------------------------------------------------------------------------------------------------------------
+template <typename R>
+struct SurfaceOut { R *p[3], *n[3], *s[3], *uv[2], *rho[3], *t; int32_t *prim, *material; };
+template <typename R>
+struct SitesIn { const int32_t* prim; const R *b1, *b2; };
+
+// what rrt_surface_at refuses of a site; prim == -1 is "no site"
+template <typename R>
+RRT_DEV bool site_ok(const SceneDev<R>& s, int32_t prim, R b1, R b2) {
+  if (prim == -1) return true;
+  if ((uint32_t)prim >= s.n_tris) return false;
+  if (s.tris[prim].plane == kSphereMark) return false;
+  return !(isinf(b1) || b1 != b1 || isinf(b2) || b2 != b2);
+}
+// the checking launch over a device-resident batch: nothing is written but the error bit
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_sites_check(SceneDev<R> s, SitesIn<R> in, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!site_ok(s, in.prim[i], in.b1[i], in.b2[i])) atomicOr(s.err, (uint32_t)ERR_SITE);
+}
+
+// SITE = false: record i is the hit record at pool position i (rrt_surface_rays: the rays were packed and traced as rrt_trace_closest does it).
+// SITE = true: record i is site i; no pool is read.
+template <typename R, bool TEX, bool SITE>
+__global__ void __launch_bounds__(kBlock) k_surface(SceneDev<R> s, Pools<R> p, SitesIn<R> in, SurfaceOut<R> out, uint32_t n) {
+  using V4 = typename Vec4T<R>::type;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int prim;
+  R t, u, v;
+  V3<R> o, d;
+  if (SITE) {
+    prim = in.prim[i]; t = R(0); u = in.b1[i]; v = in.b2[i];
+    if (prim >= 0 && !site_ok(s, prim, u, v)) prim = -1;   // (the host or k_sites_check has refused the batch already: this only keeps the index inside tris[])
+  } else {
+    const V4 h = p.hit[i];
+    prim = (int)real_to_bits(h.y); t = h.x; u = h.z; v = h.w;
+    if (prim >= 0) { const V4 ro = p.ray_o[i], rd = p.ray_d[i]; o = V3<R>(ro.x, ro.y, ro.z); d = V3<R>(rd.x, rd.y, rd.z); }
+  }
+  const bool want_s = out.s[0] != nullptr, want_uv = out.uv[0] != nullptr, want_rho = out.rho[0] != nullptr;
+  V3<R> pw, nn, ss;
+  R tu = R(0), tv = R(0);
+  Rgb<R> rho(R(0));
+  int32_t material = -1;
+  if (prim >= 0) {
+    SurfExt<R> ext;   // (always asked for: a pointer that is NULL on some paths keeps the struct in scratch; its unread members fold away)
+    const Surf<R> si = build_surface<R, SITE>(s, prim, o, d, t, u, v, &ext);
+    if (!si.ok) atomicOr(s.err, (uint32_t)ERR_SHADING_NORMAL);   // primitives.rs:66, as the frame reports it
+    pw = si.p + si.p_lo;
+    nn = vnormalize(si.n);
+    material = (int32_t)si.material;
+    if (want_s) ss = vnormalize(ao_dpdu(s, prim, si));
+    if (want_uv) { tu = ext.u; tv = ext.v; }
+    if (want_rho) {
+      TexCtx<R> tc;
+      if (TEX) {   // dpdx = dpdy = 0, dudx .. dvdy = 0 (TexCtx's defaults), as k_aov_shade sets it
+        tc.p = si.p; tc.u = ext.u; tc.v = ext.v;
+        tc.pd = V3<double>((double)si.p.x + (double)si.p_lo.x, (double)si.p.y + (double)si.p_lo.y, (double)si.p.z + (double)si.p_lo.z);
+      }
+      rho = aov_rho<R, TEX>(s, s.materials[si.material], tc);
+      if (TEX) { if (tc.err) atomicOr(s.err, (uint32_t)ERR_MIPMAP); }
+    }
+  }
+  if (out.p[0]) { out.p[0][i] = pw.x; out.p[1][i] = pw.y; out.p[2][i] = pw.z; }
+  if (out.n[0]) { out.n[0][i] = nn.x; out.n[1][i] = nn.y; out.n[2][i] = nn.z; }
+  if (want_s) { out.s[0][i] = ss.x; out.s[1][i] = ss.y; out.s[2][i] = ss.z; }
+  if (want_uv) { out.uv[0][i] = tu; out.uv[1][i] = tv; }
+  if (want_rho) { out.rho[0][i] = rho.r; out.rho[1][i] = rho.g; out.rho[2][i] = rho.b; }
+  if (out.t) out.t[i] = t;
+  if (out.prim) { out.prim[i] = prim; out.material[i] = material; }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Lightmap sites (rrt_atlas_sites, include/rrt.h): which triangle, at which barycentrics, each texel centre of a uv atlas shows. All arithmetic
+// is in double in both precision modes and is never contracted (the pragma below), so both builds and a plain numpy restatement form the
+// same bits.
+// ------------------------------------------------------------------------------------------------------------
+struct AtlasUv { double a[2], b[2], c[2]; };
+// the candidate's texture coordinates: its mesh uv, else get_uvs' (0,0), (1,0), (1,1) (triangle.rs:113-128); the object's own, no transform
+template <typename R>
+RRT_DEV AtlasUv atlas_uv(const SceneDev<R>& s, int prim) {
+  AtlasUv t{{0.0, 0.0}, {1.0, 0.0}, {1.0, 1.0}};
+  const uint32_t shade = s.tris[prim].shade;
+  if (shade != 0xffffffffu) {
+    const TriShade<R>& sh = s.shades[shade];
+    if (sh.has_uv) {
+      t.a[0] = (double)sh.uv[0][0]; t.a[1] = (double)sh.uv[0][1]; t.b[0] = (double)sh.uv[1][0]; t.b[1] = (double)sh.uv[1][1];
+      t.c[0] = (double)sh.uv[2][0]; t.c[1] = (double)sh.uv[2][1];
+    }
+  }
+  return t;
+}
+// beta of the texel centre (x + 0.5) / aw, (y + 0.5) / ah in the candidate; true = covered (edges inclusive). A == 0 covers nothing.
+RRT_DEV bool atlas_beta(const AtlasUv& t, uint32_t x, uint32_t y, double aw, double ah, double* b1, double* b2) {
+#pragma clang fp contract(off)
+  const double cx = ((double)x + 0.5) / aw, cy = ((double)y + 0.5) / ah;
+  const double bax = t.b[0] - t.a[0], bay = t.b[1] - t.a[1], cax = t.c[0] - t.a[0], cay = t.c[1] - t.a[1];
+  const double A = bax * cay - bay * cax;
+  *b1 = 0.0; *b2 = 0.0;
+  if (!(A != 0.0)) return false;   // (a NaN area covers nothing either)
+  const double px = cx - t.a[0], py = cy - t.a[1];
+  const double e1 = (px * cay - py * cax) / A, e2 = (bax * py - bay * px) / A;
+  *b1 = e1; *b2 = e2;
+  return e1 >= 0.0 && e2 >= 0.0 && e1 + e2 <= 1.0;
+}
+
+// One wave per candidate (list position k = wave index): the lanes stride the texels of its uv bounding box, grown by one texel and clipped to
+// the atlas - the coverage test itself decides - and take atomicMin of k into owner[], pre-filled with ~0u.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_atlas_owner(SceneDev<R> s, const int32_t* list, uint32_t n_list, uint32_t aw, uint32_t ah, uint32_t* owner) {
+  const uint32_t k = (uint32_t)(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63u;
+  if (k >= n_list) return;
+  const AtlasUv t = atlas_uv(s, list[k]);
+  const double daw = (double)aw, dah = (double)ah;
+  const double u0 = fmin(fmin(t.a[0], t.b[0]), t.c[0]), u1 = fmax(fmax(t.a[0], t.b[0]), t.c[0]);
+  const double v0 = fmin(fmin(t.a[1], t.b[1]), t.c[1]), v1 = fmax(fmax(t.a[1], t.b[1]), t.c[1]);
+  if (!(u0 <= u1) || !(v0 <= v1) || isinf(u0) || isinf(u1) || isinf(v0) || isinf(v1)) return;   // NaN or infinite coordinates cover nothing
+  // texel columns [x0, x1), rows [y0, y1): clamped as doubles before the conversion
+  const uint32_t x0 = (uint32_t)fmin(fmax(floor(u0 * daw) - 1.0, 0.0), daw), x1 = (uint32_t)fmin(fmax(ceil(u1 * daw) + 1.0, 0.0), daw);
+  const uint32_t y0 = (uint32_t)fmin(fmax(floor(v0 * dah) - 1.0, 0.0), dah), y1 = (uint32_t)fmin(fmax(ceil(v1 * dah) + 1.0, 0.0), dah);
+  if (x1 <= x0 || y1 <= y0) return;
+  const uint32_t bw = x1 - x0, total = bw * (y1 - y0);   // <= 16384^2 = 2^28
+  for (uint32_t idx = lane; idx < total; idx += 64u) {
+    const uint32_t x = x0 + idx % bw, y = y0 + idx / bw;   // x < aw, y < ah
+    double b1, b2;
+    if (atlas_beta(t, x, y, daw, dah, &b1, &b2)) atomicMin(&owner[(size_t)y * aw + x], k);
+  }
+}
+
+// One thread per texel: beta again for the owner, the three outputs coalesced, the owned texels counted with one atomic per wave.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_atlas_emit(SceneDev<R> s, const int32_t* list, const uint32_t* owner, uint32_t aw, uint32_t ah, int32_t* site_prim, R* b1o, R* b2o,
+                                                        unsigned long long* n_covered) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < (size_t)aw * ah;
+  bool owned = false;
+  if (in) {
+    const uint32_t k = owner[i];
+    int32_t prim = -1;
+    double b1 = 0.0, b2 = 0.0;
+    if (k != ~0u) {
+      prim = list[k];
+      atlas_beta(atlas_uv(s, prim), (uint32_t)(i % aw), (uint32_t)(i / aw), (double)aw, (double)ah, &b1, &b2);
+      owned = true;
+    }
+    site_prim[i] = prim; b1o[i] = (R)b1; b2o[i] = (R)b2;
+  }
+  const unsigned long long m = __ballot(owned);
+  if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(n_covered, (unsigned long long)__popcll(m));
 }
 
 }  // namespace rrtd

@@ -149,6 +149,56 @@ int rrt_irradiance_rays(rrt_handle* h, const rrt_points* pts, size_t n, uint64_t
   return irradiance_entry("rrt_irradiance_rays", h, pts, n, s0, s1, params, true, nullptr, nullptr, od6);
 }
 
+namespace {
+// rrt_surface_rays and rrt_surface_at: the caller's own structs first (wrong whichever handle they come with), each with its own message; then the
+// handle's checks (precision, a frame in flight, the sites themselves)
+int surface_entry(const char* fn, rrt_handle* h, const rrt_rays* rays, const rrt_sites* sites, bool rays_form, size_t n, rrt_surface* out) {
+  const std::string name(fn);
+  auto bad = [&](const char* what) { rrt::set_last_error(name + ": " + what); return (int)RRT_EINVAL; };
+  int in_mem;
+  if (rays_form) {
+    if (!rays) return bad("null ray description (rrt_rays)");
+    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz || !rays->tmax) return bad("null ray array");
+    in_mem = rays->mem;
+  } else {
+    if (!sites) return bad("null site description (rrt_sites)");
+    if (!sites->prim || !sites->b1 || !sites->b2) return bad("null site array");
+    in_mem = sites->mem;
+  }
+  if (in_mem != RRT_MEM_HOST && in_mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (!out) return bad("null record description (rrt_surface)");
+  const int groups[7][2] = {{(out->px != nullptr) + (out->py != nullptr) + (out->pz != nullptr), 3}, {(out->nx != nullptr) + (out->ny != nullptr) + (out->nz != nullptr), 3},
+                            {(out->sx != nullptr) + (out->sy != nullptr) + (out->sz != nullptr), 3}, {(out->tu != nullptr) + (out->tv != nullptr), 2},
+                            {(out->rho_r != nullptr) + (out->rho_g != nullptr) + (out->rho_b != nullptr), 3}, {out->t != nullptr, 1},
+                            {(out->prim != nullptr) + (out->material != nullptr), 2}};
+  int set = 0;
+  for (const auto& g : groups) {
+    if (g[0] != 0 && g[0] != g[1]) return bad("a group of arrays is partly set (p, n, s, uv, rho, t, prim + material: all of a group or none)");
+    set += g[0];
+  }
+  if (set == 0) return bad("no group of arrays asked for (all NULL)");
+  if (out->mem != in_mem) return bad(rays_form ? "rays and records must live in the same memory kind" : "sites and records must live in the same memory kind");
+  if (n == 0) return bad("n must be > 0");
+  if (n > 0x7fffffffu) return bad("batch too large");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->surface(fn, rays_form ? rays : nullptr, rays_form ? nullptr : sites, n, out); });
+}
+}  // namespace
+
+int rrt_surface_rays(rrt_handle* h, const rrt_rays* rays, size_t n, rrt_surface* out) { return surface_entry("rrt_surface_rays", h, rays, nullptr, true, n, out); }
+int rrt_surface_at(rrt_handle* h, const rrt_sites* sites, size_t n, rrt_surface* out) { return surface_entry("rrt_surface_at", h, nullptr, sites, false, n, out); }
+
+int rrt_atlas_sites(rrt_handle* h, int32_t aw, int32_t ah, const int32_t* prims, size_t n_list, int mem, int32_t* site_prim, void* b1, void* b2, uint64_t* n_covered) {
+  auto bad = [&](const char* what) { rrt::set_last_error(std::string("rrt_atlas_sites: ") + what); return (int)RRT_EINVAL; };
+  if (!site_prim || !b1 || !b2) return bad("null output");
+  if (aw < 1 || aw > 16384 || ah < 1 || ah > 16384) return bad("atlas size outside 1 .. 16384");
+  if (mem != RRT_MEM_HOST && mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (prims && n_list == 0) return bad("an empty candidate list (NULL = every triangle)");
+  if (prims && n_list > 0x7fffffffu) return bad("candidate list too large");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->atlas_sites(aw, ah, prims, n_list, mem, site_prim, b1, b2, n_covered); });
+}
+
 int rrt_render_rays(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_xyzw, int film_mem,
                     rrt_render_stats* stats) {
   if (const int rc = ray_samples_check("rrt_render_rays", rays, false); rc != RRT_OK) return rc;

@@ -47,6 +47,9 @@ struct HandleBase {
   virtual void radiance(const rrt_ray_samples* rays, size_t n, void* rgb4) = 0;
   // rrt_irradiance (od6 NULL; sh27 may be NULL) and rrt_irradiance_rays (od6 set, sums4 and sh27 NULL) under the name `who`
   virtual void irradiance(const char* who, const rrt_points* pts, size_t n, uint64_t s0, uint64_t s1, int mode, double offset, void* sums4, void* sh27, void* od6) = 0;
+  // rrt_surface_rays (rays set, sites NULL) and rrt_surface_at (sites set, rays NULL) under the name `who`
+  virtual void surface(const char* who, const rrt_rays* rays, const rrt_sites* sites, size_t n, const rrt_surface* out) = 0;
+  virtual void atlas_sites(int32_t aw, int32_t ah, const int32_t* prims, size_t n_list, int mem, int32_t* site_prim, void* b1, void* b2, uint64_t* n_covered) = 0;
   virtual void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film, int film_mem, rrt_render_stats* stats) = 0;   // p_film in rays->mem
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
@@ -569,6 +572,131 @@ class Handle : public HandleBase {
     HIP_CHECK(hipStreamSynchronize(st_));
     HIP_CHECK(hipStreamSynchronize(st2_));
     check_device_errors();
+  }
+  // ---- surface records and lightmap sites: rrt_surface_rays, rrt_surface_at, rrt_atlas_sites ------------------------------------------------------
+  // The rays form is trace_closest() with k_surface in place of k_unpack_hits: the same load_rays, k_rotate and launch_closest, so the pool's hit
+  // records are the ones rrt_trace_closest unpacks. The sites form launches k_surface alone. Host arrays are staged and copied back per array.
+  void surface(const char* who_c, const rrt_rays* rays, const rrt_sites* sites, size_t n, const rrt_surface* out) override {
+    const std::string who(who_c);
+    check_args(who, kWhenIdle, Prec{"record", out->precision});
+    if ((rays ? rays->precision : sites->precision) != precision()) throw std::invalid_argument(who + ": " + (rays ? "ray" : "site") + " precision must match the handle");
+    const bool host = out->mem != RRT_MEM_DEVICE;
+    if (sites && host) {   // device-resident sites: the same checks by k_sites_check, below
+      const R *b1 = (const R*)sites->b1, *b2 = (const R*)sites->b2;
+      for (size_t i = 0; i < n; i++) {
+        const int32_t pr = sites->prim[i];
+        if (pr == -1) continue;
+        const std::string at = " (site " + std::to_string(i) + ")";
+        if (pr < 0 || (size_t)pr >= surf_sphere_.size()) throw std::invalid_argument(who + ": prim outside [0, n_prim_order)" + at);
+        if (surf_sphere_[pr]) throw std::invalid_argument(who + ": prim names a sphere (its record needs the ray: rrt_surface_rays)" + at);
+        if (!std::isfinite((double)b1[i]) || !std::isfinite((double)b2[i])) throw std::invalid_argument(who + ": non-finite barycentric" + at);
+      }
+    }
+    device_prologue(/*film=*/false);
+    HIP_CHECK(hipMemsetAsync(counters_.p, 0, C_COUNT * sizeof(uint32_t), st_));
+    // the caller's arrays as the kernel takes them: the pointers themselves for device memory, else staging
+    void* const real[15] = {out->px, out->py, out->pz, out->nx, out->ny, out->nz, out->sx, out->sy, out->sz, out->tu, out->tv, out->rho_r, out->rho_g, out->rho_b, out->t};
+    R* dev_r[15];
+    int32_t *dev_prim = out->prim, *dev_mat = out->material;
+    DevBuf<R> stage_r, stage_in;
+    DevBuf<int32_t> stage_i, stage_prim;
+    if (host) {
+      size_t n_real = 0;
+      for (int k = 0; k < 15; k++) n_real += real[k] != nullptr;
+      stage_r.alloc(n_real * n);
+      R* next = stage_r.p;
+      for (int k = 0; k < 15; k++) { dev_r[k] = real[k] ? next : nullptr; if (real[k]) next += n; }
+      if (out->prim) { stage_i.alloc(2 * n); dev_prim = stage_i.p; dev_mat = stage_i.p + n; }
+    } else {
+      for (int k = 0; k < 15; k++) dev_r[k] = (R*)real[k];
+    }
+    SurfaceOut<R> so{};
+    for (int k = 0; k < 3; k++) { so.p[k] = dev_r[k]; so.n[k] = dev_r[3 + k]; so.s[k] = dev_r[6 + k]; so.rho[k] = dev_r[11 + k]; }
+    so.uv[0] = dev_r[9]; so.uv[1] = dev_r[10]; so.t = dev_r[14]; so.prim = dev_prim; so.material = dev_mat;
+    const dim3 grid((uint32_t)((n + kBlock - 1) / kBlock));
+    if (rays) {
+      ensure_pools(n);
+      load_rays(rays, n);
+      hipLaunchKernelGGL(k_rotate, dim3(1), dim3(1), 0, st_, counters_.p, 3);
+      launch_closest(nullptr, nullptr, (uint32_t)n, false, nullptr, nullptr, nullptr);
+      with_flag(tex_depth_ > 0, [&](auto TEX) { hipLaunchKernelGGL((k_surface<R, TEX(), false>), grid, dim3(kBlock), 0, st_, scene_, pool_, SitesIn<R>{}, so, (uint32_t)n); });
+    } else {
+      SitesIn<R> in{sites->prim, (const R*)sites->b1, (const R*)sites->b2};
+      if (host) {
+        stage_in.alloc(2 * n); stage_prim.alloc(n);
+        HIP_CHECK(hipMemcpyAsync(stage_prim.p, sites->prim, n * sizeof(int32_t), hipMemcpyHostToDevice, st_));
+        HIP_CHECK(hipMemcpyAsync(stage_in.p, sites->b1, n * sizeof(R), hipMemcpyHostToDevice, st_));
+        HIP_CHECK(hipMemcpyAsync(stage_in.p + n, sites->b2, n * sizeof(R), hipMemcpyHostToDevice, st_));
+        in = SitesIn<R>{stage_prim.p, stage_in.p, stage_in.p + n};
+      } else {
+        hipLaunchKernelGGL((k_sites_check<R>), grid, dim3(kBlock), 0, st_, scene_, in, (uint32_t)n);
+        HIP_CHECK(hipGetLastError());
+        uint32_t err = 0;
+        HIP_CHECK(hipStreamSynchronize(st_));
+        HIP_CHECK(hipMemcpy(&err, counters_.p + C_ERROR, sizeof(err), hipMemcpyDeviceToHost));
+        if (err & ERR_SITE) {
+          HIP_CHECK(hipMemsetAsync(counters_.p + C_ERROR, 0, sizeof(uint32_t), st_));
+          throw std::invalid_argument(who + ": a refused site (a prim outside [0, n_prim_order) other than -1, a sphere, or a non-finite barycentric)");
+        }
+      }
+      with_flag(tex_depth_ > 0, [&](auto TEX) { hipLaunchKernelGGL((k_surface<R, TEX(), true>), grid, dim3(kBlock), 0, st_, scene_, pool_, in, so, (uint32_t)n); });
+    }
+    HIP_CHECK(hipGetLastError());
+    if (host) {
+      for (int k = 0; k < 15; k++) if (real[k]) HIP_CHECK(hipMemcpyAsync(real[k], dev_r[k], n * sizeof(R), hipMemcpyDeviceToHost, st_));
+      if (out->prim) {
+        HIP_CHECK(hipMemcpyAsync(out->prim, dev_prim, n * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipMemcpyAsync(out->material, dev_mat, n * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+      }
+    }
+    HIP_CHECK(hipStreamSynchronize(st_));
+    check_device_errors();
+  }
+  // k_atlas_owner over the candidate list (the caller's, or every triangle entry of prim_order), k_atlas_emit over the texels
+  void atlas_sites(int32_t aw, int32_t ah, const int32_t* prims, size_t n_list, int mem, int32_t* site_prim, void* b1, void* b2, uint64_t* n_covered) override {
+    const std::string who("rrt_atlas_sites");
+    check_args(who, kWhenIdle);
+    std::vector<int32_t> list;
+    if (prims) {
+      for (size_t i = 0; i < n_list; i++) {
+        const int32_t pr = prims[i];
+        if (pr < 0 || (size_t)pr >= surf_sphere_.size()) throw std::invalid_argument(who + ": list entry outside [0, n_prim_order) (entry " + std::to_string(i) + ")");
+        if (surf_sphere_[pr]) throw std::invalid_argument(who + ": list entry names a sphere (entry " + std::to_string(i) + ")");
+      }
+      list.assign(prims, prims + n_list);
+    } else {
+      for (size_t i = 0; i < surf_sphere_.size(); i++) if (!surf_sphere_[i]) list.push_back((int32_t)i);
+    }
+    HIP_CHECK(hipSetDevice(dev_));
+    const size_t nt = (size_t)aw * (size_t)ah;
+    const bool host = mem != RRT_MEM_DEVICE;
+    DevBuf<uint32_t> owner;
+    DevBuf<int32_t> dlist, stage_i;
+    DevBuf<unsigned long long> count;
+    DevBuf<R> stage_r;
+    owner.alloc(nt); count.alloc(1);
+    HIP_CHECK(hipMemsetAsync(owner.p, 0xff, nt * sizeof(uint32_t), st_));
+    HIP_CHECK(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), st_));
+    dlist.upload(list, st_);
+    int32_t* d_prim = site_prim;
+    R *d_b1 = (R*)b1, *d_b2 = (R*)b2;
+    if (host) { stage_i.alloc(nt); stage_r.alloc(2 * nt); d_prim = stage_i.p; d_b1 = stage_r.p; d_b2 = stage_r.p + nt; }
+    if (!list.empty()) {
+      const size_t blocks = (list.size() * 64 + kBlock - 1) / kBlock;
+      hipLaunchKernelGGL((k_atlas_owner<R>), dim3((uint32_t)blocks), dim3(kBlock), 0, st_, scene_, (const int32_t*)dlist.p, (uint32_t)list.size(), (uint32_t)aw, (uint32_t)ah, owner.p);
+    }
+    hipLaunchKernelGGL((k_atlas_emit<R>), dim3((uint32_t)((nt + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, (const int32_t*)dlist.p, (const uint32_t*)owner.p, (uint32_t)aw, (uint32_t)ah,
+                       d_prim, d_b1, d_b2, count.p);
+    HIP_CHECK(hipGetLastError());
+    if (host) {
+      HIP_CHECK(hipMemcpyAsync(site_prim, d_prim, nt * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipMemcpyAsync(b1, d_b1, nt * sizeof(R), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipMemcpyAsync(b2, d_b2, nt * sizeof(R), hipMemcpyDeviceToHost, st_));
+    }
+    unsigned long long c = 0;
+    if (n_covered) HIP_CHECK(hipMemcpyAsync(&c, count.p, sizeof(c), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));   // the work buffers go out of scope
+    if (n_covered) *n_covered = (uint64_t)c;
   }
   void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("rrt_render_rays", kWhenIdle, Prec{"ray", rays->precision}, {}, rect);
@@ -1644,6 +1772,7 @@ class Handle : public HandleBase {
   DevBuf<typename Vec4T<R>::type> matte_w_;
   DevBuf<uint2> matte_rec_;
   std::vector<uint32_t> matte_order_, matte_mat_, matte_id_host_;
+  std::vector<uint8_t> surf_sphere_;   // per entry of prim_order: 1 = a sphere
   uint32_t aov_serial_ = 0;   // k_aov_shade_frame's stamp of the pass last shaded: counted up per pass over the handle's life, never 0 in a record
 
   void check_renderable() {
@@ -1693,6 +1822,9 @@ class Handle : public HandleBase {
     matte_order_.assign(d->prim_order, d->prim_order + d->n_prim_order);
     matte_mat_.resize(d->n_prim_order);
     for (size_t i = 0; i < d->n_prim_order; i++) matte_mat_[i] = d->prims[d->prim_order[i]].material + 1u;
+    // rrt_surface_at, rrt_atlas_sites: which entries of prim_order are spheres (refused as sites and as candidates), kept on the host
+    surf_sphere_.resize(fs.tris.size());
+    for (size_t i = 0; i < fs.tris.size(); i++) surf_sphere_[i] = fs.tris[i].plane == kSphereMark ? 1 : 0;
     shade_kinds_scene_ = fs.used.shade == ShadeClass::Lambert ? kKindsLambert : (fs.used.shade == ShadeClass::Glossy ? kKindsGlossy : kAllKinds);
     shade_kinds_ = shade_kinds_scene_;
     if (!fs.used.warning.empty()) warnings.push_back(fs.used.warning);
