@@ -530,6 +530,52 @@ int rrt_surface_at(rrt_handle*, const rrt_sites* sites, size_t n, rrt_surface* o
 int rrt_atlas_sites(rrt_handle*, int32_t aw, int32_t ah, const int32_t* prims /* host, may be NULL */, size_t n_list, int mem, int32_t* site_prim /* aw * ah */,
                     void* b1, void* b2 /* aw * ah, handle precision */, uint64_t* n_covered /* host, may be NULL */);
 
+/* Nearest-surface point queries (no counterpart in the reference; none of its quirks applies to a distance, so the call is defined geometrically):
+ * per point the nearest site on the scene's triangles and its distance - what a probe grid needs to drop probes against a wall, what baking from one
+ * mesh onto another starts from, what a distance field is made of. {prim, b1, b2} of the output ARE an rrt_sites: they go into rrt_surface_at as
+ * they are. rrt_points is reused so that a record set or an irradiance point set can be passed as it is: only px, py, pz, mem and precision are read;
+ * the normals and `pixel` may be NULL and are ignored. All arrays in `mem` (out->mem must equal points->mem), element type = the handle's precision.
+ *   Candidates: the triangle entries of prim_order. Sphere entries are NOT candidates (as for rrt_atlas_sites); a scene with no triangle entry is
+ *     RRT_EUNSUP. A candidate's world-space vertices a, b, c are the ones the handle stores (fp32 handles: rounded to float); for a triangle of a
+ *     non-rigid instance the handle kept, the stored raw vertices taken through the instance's primitive_to_world (m v + t, row by row,
+ *     ((m0 x + m1 y) + m2 z) + m3), in the handle's type.
+ *   Closest point of a candidate: the Voronoi-region test (Ericson, Real-Time Collision Detection 5.1.5), all in the handle's type, no operation
+ *     contracted to an fma, dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z:
+ *       ab = b - a, ac = c - a, ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap); bp = p - b, d3 = dot(ab, bp), d4 = dot(ac, bp);
+ *       cp = p - c, d5 = dot(ab, cp), d6 = dot(ac, cp); vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4;
+ *       the first rule that holds gives (b1, b2):
+ *         d1 <= 0 && d2 <= 0                        (0, 0)
+ *         d3 >= 0 && d4 <= d3                       (1, 0)
+ *         vc <= 0 && d1 >= 0 && d3 <= 0             (d1 / (d1 - d3), 0)
+ *         d6 >= 0 && d5 <= d6                       (0, 1)
+ *         vb <= 0 && d2 >= 0 && d6 <= 0             (0, d2 / (d2 - d6))
+ *         va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0   w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), (1 - w, w)
+ *         otherwise                                 den = 1 / ((va + vb) + vc), (vb den, vc den)
+ *       each of b1, b2 clamped to [0, 1]; q = a + (ab b1 + ac b2); d2 = ((p - q).x^2 + (p - q).y^2) + (p - q).z^2; dist = sqrt(d2).
+ *     The result depends on (p, a, b, c) alone. b1 >= 0 and b2 >= 0 exactly; b1 + b2 <= 1 up to one rounding.
+ *   Winner: the candidate with the smallest d2; among equal d2 the smallest index into prim_order (a point on a shared edge or vertex is a tie). A
+ *     candidate whose d2 is NaN (a degenerate triangle can have one) never wins. The result is therefore that of a scan over all candidates and does
+ *     not depend on the tree: a subtree is skipped only where its box's squared distance exceeds the current bound by a margin that covers the
+ *     roundings of both distances (csrc/host/nearest.hpp kNearestPadUlps).
+ *   Outputs (overwritten): a point is accepted iff dist <= (R)max_dist: prim = the winner's index into prim_order as rrt_hits.prim, b1, b2 its
+ *     barycentrics as rrt_hits.u / .v, dist. A point with no accepted candidate, and a point with a non-finite coordinate (dead), gets prim = -1,
+ *     b1 = b2 = 0, dist = (R)max_dist. dist may be NULL.
+ * Errors, before any device work, the structs checked before the handle: RRT_EINVAL for NULL arguments (dist alone may be NULL), a bad mem, a
+ * precision that is not the handle's, n == 0 or n > 2^31 - 1, max_dist NaN or negative (+inf and 0 are legal), a frame in flight. The call leaves
+ * the handle as it was (a frame rendered before and after is the same frame).
+ * Not provided: sphere candidates, a per-point radius, an excluded primitive, a sign (inside or outside), the k nearest, a _begin / _end form.
+ * Measured (tools/nearest_time.py, profiles/nearest_time.json; config 4, fp32, everything in device memory, one MI355X): 1 048 576 atlas points lifted 0.01
+ * extent off the surface 1.07 ms (1.0 ns per point) against 0.238 ms for rrt_trace_closest over as many rays; a 128^3 grid over the world bound 8.39 ms
+ * (4.0 ns per point) against 0.281 ms. The fp32 default is the generic kernel on the linear tree; the pair-node kernel (option "nearest_pairs") returns the
+ * same bits and measured 1.62 ms and 11.78 ms. */
+typedef struct rrt_nearest_out {
+  int32_t mem, precision;
+  int32_t* prim;      /* n: index into prim_order as rrt_hits.prim; -1 = nothing within max_dist */
+  void *b1, *b2;      /* n, handle precision: barycentrics as rrt_hits.u / .v  -> {prim, b1, b2} ARE an rrt_sites */
+  void *dist;         /* n, handle precision; may be NULL */
+} rrt_nearest_out;
+int rrt_nearest(rrt_handle*, const rrt_points* points, size_t n, double max_dist, rrt_nearest_out* out);
+
 /* Multi-GPU film partition: the same, for the rows of the interleaved 16-row tile bands b with
  * b % world == rank (tile height of integrator/mod.rs:55), rendered as one pixel set. Box filter: the ranks' films are
  * disjoint; wider filters: a sample's splat may land in a neighbour's rows of this rank's film. Either way summing
@@ -923,6 +969,8 @@ int rrt_film_gather_all(rrt_handle* const* handles, void* const* films_device, i
  *                                 0: the per-slot layout and k_film_box
  * dn_lds                1         rrt_denoise: 1: the a-trous steps 1 and 2 read their taps from an LDS tile with       invariant (tests/test_denoise.py::test_denoise_lds_changes_nothing)
  *                                 halo (the steps at which that measured faster); 0: direct gathers at every step
+ * nearest_pairs         0  fp32   rrt_nearest: 1: the walk on the pair-node tree (LDS treelet and stack; measured     invariant (tests/test_nearest.py::test_invariances, test_tree_shapes)
+ *                                 1.4 - 1.5 x slower on config 4); 0: the generic kernel on the linear tree
  */
 int rrt_set_option(rrt_handle*, const char* key, double value);
 

@@ -445,6 +445,44 @@ class Renderer:
         out = resolve_irradiance(sums, s1 - s0)
         return dict(E=out["E"].reshape(ah, aw, 3), stderr=out["stderr"].reshape(ah, aw), covered=sites["prim"] >= 0)
 
+    # nearest-surface point queries (rrt_nearest)
+    def nearest(self, p, max_dist=np.inf):
+        """rrt_nearest over host arrays: p (m, 3) points; returns dict(prim (m,) int32 - index into prim_order as trace_closest's prim, -1 = nothing
+        within max_dist -, b1, b2 (m,) barycentrics, dist (m,)). (prim, b1, b2) go into surface_at as they are. Spheres are not candidates."""
+        p = np.asarray(p)
+        m = len(p)
+        cols = [np.ascontiguousarray(p[:, k], self.dtype) for k in range(3)]
+        pts = A.Points(A.RRT_MEM_HOST, self.precision, *[c.ctypes.data for c in cols], None, None, None, None)
+        prim = np.zeros(m, np.int32)
+        b1 = np.zeros(m, self.dtype); b2 = np.zeros(m, self.dtype); dist = np.zeros(m, self.dtype)
+        out = A.NearestOut(A.RRT_MEM_HOST, self.precision, prim.ctypes.data, b1.ctypes.data, b2.ctypes.data, dist.ctypes.data)
+        _check(A.lib().rrt_nearest(self._h, C.byref(pts), m, float(max_dist), C.byref(out)))
+        return dict(prim=prim, b1=b1, b2=b2, dist=dist)
+
+    def nearest_device(self, ptrs, n, max_dist=np.inf):
+        """rrt_nearest on device-resident arrays (raw pointers): ptrs = {"px", "py", "pz", "prim", "b1", "b2" and optionally "dist": pointer to n values}."""
+        pts = A.Points(A.RRT_MEM_DEVICE, self.precision, ptrs["px"], ptrs["py"], ptrs["pz"], None, None, None, None)
+        out = A.NearestOut(A.RRT_MEM_DEVICE, self.precision, ptrs["prim"], ptrs["b1"], ptrs["b2"], ptrs.get("dist"))
+        _check(A.lib().rrt_nearest(self._h, C.byref(pts), n, float(max_dist), C.byref(out)))
+
+    def nearest_records(self, p, max_dist=np.inf, fields=SURFACE_FIELDS):
+        """nearest composed with surface_at: the surface records (dict as surface_at returns it) of the sites nearest to the points p, plus
+        "dist", "b1" and "b2"; a point with nothing within max_dist gets the dead record (prim = -1)."""
+        near = self.nearest(p, max_dist)
+        rec = self.surface_at(near["prim"], near["b1"], near["b2"], fields=fields)
+        rec.update(dist=near["dist"], b1=near["b1"], b2=near["b2"])
+        rec.setdefault("prim", near["prim"])
+        return rec
+
+    def distance_field(self, lo, hi, res, max_dist=np.inf):
+        """The distances at the cell centres of a (rx, ry, rz) grid over the box lo .. hi, as an array (rz, ry, rx): nearest() over points built in
+        numpy; cells with nothing within max_dist hold max_dist."""
+        lo = np.asarray(lo, np.float64); hi = np.asarray(hi, np.float64)
+        rx, ry, rz = (int(r) for r in res)
+        ax = [lo[k] + (np.arange(r) + 0.5) * ((hi[k] - lo[k]) / r) for k, r in enumerate((rx, ry, rz))]
+        z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+        return self.nearest(np.stack([x.ravel(), y.ravel(), z.ravel()], 1), max_dist)["dist"].reshape(rz, ry, rx)
+
     def render_rays_device(self, rect, s0, s1, ptrs6, weight_ptr, p_film_ptr, film_ptr, stats=True):
         """rrt_render_rays on device-resident samples into a device film (+=)."""
         rs = A.RaySamples(A.RRT_MEM_DEVICE, self.precision, *ptrs6, weight_ptr)

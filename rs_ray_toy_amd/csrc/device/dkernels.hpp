@@ -4,6 +4,7 @@
 #pragma once
 #include "dmath.hpp"
 #include "dtexture.hpp"
+#include "nearest.hpp"   // rrt_nearest: the per-triangle function and the walk, shared with the host (tools/nearest_check.cpp)
 
 namespace rrtd {
 
@@ -30,7 +31,8 @@ template <> struct ShadeBlock<float> { static constexpr int n = RRT_SHADE_BLOCK;
 enum { ERR_SHADING_NORMAL = 1, ERR_BETA = 4, ERR_NULL_BSDF = 8, ERR_MIPMAP = 16, ERR_HALTON_DIMS = 32, ERR_ST_DIMS = 64, ERR_NO_LIGHTS = 128,
        ERR_KIND_SET = 256 /* a material produced a lobe outside the shading kernel's kind set (dmath.hpp): host-side selection error */,
        ERR_INGEST = 512 /* k_ingest_rays: a pixel or sample_num of rrt_ray_samples outside the film / outside 1 .. nsamp-1 */,
-       ERR_SITE = 1024 /* k_sites_check: a site of rrt_sites that rrt_surface_at refuses */ };
+       ERR_SITE = 1024 /* k_sites_check: a site of rrt_sites that rrt_surface_at refuses */,
+       ERR_NEAREST = 2048 /* k_nearest / k_nearest_pairs_f32: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */ };
 static_assert(ERR_ST_DIMS == kErrStDims, "error bit shared with dmath.hpp");
 static_assert(ERR_HALTON_DIMS == kErrHaltonDims, "error bit shared with dmath.hpp");
 
@@ -2884,6 +2886,39 @@ __global__ void __launch_bounds__(kBlock) k_atlas_emit(SceneDev<R> s, const int3
   }
   const unsigned long long m = __ballot(owned);
   if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(n_covered, (unsigned long long)__popcll(m));
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Nearest-surface point queries (rrt_nearest, include/rrt.h): one lane per point over the linear tree (host/nearest.hpp nearest_walk). The stack
+// holds node indices only - a popped node is fetched and its box judged against the bound of that moment - as [entry][thread of the launch] in
+// global memory, stack_depth entries per thread, like the generic closest-hit kernel's deep stack. Point base + i of the call is thread i.
+// ------------------------------------------------------------------------------------------------------------
+template <typename R>
+struct NearestIO {
+  const R *px, *py, *pz;
+  int32_t* prim;
+  R *b1, *b2, *dist;       // dist may be null
+  R max_dist, prune0, delta;   // prune0 = nn_prune_start(max_dist, delta), delta = kNearestPadUlps x eps x M
+};
+template <typename R>
+RRT_DEV void nearest_store(const NearestIO<R>& io, size_t g, const NnBest<R>& best) {
+  const NnOut<R> o = nn_result<R>(best, io.max_dist);
+  io.prim[g] = o.prim; io.b1[g] = o.b1; io.b2[g] = o.b2;
+  if (io.dist) io.dist[g] = o.dist;
+}
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_nearest(const Node<R>* nodes, uint32_t n_nodes, const Tri<R>* tris, uint32_t n_tris, const InstDev<R>* insts, uint32_t* err,
+                                                     NearestIO<R> io, size_t base, uint32_t n, uint32_t* stack, uint32_t stride, uint32_t stack_cap) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t g = base + i;
+  const R px = io.px[g], py = io.py[g], pz = io.pz[g];
+  NnBest<R> best = nn_none<R>();
+  if (nn_finite(px) && nn_finite(py) && nn_finite(pz)) {   // a point with a non-finite coordinate is dead
+    GlobStack st{stack + i, stride};
+    if (!nearest_walk<R>(nodes, n_nodes, tris, n_tris, insts, px, py, pz, io.prune0, io.delta, st, stack_cap, &best)) atomicOr(err, (uint32_t)ERR_NEAREST);
+  }
+  nearest_store<R>(io, g, best);
 }
 
 }  // namespace rrtd

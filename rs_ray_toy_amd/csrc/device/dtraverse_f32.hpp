@@ -1582,4 +1582,95 @@ static __global__ void __launch_bounds__(64 * kFrTiles) k_film_box_runs(SceneDev
   if (live) { px[0] = cr; px[1] = cg; px[2] = cb; px[3] = wsum; }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Nearest-surface point queries on the pair-node tree (rrt_nearest in fp32; host/nearest.hpp has the per-triangle function, the box distance and
+// the prune bound, dkernels.hpp the generic kernel this one must equal bit for bit). One lane per point, a plain grid. NOT the default: measured
+// 1.4 - 1.5 x slower than k_nearest<float> on config 4 (profiles/nearest_time.json); option "nearest_pairs" = 1 selects it. One 64 B fetch yields both
+// children's box distances (max(bmin - p, p - bmax, 0) per axis); the lane descends into the nearer child and pushes the farther one with its d2 if
+// that is within the bound. The bound only shrinks, so - unlike a ray's t_max (Q10) - a popped entry beyond the bound of that moment is simply
+// dropped. The top of the tree comes from the LDS treelet; the stack is [entry][thread] in LDS for kNnStackLds entries, deeper ones in a global
+// array [entry][thread of the launch] sized from stack_depth. Every word is checked against its array before it is followed, the stack against
+// stack_depth and the loop against 2 n_nodes + 2 steps: a walk that passes a bound sets ERR_NEAREST and stops.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int kNnBlock = 512;      // as kTravBlock: 8 waves share one copy of the treelet (32 KB + 32 KB of stack: two workgroups per CU)
+constexpr int kNnStackLds = 8;
+
+// a kSpecialLeaf leaf: spheres are no candidates, triangles of kept instances go through InstDev::m. Rare path, not inlined (as special_leaf_f32).
+__attribute__((noinline)) __device__ NnBest<float> nn_special_leaf_f32(const Tri<float>* tris, const InstDev<float>* insts, uint32_t lf, uint32_t ln, float px, float py, float pz,
+                                                                        NnBest<float> best) {
+  for (uint32_t k = 0; k < ln; k++) nn_consider<float, true>(best, tris[lf + k], insts, lf + k, px, py, pz);
+  return best;
+}
+
+template <bool MIXED>
+__global__ void __launch_bounds__(kNnBlock) k_nearest_pairs_f32(TravScene ts, NearestIO<float> io, size_t base, uint32_t n, uint32_t n_tris, uint32_t stack_cap, uint32_t* err,
+                                                                 uint2* overflow, uint32_t overflow_stride) {
+  __shared__ float4 treelet[kTreeletNodes * 4];
+  __shared__ uint2 stk[kNnStackLds * kNnBlock];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < ts.n_treelet * 4u; i += kNnBlock) treelet[i] = reinterpret_cast<const float4*>(ts.pairs)[i];
+  __syncthreads();
+  const uint32_t col = blockIdx.x * kNnBlock + tid;
+  if (col >= n) return;
+  const size_t g = base + col;
+  const float px = io.px[g], py = io.py[g], pz = io.pz[g];
+  NnBest<float> best = nn_none<float>();
+  const uint32_t treelet_bytes = ts.n_treelet * 64u, pair_bytes = (ts.n_nodes >> 1) * 64u;   // a tree of n nodes has (n - 1) / 2 interior ones
+  const Tri<float>* const tris = reinterpret_cast<const Tri<float>*>(ts.tris);
+  float prune = io.prune0;
+  uint32_t cur = kIdle, sp = 0u, steps = 0u;
+  bool bad = false;
+  if (nn_finite(px) && nn_finite(py) && nn_finite(pz) && ts.n_nodes != 0u &&
+      !(nn_box_d2<float>(ts.root_box[0], ts.root_box[1], ts.root_box[2], ts.root_box[3], ts.root_box[4], ts.root_box[5], px, py, pz) > prune))
+    cur = ts.root_id;
+  const uint32_t limit = 2u * ts.n_nodes + 2u;
+  while (cur != kIdle) {
+    if (++steps > limit) { bad = true; break; }
+    bool pop = true;
+    if (is_node(cur)) {
+      if (cur >= pair_bytes || (cur & 63u) != 0u) { bad = true; break; }
+      float4 a, b, c; uint32_t id0, id1;
+      if (cur < treelet_bytes) {
+        const float4* tp = treelet + (cur >> 4);
+        a = tp[0]; b = tp[1]; c = tp[2]; const float4 dd = tp[3];
+        id0 = __float_as_uint(dd.x); id1 = __float_as_uint(dd.y);
+      } else {
+        const char* np = reinterpret_cast<const char*>(ts.pairs) + cur;
+        a = *reinterpret_cast<const float4*>(np); b = *reinterpret_cast<const float4*>(np + 16); c = *reinterpret_cast<const float4*>(np + 32);
+        const uint2 dd = *reinterpret_cast<const uint2*>(np + 48);
+        id0 = dd.x; id1 = dd.y;
+      }
+      const float e0 = nn_box_d2<float>(a.x, a.y, c.x, a.z, a.w, c.y, px, py, pz), e1 = nn_box_d2<float>(b.x, b.y, c.z, b.z, b.w, c.w, px, py, pz);
+      const bool second = e1 < e0;
+      const float e_near = second ? e1 : e0, e_far = second ? e0 : e1;
+      if (!(e_far > prune)) {
+        if (sp >= stack_cap) { bad = true; break; }
+        const uint2 e = make_uint2(second ? id0 : id1, __float_as_uint(e_far));
+        if (sp < (uint32_t)kNnStackLds) stk[sp * kNnBlock + tid] = e;
+        else overflow[(size_t)(sp - kNnStackLds) * overflow_stride + col] = e;
+        sp++;
+      }
+      if (!(e_near > prune)) { cur = second ? id1 : id0; pop = false; }
+    } else {
+      const uint32_t lf = cur & 0x7ffffu, ln = (cur >> 19) & kLeafCountMask;
+      if (!is_leaf(cur) || lf > n_tris || ln > n_tris - lf) { bad = true; break; }
+      const int32_t before = best.prim;
+      const float before_d2 = best.d2;
+      if (MIXED && (cur & kSpecialLeaf) != 0u) best = nn_special_leaf_f32(tris, ts.insts, lf, ln, px, py, pz, best);
+      else for (uint32_t k = 0; k < ln; k++) nn_consider<float, false>(best, tris[lf + k], nullptr, lf + k, px, py, pz);
+      if (best.prim != before || best.d2 != before_d2) prune = fminf(prune, nn_prune_bound<float>(best.d2, io.delta));
+    }
+    if (pop) {
+      cur = kIdle;
+      while (sp > 0u) {
+        sp--;
+        const uint2 e = sp < (uint32_t)kNnStackLds ? stk[sp * kNnBlock + tid] : overflow[(size_t)(sp - kNnStackLds) * overflow_stride + col];
+        if (!(__uint_as_float(e.y) > prune)) { cur = e.x; break; }
+      }
+    }
+  }
+  if (bad) { atomicOr(err, (uint32_t)ERR_NEAREST); best = nn_none<float>(); }
+  nearest_store<float>(io, g, best);
+}
+
 }  // namespace rrtd

@@ -199,6 +199,21 @@ int rrt_atlas_sites(rrt_handle* h, int32_t aw, int32_t ah, const int32_t* prims,
   return guarded([&]() { h->impl->atlas_sites(aw, ah, prims, n_list, mem, site_prim, b1, b2, n_covered); });
 }
 
+int rrt_nearest(rrt_handle* h, const rrt_points* pts, size_t n, double max_dist, rrt_nearest_out* out) {
+  auto bad = [&](const char* what) { rrt::set_last_error(std::string("rrt_nearest: ") + what); return (int)RRT_EINVAL; };
+  if (!pts) return bad("null point description (rrt_points)");
+  if (!pts->px || !pts->py || !pts->pz) return bad("null point array");
+  if (pts->mem != RRT_MEM_HOST && pts->mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (!out) return bad("null output description (rrt_nearest_out)");
+  if (!out->prim || !out->b1 || !out->b2) return bad("null output array (dist alone may be NULL)");
+  if (out->mem != pts->mem) return bad("points and outputs must live in the same memory kind");
+  if (n == 0) return bad("n must be > 0");
+  if (n > 0x7fffffffu) return bad("batch too large");
+  if (!(max_dist >= 0.0)) return bad("max_dist must be >= 0 (+inf = no limit), not negative or NaN");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->nearest(pts, n, max_dist, out); });
+}
+
 int rrt_render_rays(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_xyzw, int film_mem,
                     rrt_render_stats* stats) {
   if (const int rc = ray_samples_check("rrt_render_rays", rays, false); rc != RRT_OK) return rc;

@@ -50,6 +50,7 @@ struct HandleBase {
   // rrt_surface_rays (rays set, sites NULL) and rrt_surface_at (sites set, rays NULL) under the name `who`
   virtual void surface(const char* who, const rrt_rays* rays, const rrt_sites* sites, size_t n, const rrt_surface* out) = 0;
   virtual void atlas_sites(int32_t aw, int32_t ah, const int32_t* prims, size_t n_list, int mem, int32_t* site_prim, void* b1, void* b2, uint64_t* n_covered) = 0;
+  virtual void nearest(const rrt_points* pts, size_t n, double max_dist, const rrt_nearest_out* out) = 0;
   virtual void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film, int film_mem, rrt_render_stats* stats) = 0;   // p_film in rays->mem
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
@@ -288,6 +289,7 @@ class Handle : public HandleBase {
     else if (key == "film_records") film_records_on_ = v != 0;   // 1 (default): the path integrator's tile-tree passes keep radiance in per-workgroup record runs, added up by k_film_box_runs
     else if (key == "shade_spec") shade_kinds_ = v != 0 ? shade_kinds_scene_ : kAllKinds;
     else if (key == "frame_stats") frame_stats_ = v != 0;
+    else if (key == "nearest_pairs") nn_pairs_on_ = v != 0;   // rrt_nearest in fp32: 0 (default): k_nearest<float> on the linear tree; 1: k_nearest_pairs_f32 on the pair nodes (the same bits, measured slower)
     else if (key == "dn_lds") dn_lds_ = v != 0;   // rrt_denoise: 1 (default): the a-trous steps 1 and 2 read their taps from an LDS tile; 0: direct gathers at every step
     else if (key == "halton_tables") scene_.n_hblk = (v != 0 && hblk_.n) ? (uint32_t)kHaltonTabDims : 0u;
     else if (key == "cam_tables") { for (int w = 0; w < 3; w++) { scene_.cam_lo[w] = (v != 0 && cam_lo_.n) ? cam_lo_.p + cam_lo_off_[w] : nullptr; scene_.cam_hi[w] = (v != 0 && cam_hi_.n) ? cam_hi_.p + cam_hi_off_[w] : nullptr; } }
@@ -698,6 +700,64 @@ class Handle : public HandleBase {
     HIP_CHECK(hipStreamSynchronize(st_));   // the work buffers go out of scope
     if (n_covered) *n_covered = (uint64_t)c;
   }
+  // ---- nearest-surface point queries: rrt_nearest ------------------------------------------------------------------------------------------------
+  // One lane per point, no pool and no queue: the points are cut into passes of at most max_paths (and 2^20) points only to bound the stack arrays,
+  // which the handle keeps between calls. k_nearest<R> runs in both precisions; fp32 handles with a pair-node tree run k_nearest_pairs_f32 under option
+  // "nearest_pairs" (measured slower: DESIGN.md). A point's result depends on the point alone, so neither the cut nor the kernel changes a bit. Host arrays are staged and copied back per array.
+  void nearest(const rrt_points* pts, size_t n, double max_dist, const rrt_nearest_out* out) override {
+    const std::string who("rrt_nearest");
+    check_args(who, kWhenIdle, Prec{"point", pts->precision});
+    if (out->precision != precision()) throw std::invalid_argument(who + ": output precision must match the handle");
+    if (!nn_has_tri_) throw UnsupportedError(who + ": the scene has no triangle entry (spheres are not candidates)");
+    HIP_CHECK(hipSetDevice(dev_));
+    HIP_CHECK(hipMemsetAsync(counters_.p + C_ERROR, 0, sizeof(uint32_t), st_));
+    const bool host = pts->mem != RRT_MEM_DEVICE;
+    DevBuf<R> stage_in, stage_out;
+    DevBuf<int32_t> stage_prim;
+    NearestIO<R> io{};
+    io.px = (const R*)pts->px; io.py = (const R*)pts->py; io.pz = (const R*)pts->pz;
+    io.prim = out->prim; io.b1 = (R*)out->b1; io.b2 = (R*)out->b2; io.dist = (R*)out->dist;
+    if (host) {
+      stage_in.alloc(3 * n); stage_out.alloc((out->dist ? 3 : 2) * n); stage_prim.alloc(n);
+      const void* src[3] = {pts->px, pts->py, pts->pz};
+      for (int k = 0; k < 3; k++) HIP_CHECK(hipMemcpyAsync(stage_in.p + (size_t)k * n, src[k], n * sizeof(R), hipMemcpyHostToDevice, st_));
+      io.px = stage_in.p; io.py = stage_in.p + n; io.pz = stage_in.p + 2 * n;
+      io.prim = stage_prim.p; io.b1 = stage_out.p; io.b2 = stage_out.p + n; io.dist = out->dist ? stage_out.p + 2 * n : nullptr;
+    }
+    io.max_dist = (R)max_dist; io.delta = nn_delta_; io.prune0 = nn_prune_start<R>(io.max_dist, io.delta);
+    const size_t per_pass = std::min<size_t>({n, max_paths_, (size_t)1 << 20});
+    const uint32_t depth = scene_.stack_depth;
+    bool pairs = false;
+    if constexpr (std::is_same<R, float>::value) pairs = pairs_ok_ && nn_pairs_on_;
+    const size_t block = pairs ? (size_t)kNnBlock : (size_t)kBlock;
+    const size_t stride = (per_pass + block - 1) / block * block;   // threads of a launch
+    if (pairs) {
+      if (depth > (uint32_t)kNnStackLds && nn_overflow_.n < (size_t)(depth - kNnStackLds) * stride) nn_overflow_.alloc((size_t)(depth - kNnStackLds) * stride);
+    } else if (nn_stack_.n < (size_t)depth * stride) nn_stack_.alloc((size_t)depth * stride);
+    for (size_t p0 = 0; p0 < n; p0 += per_pass) {
+      const uint32_t m = (uint32_t)std::min(per_pass, n - p0);
+      const dim3 grid((uint32_t)((m + block - 1) / block));
+      if constexpr (std::is_same<R, float>::value) {
+        if (pairs) {
+          with_flag(mixed_, [&](auto MIXED) {
+            hipLaunchKernelGGL((k_nearest_pairs_f32<MIXED()>), grid, dim3(kNnBlock), 0, st_, trav_, io, p0, m, scene_.n_tris, depth, counters_.p + C_ERROR, nn_overflow_.p, (uint32_t)stride);
+          });
+          continue;
+        }
+      }
+      hipLaunchKernelGGL((k_nearest<R>), grid, dim3(kBlock), 0, st_, scene_.nodes, scene_.n_nodes, scene_.tris, scene_.n_tris, scene_.insts, counters_.p + C_ERROR, io, p0, m,
+                         nn_stack_.p, (uint32_t)stride, depth);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (host) {
+      HIP_CHECK(hipMemcpyAsync(out->prim, io.prim, n * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipMemcpyAsync(out->b1, io.b1, n * sizeof(R), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipMemcpyAsync(out->b2, io.b2, n * sizeof(R), hipMemcpyDeviceToHost, st_));
+      if (out->dist) HIP_CHECK(hipMemcpyAsync(out->dist, io.dist, n * sizeof(R), hipMemcpyDeviceToHost, st_));
+    }
+    HIP_CHECK(hipStreamSynchronize(st_));
+    check_device_errors();
+  }
   void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("rrt_render_rays", kWhenIdle, Prec{"ray", rays->precision}, {}, rect);
     if (s0 < 1 || s1 > desc_.sampler.samples_per_pixel || s0 >= s1) throw std::invalid_argument("rrt_render_rays: sample range outside [1, nsamp) or empty");
@@ -772,6 +832,7 @@ class Handle : public HandleBase {
     if (err & ERR_NULL_BSDF) throw PanicError("glass.rs:70 / translucent.rs:66 null BSDF (textures evaluate to black): path.rs:103 `bounces -= 1` underflows");
     if (err & ERR_BETA) throw PanicError("path.rs:146 assert!(beta.y() > 0.0 && beta.y().is_finite())");
     if (err & ERR_KIND_SET) throw DeviceError("internal: a material produced a BxDF outside the kind set its shading kernel was selected for (shade_spec())");
+    if (err & ERR_NEAREST) throw DeviceError("internal: a rrt_nearest walk passed its step or stack bound (the tree is not the tree its depth and node count describe)");
   }
   void render_bands(int rank, int world, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("render_bands", kAnyTime, {}, Ranks{rank, world});
@@ -1773,6 +1834,12 @@ class Handle : public HandleBase {
   DevBuf<uint2> matte_rec_;
   std::vector<uint32_t> matte_order_, matte_mat_, matte_id_host_;
   std::vector<uint8_t> surf_sphere_;   // per entry of prim_order: 1 = a sphere
+  // rrt_nearest: the absolute part of the prune margin (host/nearest.hpp: kNearestPadUlps x eps x M), whether any entry is a triangle, the stack
+  // arrays of the two kernels (kept between calls, grown on demand), the fp32 kernel choice (option "nearest_pairs")
+  R nn_delta_ = R(0);
+  bool nn_has_tri_ = false, nn_pairs_on_ = false;
+  DevBuf<uint32_t> nn_stack_;
+  DevBuf<uint2> nn_overflow_;
   uint32_t aov_serial_ = 0;   // k_aov_shade_frame's stamp of the pass last shaded: counted up per pass over the handle's life, never 0 in a record
 
   void check_renderable() {
@@ -1825,6 +1892,20 @@ class Handle : public HandleBase {
     // rrt_surface_at, rrt_atlas_sites: which entries of prim_order are spheres (refused as sites and as candidates), kept on the host
     surf_sphere_.resize(fs.tris.size());
     for (size_t i = 0; i < fs.tris.size(); i++) surf_sphere_[i] = fs.tris[i].plane == kSphereMark ? 1 : 0;
+    {   // rrt_nearest: M = the largest coordinate a query meets - the root box, and what a kept instance's vertex transform sums up (|m_ij| |v_j| + |t_i|)
+      double M = 0.0;
+      if (!fs.nodes.empty()) for (int k = 0; k < 3; k++) M = std::max({M, std::fabs((double)fs.nodes[0].bmin[k]), std::fabs((double)fs.nodes[0].bmax[k])});
+      nn_has_tri_ = false;
+      for (const Tri<R>& t : fs.tris) {
+        if (t.plane == kSphereMark) continue;
+        nn_has_tri_ = true;
+        if ((t.material & kInstFlag) == 0u) continue;
+        const R* m = fs.insts[(t.material >> 16) & 0x7fffu].m;
+        for (const R* v : {t.p0, t.p1, t.p2}) for (int i = 0; i < 3; i++)
+          M = std::max(M, std::fabs((double)m[4 * i] * (double)v[0]) + std::fabs((double)m[4 * i + 1] * (double)v[1]) + std::fabs((double)m[4 * i + 2] * (double)v[2]) + std::fabs((double)m[4 * i + 3]));
+      }
+      nn_delta_ = (R)((double)kNearestPadUlps * (double)NnConst<R>::eps * M);
+    }
     shade_kinds_scene_ = fs.used.shade == ShadeClass::Lambert ? kKindsLambert : (fs.used.shade == ShadeClass::Glossy ? kKindsGlossy : kAllKinds);
     shade_kinds_ = shade_kinds_scene_;
     if (!fs.used.warning.empty()) warnings.push_back(fs.used.warning);
