@@ -576,6 +576,63 @@ typedef struct rrt_nearest_out {
 } rrt_nearest_out;
 int rrt_nearest(rrt_handle*, const rrt_points* points, size_t n, double max_dist, rrt_nearest_out* out);
 
+/* All hits along a ray, in order (no counterpart in the reference, like rrt_nearest; defined geometrically, as a scan over all candidates): per ray the
+ * k nearest accepted triangle hits, sorted, and the number of all of them - what thickness and layered baking, transparency and X-ray passes, inside /
+ * outside tests and the sign of a distance field are made of. One traversal per ray, against k launches and k root-to-leaf walks of a peel with
+ * rrt_trace_closest, which moreover neither terminates cleanly on coplanar faces nor is complete (Q10). Slot-major outputs: plane s of
+ * {prim, b1, b2} (n values from [s * n]) IS an rrt_sites and goes into rrt_surface_at as it is. All arrays in `mem` (out->mem must equal rays->mem),
+ * element type = the handle's precision R.
+ *   Candidates: the triangle entries of prim_order. Sphere entries are NOT candidates (as for rrt_nearest and rrt_atlas_sites); a scene with no
+ *     triangle entry is RRT_EUNSUP. A candidate's world-space vertices a, b, c are the ones the handle stores (fp32 handles: rounded to float); for a
+ *     triangle of a non-rigid instance the handle kept, the stored raw vertices taken through the instance's primitive_to_world (m v + t, row by row,
+ *     ((m0 x + m1 y) + m2 z) + m3), in the handle's type. rays->skip_prim[i], where the array is given and the value is >= 0, removes that one entry (by
+ *     index into prim_order) from ray i's candidates.
+ *   Acceptance of candidate (a, b, c) for ray (o, d, tmax): all in the handle's type, no operation contracted to an fma, the two divisions IEEE
+ *     divisions, dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, (u x v) = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x). All three must hold:
+ *     (i)   the triangle test, Moller-Trumbore in the operation order of rrt_trace_closest's (Triangle::intersect): E1 = b - a, E2 = c - a, P = d x E2,
+ *           det = dot(E1, P), rejected if -1e-7 < det < 1e-7; f = 1 / det; T = o - a; u = f dot(T, P), 0 <= u <= 1; Q = T x E1; v = f dot(d, Q), v >= 0,
+ *           u + v <= 1; t = f dot(E2, Q), t >= 1e-7. (No double-float origin: public rays carry none.)
+ *     (ii)  t < (R)tmax.
+ *     (iii) the ray passes the slab test of the candidate's OWN box, lo = min(a, b, c), hi = max(a, b, c) per axis: inv = 1 / d; per axis
+ *           near = (lo - o) * inv, far = (hi - o) * inv, the two swapped where inv < 0; far *= 1 + 2 gamma(3), gamma(3) = 3 eps / (1 - 3 eps),
+ *           eps = 2^-24 / 2^-53 (Bounds3::intersect_p); a NaN term is dropped and is never a reason to reject; pass iff max(nears, 0) <= min(fars, tmax).
+ *     Rule (iii) makes the result independent of the tree: rounding is monotone, so a node box that contains the own box passes the same test
+ *     whenever the own box does (node boxes are rounded outward; for scenes with kept instances they are grown by csrc/host/multihit.hpp
+ *     kMultihitPadUlps), and a Moller-Trumbore "hit" at a grazing angle whose point lies nowhere near the triangle is rejected by definition
+ *     instead of by accident of the tree. The walk opens every node whose box passes and prunes nothing by t, with or without `count`.
+ *   Result (outputs are overwritten): the accepted candidates sorted by (t ascending, index into prim_order ascending). Slots 0 .. min(k, count) - 1
+ *     hold them: t, prim = the index as rrt_hits.prim, b1 = u and b2 = v as rrt_hits.u / .v. The remaining slots hold prim = -1, t = (R)tmax,
+ *     b1 = b2 = 0. count = the number of ALL accepted candidates, not clipped at k. A ray with a non-finite origin, direction or tmax (+inf is legal),
+ *     or with a zero direction, is dead: count = 0 and all slots empty. With k == 0 the slot arrays are ignored and count must be set (the count-only
+ *     form, for parity). b1 and b2 may both be NULL.
+ *     WARNING for parity users: two triangles that share an edge BOTH report a ray through that edge (and all triangles around a vertex a ray through
+ *     that vertex), at equal or nearly equal t, the smaller index first among equal t: such a ray's count is not the number of surface crossings.
+ *   Relation to rrt_trace_closest: slot 0 is the NEAREST accepted hit. rrt_trace_closest returns the LAST accepted one in traversal order (Q10: the
+ *     reference's triangle test never looks at t_max), its t for a triangle of a kept instance is the object-space one (Q15), it tests spheres, its
+ *     fp32 kernels use a fast reciprocal and contract to fma, and it has no rule (iii). Where its hit is a rigid triangle and the nearest one, slot 0
+ *     names the same prim; t, u and v agree to rounding, not to the bit.
+ * Errors, before any device work, the structs checked before the handle: RRT_EINVAL for NULL arguments or ray arrays, k outside 0 .. RRT_MAX_HITS,
+ * k > 0 with a NULL t or prim, exactly one of b1 / b2 set, k == 0 with count == NULL, a bad mem or out->mem != rays->mem, a precision that is not the
+ * handle's, n == 0 or n > 2^31 - 1, a frame in flight. The call leaves the handle as it was (a frame rendered before and after is the same frame).
+ * Not provided: sphere candidates, more than RRT_MAX_HITS slots, per-slot surface records in the same call (feed plane s to rrt_surface_at), a
+ * pair-node fp32 kernel (the walk runs on the linear tree in both precisions), a _begin / _end form.
+ * Measured (tools/trace_all_time.py, profiles/trace_all_time.json; config 4, fp32, everything in device memory, one MI355X): 1 048 576 unbounded rays
+ * between random points of 1.2 x the world bound, 2.4 hits a ray on average and at most 19: k = 1 2.38 ms, k = 4 2.43 ms, k = 16 3.28 ms, the count-only
+ * form 2.31 ms (2.2 - 3.1 ns per ray); a NULL count changes nothing (2.37 / 2.43 / 3.27 ms: nothing is pruned by t). One rrt_trace_closest over the same
+ * rays 0.405 ms - it stops at the first hit, on the pair-node tree, where this call walks the whole ray on the linear tree -; a peel of k
+ * rrt_trace_closest calls with skip_prim and an advanced origin 0.53 ms at k = 1, 2.14 ms at k = 4, 8.10 ms at k = 16: the single walk overtakes
+ * the peel between k = 4 (0.88 x) and k = 16 (2.5 x), and unlike the peel it is complete and terminates on coplanar faces. */
+#define RRT_MAX_HITS 16
+typedef struct rrt_multi_hits {
+  int32_t mem, precision;   /* mem must equal rays->mem; precision the handle's */
+  int32_t k, pad;           /* slots per ray, 0 .. RRT_MAX_HITS */
+  void* t;                  /* k * n, slot-major: slot s of ray i at [s * n + i] */
+  int32_t* prim;            /* k * n, index into prim_order as rrt_hits.prim; -1 = empty slot */
+  void *b1, *b2;            /* k * n, as rrt_hits.u / .v; both NULL or both set */
+  uint32_t* count;          /* n: ALL accepted candidates of the ray, not clipped at k; may be NULL */
+} rrt_multi_hits;
+int rrt_trace_all(rrt_handle*, const rrt_rays* rays, size_t n, rrt_multi_hits* out);
+
 /* Multi-GPU film partition: the same, for the rows of the interleaved 16-row tile bands b with
  * b % world == rank (tile height of integrator/mod.rs:55), rendered as one pixel set. Box filter: the ranks' films are
  * disjoint; wider filters: a sample's splat may land in a neighbour's rows of this rank's film. Either way summing

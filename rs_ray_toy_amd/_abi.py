@@ -175,6 +175,14 @@ class NearestOut(C.Structure):
     _fields_ = [("mem", C.c_int32), ("precision", C.c_int32), ("prim", C.c_void_p), ("b1", C.c_void_p), ("b2", C.c_void_p), ("dist", C.c_void_p)]
 
 
+RRT_MAX_HITS = 16
+
+
+class MultiHits(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("precision", C.c_int32), ("k", C.c_int32), ("pad", C.c_int32), ("t", C.c_void_p), ("prim", C.c_void_p), ("b1", C.c_void_p),
+                ("b2", C.c_void_p), ("count", C.c_void_p)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("camera_samples", C.c_uint64), ("camera_rays", C.c_uint64), ("closest_queries", C.c_uint64),
                 ("any_queries", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
@@ -253,6 +261,7 @@ PROTOTYPES = {
     "rrt_surface_at": (C.c_int, [C.c_void_p, C.POINTER(Sites), C.c_size_t, C.POINTER(Surface)]),
     "rrt_atlas_sites": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rrt_nearest": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.c_double, C.POINTER(NearestOut)]),
+    "rrt_trace_all": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(MultiHits)]),
     "rrt_render_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_render_bands_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rrt_render_end": (C.c_int, [C.c_void_p]),

@@ -474,14 +474,75 @@ class Renderer:
         rec.setdefault("prim", near["prim"])
         return rec
 
-    def distance_field(self, lo, hi, res, max_dist=np.inf):
+    def distance_field(self, lo, hi, res, max_dist=np.inf, signed=False):
         """The distances at the cell centres of a (rx, ry, rz) grid over the box lo .. hi, as an array (rz, ry, rx): nearest() over points built in
-        numpy; cells with nothing within max_dist hold max_dist."""
+        numpy; cells with nothing within max_dist hold max_dist. signed=True negates the distances of the cells inside() finds inside (closed
+        surfaces only)."""
         lo = np.asarray(lo, np.float64); hi = np.asarray(hi, np.float64)
         rx, ry, rz = (int(r) for r in res)
         ax = [lo[k] + (np.arange(r) + 0.5) * ((hi[k] - lo[k]) / r) for k, r in enumerate((rx, ry, rz))]
         z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
-        return self.nearest(np.stack([x.ravel(), y.ravel(), z.ravel()], 1), max_dist)["dist"].reshape(rz, ry, rx)
+        p = np.stack([x.ravel(), y.ravel(), z.ravel()], 1)
+        dist = self.nearest(p, max_dist)["dist"]
+        if signed:
+            dist = np.where(self.inside(p), -dist, dist)
+        return dist.reshape(rz, ry, rx)
+
+    # all hits along a ray, in order (rrt_trace_all)
+    def trace_all(self, o, d, tmax, k=8, count=True, skip_prim=None):
+        """rrt_trace_all over host arrays: o, d (m, 3), tmax (m,); returns dict(t, prim, b1, b2 of shape (k, m) - slot s of ray i at [s, i], the accepted
+        triangle hits sorted by (t, prim), prim = index into prim_order as trace_closest's prim, -1 / tmax / 0 / 0 in the empty slots - and, with
+        count=True, count (m,) uint32: ALL accepted hits of the ray, not clipped at k). Plane s of (prim, b1, b2) goes into surface_at as it is.
+        k = 0 is the count-only form. Spheres are not candidates."""
+        o = np.asarray(o); d = np.asarray(d)
+        m = len(tmax)
+        soa = [np.ascontiguousarray(a, self.dtype) for a in (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2], tmax)]
+        skip = None if skip_prim is None else np.ascontiguousarray(skip_prim, np.int32)
+        rays = A.Rays(A.RRT_MEM_HOST, self.precision, *[a.ctypes.data for a in soa], None if skip is None else skip.ctypes.data)
+        k = int(k)
+        t = np.zeros((k, m), self.dtype); b1 = np.zeros((k, m), self.dtype); b2 = np.zeros((k, m), self.dtype)
+        prim = np.zeros((k, m), np.int32)
+        cnt = np.zeros(m, np.uint32) if count else None
+        slots = [a.ctypes.data if k > 0 else None for a in (t, prim, b1, b2)]
+        out = A.MultiHits(A.RRT_MEM_HOST, self.precision, k, 0, *slots, None if cnt is None else cnt.ctypes.data)
+        _check(A.lib().rrt_trace_all(self._h, C.byref(rays), m, C.byref(out)))
+        res = dict(t=t, prim=prim, b1=b1, b2=b2)
+        if count:
+            res["count"] = cnt
+        return res
+
+    def trace_all_device(self, ptrs7, n, out_ptrs, k, skip_ptr=None):
+        """rrt_trace_all on device-resident arrays (raw pointers): ptrs7 = ox, oy, oz, dx, dy, dz, tmax (n values each); out_ptrs = {"t", "prim" and
+        optionally "b1" and "b2": pointer to k * n values, slot-major; optionally "count": pointer to n uint32}."""
+        rays = A.Rays(A.RRT_MEM_DEVICE, self.precision, *ptrs7, skip_ptr)
+        out = A.MultiHits(A.RRT_MEM_DEVICE, self.precision, int(k), 0, out_ptrs.get("t"), out_ptrs.get("prim"), out_ptrs.get("b1"), out_ptrs.get("b2"), out_ptrs.get("count"))
+        _check(A.lib().rrt_trace_all(self._h, C.byref(rays), n, C.byref(out)))
+
+    # three fixed, mutually skew directions (no two parallel, none along an axis or a face diagonal of an axis-aligned mesh)
+    INSIDE_DIRECTIONS = ((0.8164, 0.4082, 0.4083), (-0.3015, 0.9045, 0.3016), (0.2673, -0.5345, 0.8018))
+
+    def inside(self, p):
+        """Whether the points p (m, 3) lie inside the scene's closed triangle surfaces: the parity of trace_all's count (k = 0, unbounded rays) along
+        INSIDE_DIRECTIONS, decided by majority - a ray through a shared edge or a vertex counts every triangle around it, which one vote absorbs.
+        Returns (m,) bool."""
+        p = np.asarray(p, np.float64)
+        m = len(p)
+        votes = np.zeros(m, np.int32)
+        tmax = np.full(m, np.inf)
+        for d in self.INSIDE_DIRECTIONS:
+            votes += (self.trace_all(p, np.broadcast_to(np.asarray(d, np.float64), (m, 3)), tmax, k=0)["count"] & 1).astype(np.int32)
+        return votes >= 2
+
+    def thickness(self, o, d, tmax, k=A.RRT_MAX_HITS):
+        """The length of the rays inside the scene's closed surfaces, in units of |d|: the sum of t[2j + 1] - t[2j] over the pairs of the first k hits
+        (an unpaired last hit adds nothing). Returns (m,) in the handle's type."""
+        hits = self.trace_all(o, d, tmax, k=k)
+        held = np.minimum(hits["count"], k)
+        total = np.zeros(len(held), self.dtype)
+        for j in range(k // 2):
+            with np.errstate(invalid="ignore"):      # (empty slots hold tmax: inf - inf where nothing is held)
+                total += np.where(held >= 2 * j + 2, hits["t"][2 * j + 1] - hits["t"][2 * j], 0)
+        return total
 
     def render_rays_device(self, rect, s0, s1, ptrs6, weight_ptr, p_film_ptr, film_ptr, stats=True):
         """rrt_render_rays on device-resident samples into a device film (+=)."""

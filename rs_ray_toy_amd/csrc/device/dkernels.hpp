@@ -5,6 +5,7 @@
 #include "dmath.hpp"
 #include "dtexture.hpp"
 #include "nearest.hpp"   // rrt_nearest: the per-triangle function and the walk, shared with the host (tools/nearest_check.cpp)
+#include "multihit.hpp"  // rrt_trace_all: the triangle test, the slab test, the sorted insert and the walk, shared with the host (tools/trace_all_check.cpp)
 
 namespace rrtd {
 
@@ -32,7 +33,8 @@ enum { ERR_SHADING_NORMAL = 1, ERR_BETA = 4, ERR_NULL_BSDF = 8, ERR_MIPMAP = 16,
        ERR_KIND_SET = 256 /* a material produced a lobe outside the shading kernel's kind set (dmath.hpp): host-side selection error */,
        ERR_INGEST = 512 /* k_ingest_rays: a pixel or sample_num of rrt_ray_samples outside the film / outside 1 .. nsamp-1 */,
        ERR_SITE = 1024 /* k_sites_check: a site of rrt_sites that rrt_surface_at refuses */,
-       ERR_NEAREST = 2048 /* k_nearest / k_nearest_pairs_f32: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */ };
+       ERR_NEAREST = 2048 /* k_nearest / k_nearest_pairs_f32: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */,
+       ERR_TRACE_ALL = 4096 /* k_trace_all: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */ };
 static_assert(ERR_ST_DIMS == kErrStDims, "error bit shared with dmath.hpp");
 static_assert(ERR_HALTON_DIMS == kErrHaltonDims, "error bit shared with dmath.hpp");
 
@@ -2919,6 +2921,68 @@ __global__ void __launch_bounds__(kBlock) k_nearest(const Node<R>* nodes, uint32
     if (!nearest_walk<R>(nodes, n_nodes, tris, n_tris, insts, px, py, pz, io.prune0, io.delta, st, stack_cap, &best)) atomicOr(err, (uint32_t)ERR_NEAREST);
   }
   nearest_store<R>(io, g, best);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// All hits along a ray, in order (rrt_trace_all, include/rrt.h): one lane per ray over the linear tree (host/multihit.hpp multihit_walk). The stack
+// is private for trees up to 64 deep and [entry][thread of the launch] in global memory for deeper ones (DEEP), as k_closest's. The k-buffer holds
+// (t, prim) per slot in dynamic LDS, [slot][thread of the block] - k x blockDim x (sizeof(R) + 4) bytes, the t plane first -, so that no
+// runtime-indexed private array goes to scratch; b1 and b2 of the surviving slots are recomputed after the walk by the same triangle test. A lane
+// touches its own column only: no barrier. Ray base + i of the call is thread i; slot s of ray j is at [s * io.n + j].
+// ------------------------------------------------------------------------------------------------------------
+template <typename R>
+struct TraceAllIO {
+  const R *ox, *oy, *oz, *dx, *dy, *dz, *tmax;
+  const int32_t* skip;     // may be null
+  R* t;
+  int32_t* prim;
+  R *b1, *b2;              // both null or both set
+  uint32_t* count;         // may be null
+  size_t n;                // rays of the call: the stride of a slot plane
+  uint32_t k;
+  R delta;                 // kMultihitPadUlps x eps x M for scenes with kept instances, else 0
+};
+template <typename R>
+struct LdsHits {
+  R* ts;
+  int32_t* ps;
+  uint32_t stride;
+  RRT_DEV R t(uint32_t s) const { return ts[s * stride]; }
+  RRT_DEV int32_t prim(uint32_t s) const { return ps[s * stride]; }
+  RRT_DEV void set(uint32_t s, R t, int32_t p) { ts[s * stride] = t; ps[s * stride] = p; }
+};
+extern __shared__ double trace_all_lds[];
+template <typename R, bool DEEP>
+__global__ void __launch_bounds__(kBlock) k_trace_all(const Node<R>* nodes, uint32_t n_nodes, const Tri<R>* tris, uint32_t n_tris, const InstDev<R>* insts, uint32_t* err,
+                                                       TraceAllIO<R> io, size_t base, uint32_t n, uint32_t* stack, uint32_t stride, uint32_t stack_cap) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t g = base + i;
+  R* const lds_t = reinterpret_cast<R*>(trace_all_lds);
+  LdsHits<R> buf{lds_t + threadIdx.x, reinterpret_cast<int32_t*>(lds_t + (size_t)io.k * blockDim.x) + threadIdx.x, blockDim.x};
+  MhRay<R> r;
+  const bool live = mh_make_ray<R>(io.ox[g], io.oy[g], io.oz[g], io.dx[g], io.dy[g], io.dz[g], io.tmax[g], &r);
+  const int32_t skip = io.skip ? io.skip[g] : -1;
+  uint32_t count = 0u;
+  if (live) {
+    bool ok;
+    if (DEEP) { GlobStack st{stack + i, stride}; ok = multihit_walk<R>(nodes, n_nodes, tris, n_tris, insts, r, skip, io.delta, st, stack_cap, buf, io.k, &count); }
+    else { PrivStack st; ok = multihit_walk<R>(nodes, n_nodes, tris, n_tris, insts, r, skip, io.delta, st, stack_cap < 64u ? stack_cap : 64u, buf, io.k, &count); }
+    if (!ok) { atomicOr(err, (uint32_t)ERR_TRACE_ALL); count = 0u; }
+  }
+  if (io.count) io.count[g] = count;
+  const uint32_t held = count < io.k ? count : io.k;
+  for (uint32_t s = 0; s < io.k; s++) {
+    const size_t at = (size_t)s * io.n + g;
+    if (s < held) {
+      const int32_t p = buf.prim(s);
+      io.t[at] = buf.t(s); io.prim[at] = p;
+      if (io.b1) { const MhHit<R> h = mh_rehit<R>(r, tris[p], insts); io.b1[at] = h.u; io.b2[at] = h.v; }
+    } else {
+      io.t[at] = io.tmax[g]; io.prim[at] = -1;
+      if (io.b1) { io.b1[at] = R(0); io.b2[at] = R(0); }
+    }
+  }
 }
 
 }  // namespace rrtd

@@ -214,6 +214,23 @@ int rrt_nearest(rrt_handle* h, const rrt_points* pts, size_t n, double max_dist,
   return guarded([&]() { h->impl->nearest(pts, n, max_dist, out); });
 }
 
+int rrt_trace_all(rrt_handle* h, const rrt_rays* rays, size_t n, rrt_multi_hits* out) {
+  auto bad = [&](const char* what) { rrt::set_last_error(std::string("rrt_trace_all: ") + what); return (int)RRT_EINVAL; };
+  if (!rays) return bad("null ray description (rrt_rays)");
+  if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz || !rays->tmax) return bad("null ray array");
+  if (rays->mem != RRT_MEM_HOST && rays->mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (!out) return bad("null output description (rrt_multi_hits)");
+  if (out->k < 0 || out->k > RRT_MAX_HITS) return bad("k must be 0 .. RRT_MAX_HITS");
+  if (out->k > 0 && (!out->t || !out->prim)) return bad("null slot array (t and prim are needed with k > 0)");
+  if (out->k > 0 && ((out->b1 == nullptr) != (out->b2 == nullptr))) return bad("b1 and b2 must both be NULL or both be set");
+  if (out->k == 0 && !out->count) return bad("k == 0 needs count (the count-only form)");
+  if (out->mem != rays->mem) return bad("rays and outputs must live in the same memory kind");
+  if (n == 0) return bad("n must be > 0");
+  if (n > 0x7fffffffu) return bad("batch too large");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->trace_all(rays, n, out); });
+}
+
 int rrt_render_rays(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_xyzw, int film_mem,
                     rrt_render_stats* stats) {
   if (const int rc = ray_samples_check("rrt_render_rays", rays, false); rc != RRT_OK) return rc;

@@ -51,6 +51,7 @@ struct HandleBase {
   virtual void surface(const char* who, const rrt_rays* rays, const rrt_sites* sites, size_t n, const rrt_surface* out) = 0;
   virtual void atlas_sites(int32_t aw, int32_t ah, const int32_t* prims, size_t n_list, int mem, int32_t* site_prim, void* b1, void* b2, uint64_t* n_covered) = 0;
   virtual void nearest(const rrt_points* pts, size_t n, double max_dist, const rrt_nearest_out* out) = 0;
+  virtual void trace_all(const rrt_rays* rays, size_t n, const rrt_multi_hits* out) = 0;
   virtual void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film, int film_mem, rrt_render_stats* stats) = 0;   // p_film in rays->mem
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
@@ -758,6 +759,70 @@ class Handle : public HandleBase {
     HIP_CHECK(hipStreamSynchronize(st_));
     check_device_errors();
   }
+  // ---- all hits along a ray, in order: rrt_trace_all ---------------------------------------------------------------------------------------------
+  // One lane per ray, no pool and no queue, as nearest(): the rays are cut into passes of at most max_paths (and 2^20) rays only to bound the deep
+  // stack array, which the handle keeps between calls (trees deeper than 64 alone use it). A ray's result depends on the ray alone, so the cut
+  // changes no bit. The k-buffer is dynamic LDS, k x kBlock x (sizeof(R) + 4) bytes a block: 32 KiB in fp32 and 48 KiB in f64 at k = 16, so three
+  // f64 blocks fit the 160 KiB of a CU. Host arrays are staged and copied back per array.
+  void trace_all(const rrt_rays* rays, size_t n, const rrt_multi_hits* out) override {
+    const std::string who("rrt_trace_all");
+    check_args(who, kWhenIdle, Prec{"ray", rays->precision});
+    if (out->precision != precision()) throw std::invalid_argument(who + ": output precision must match the handle");
+    if (!nn_has_tri_) throw UnsupportedError(who + ": the scene has no triangle entry (spheres are not candidates)");
+    HIP_CHECK(hipSetDevice(dev_));
+    HIP_CHECK(hipMemsetAsync(counters_.p + C_ERROR, 0, sizeof(uint32_t), st_));
+    const bool host = rays->mem != RRT_MEM_DEVICE;
+    const size_t k = (size_t)out->k, kn = k * n;
+    const bool bary = k > 0 && out->b1 != nullptr;
+    DevBuf<R> stage_in, stage_out;
+    DevBuf<int32_t> stage_skip, stage_prim;
+    DevBuf<uint32_t> stage_count;
+    TraceAllIO<R> io{};
+    io.ox = (const R*)rays->ox; io.oy = (const R*)rays->oy; io.oz = (const R*)rays->oz; io.dx = (const R*)rays->dx; io.dy = (const R*)rays->dy; io.dz = (const R*)rays->dz;
+    io.tmax = (const R*)rays->tmax; io.skip = rays->skip_prim;
+    io.t = k ? (R*)out->t : nullptr; io.prim = k ? out->prim : nullptr; io.b1 = bary ? (R*)out->b1 : nullptr; io.b2 = bary ? (R*)out->b2 : nullptr; io.count = out->count;
+    io.n = n; io.k = (uint32_t)k; io.delta = mh_delta_;
+    if (host) {
+      stage_in.alloc(7 * n);
+      const void* src[7] = {rays->ox, rays->oy, rays->oz, rays->dx, rays->dy, rays->dz, rays->tmax};
+      for (int a = 0; a < 7; a++) HIP_CHECK(hipMemcpyAsync(stage_in.p + (size_t)a * n, src[a], n * sizeof(R), hipMemcpyHostToDevice, st_));
+      io.ox = stage_in.p; io.oy = stage_in.p + n; io.oz = stage_in.p + 2 * n; io.dx = stage_in.p + 3 * n; io.dy = stage_in.p + 4 * n; io.dz = stage_in.p + 5 * n; io.tmax = stage_in.p + 6 * n;
+      if (rays->skip_prim) { stage_skip.alloc(n); HIP_CHECK(hipMemcpyAsync(stage_skip.p, rays->skip_prim, n * sizeof(int32_t), hipMemcpyHostToDevice, st_)); io.skip = stage_skip.p; }
+      if (k) {
+        stage_out.alloc((bary ? 3 : 1) * kn); stage_prim.alloc(kn);
+        io.t = stage_out.p; io.prim = stage_prim.p;
+        if (bary) { io.b1 = stage_out.p + kn; io.b2 = stage_out.p + 2 * kn; }
+      }
+      if (out->count) { stage_count.alloc(n); io.count = stage_count.p; }
+    }
+    const size_t per_pass = std::min<size_t>({n, max_paths_, (size_t)1 << 20});
+    const uint32_t depth = scene_.stack_depth;
+    const size_t stride = (per_pass + kBlock - 1) / kBlock * kBlock;   // threads of a launch
+    if (deep_ && mh_stack_.n < (size_t)depth * stride) mh_stack_.alloc((size_t)depth * stride);
+    const size_t lds = k * (size_t)kBlock * (sizeof(R) + sizeof(int32_t));
+    for (size_t p0 = 0; p0 < n; p0 += per_pass) {
+      const uint32_t m = (uint32_t)std::min(per_pass, n - p0);
+      const dim3 grid((uint32_t)((m + kBlock - 1) / kBlock));
+      with_flag(deep_, [&](auto DEEP) {
+        hipLaunchKernelGGL((k_trace_all<R, DEEP()>), grid, dim3(kBlock), lds, st_, scene_.nodes, scene_.n_nodes, scene_.tris, scene_.n_tris, scene_.insts, counters_.p + C_ERROR, io, p0, m,
+                           deep_ ? mh_stack_.p : nullptr, (uint32_t)stride, depth);
+      });
+    }
+    HIP_CHECK(hipGetLastError());
+    if (host) {
+      if (k) {
+        HIP_CHECK(hipMemcpyAsync(out->t, io.t, kn * sizeof(R), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipMemcpyAsync(out->prim, io.prim, kn * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+        if (bary) {
+          HIP_CHECK(hipMemcpyAsync(out->b1, io.b1, kn * sizeof(R), hipMemcpyDeviceToHost, st_));
+          HIP_CHECK(hipMemcpyAsync(out->b2, io.b2, kn * sizeof(R), hipMemcpyDeviceToHost, st_));
+        }
+      }
+      if (out->count) HIP_CHECK(hipMemcpyAsync(out->count, io.count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+    }
+    HIP_CHECK(hipStreamSynchronize(st_));
+    check_device_errors();
+  }
   void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("rrt_render_rays", kWhenIdle, Prec{"ray", rays->precision}, {}, rect);
     if (s0 < 1 || s1 > desc_.sampler.samples_per_pixel || s0 >= s1) throw std::invalid_argument("rrt_render_rays: sample range outside [1, nsamp) or empty");
@@ -833,6 +898,7 @@ class Handle : public HandleBase {
     if (err & ERR_BETA) throw PanicError("path.rs:146 assert!(beta.y() > 0.0 && beta.y().is_finite())");
     if (err & ERR_KIND_SET) throw DeviceError("internal: a material produced a BxDF outside the kind set its shading kernel was selected for (shade_spec())");
     if (err & ERR_NEAREST) throw DeviceError("internal: a rrt_nearest walk passed its step or stack bound (the tree is not the tree its depth and node count describe)");
+    if (err & ERR_TRACE_ALL) throw DeviceError("internal: a rrt_trace_all walk passed its step or stack bound (the tree is not the tree its depth and node count describe)");
   }
   void render_bands(int rank, int world, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("render_bands", kAnyTime, {}, Ranks{rank, world});
@@ -1839,6 +1905,9 @@ class Handle : public HandleBase {
   R nn_delta_ = R(0);
   bool nn_has_tri_ = false, nn_pairs_on_ = false;
   DevBuf<uint32_t> nn_stack_;
+  // rrt_trace_all: the pad of the node boxes (host/multihit.hpp: kMultihitPadUlps x eps x M where the scene has a kept instance, else 0) and the deep stack
+  R mh_delta_ = R(0);
+  DevBuf<uint32_t> mh_stack_;
   DevBuf<uint2> nn_overflow_;
   uint32_t aov_serial_ = 0;   // k_aov_shade_frame's stamp of the pass last shaded: counted up per pass over the handle's life, never 0 in a record
 
@@ -1896,15 +1965,18 @@ class Handle : public HandleBase {
       double M = 0.0;
       if (!fs.nodes.empty()) for (int k = 0; k < 3; k++) M = std::max({M, std::fabs((double)fs.nodes[0].bmin[k]), std::fabs((double)fs.nodes[0].bmax[k])});
       nn_has_tri_ = false;
+      bool kept = false;
       for (const Tri<R>& t : fs.tris) {
         if (t.plane == kSphereMark) continue;
         nn_has_tri_ = true;
         if ((t.material & kInstFlag) == 0u) continue;
+        kept = true;
         const R* m = fs.insts[(t.material >> 16) & 0x7fffu].m;
         for (const R* v : {t.p0, t.p1, t.p2}) for (int i = 0; i < 3; i++)
           M = std::max(M, std::fabs((double)m[4 * i] * (double)v[0]) + std::fabs((double)m[4 * i + 1] * (double)v[1]) + std::fabs((double)m[4 * i + 2] * (double)v[2]) + std::fabs((double)m[4 * i + 3]));
       }
       nn_delta_ = (R)((double)kNearestPadUlps * (double)NnConst<R>::eps * M);
+      mh_delta_ = kept ? (R)((double)kMultihitPadUlps * (double)NnConst<R>::eps * M) : R(0);
     }
     shade_kinds_scene_ = fs.used.shade == ShadeClass::Lambert ? kKindsLambert : (fs.used.shade == ShadeClass::Glossy ? kKindsGlossy : kAllKinds);
     shade_kinds_ = shade_kinds_scene_;
