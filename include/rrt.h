@@ -355,6 +355,22 @@ int rrt_trace_any(rrt_handle*, const rrt_rays* rays, size_t n, uint8_t* occluded
 int rrt_camera_samples(rrt_handle*, const int32_t rect[4], uint64_t s0, uint64_t s1,
                        double* dims5, double* ray_od6, double* weight);
 
+/* The sampler's unit-test surface, as rrt_camera_samples is the camera's: the values the frame's kernels draw, from the device functions they
+ * call (halton_pixel_offset, draw_1d, draw_2d of dmath.hpp). All arrays are the host's; the values are doubles in both precisions, because the
+ * sampler produces f64 in both. Stream i is (pixel[i] = y << 16 | x inside the film, sample_num[i] in 0 .. nsamp-1).
+ *   index[i]                     the word the kernels carry for the stream (may be NULL): HaltonSampler halton_pixel_offset + sample_num * stride
+ *                                (Halton::get_index_for_sample halton.rs:75-105), StratifiedSampler (y * xres + x) << 10 | sample_num
+ *   v1[i * count + k]            what get_1d returns with the stream's 1D counter at first + k: HaltonSampler dimension first + k
+ *   v2[(i * count + k) * 2 ..]   what get_2d returns with the counter at first + k: HaltonSampler dimensions first + k and first + k + 1,
+ *                                StratifiedSampler its 2D counter (which counts apart from the 1D one)
+ * The handle's options apply as they do to a frame ("halton_tables"; "cam_tables" belongs to the camera kernels, which this call does not run).
+ * Leaves the handle as it was and never sets a device error bit: RRT_EINVAL, before any device work, for NULL arguments (index excepted), n == 0,
+ * count == 0, n * count > 2^31 - 1, a pixel outside the film, sample_num >= nsamp, first + count >= 1000 under the HaltonSampler (v2 would read
+ * dimension 1000), first + count > 4095 under the StratifiedSampler (a counter of 4095), a frame in flight. RRT_EUNSUP / RRT_EPANIC as
+ * rrt_render_rect gives for the scene's sampler. */
+int rrt_sampler_values(rrt_handle*, const uint32_t* pixel, const uint32_t* sample_num, size_t n, uint32_t first, uint32_t count,
+                       uint64_t* index /* n, may be NULL */, double* v1 /* n x count */, double* v2 /* n x count x 2 */);
+
 /* SamplerIntegrator::si_render integrator/mod.rs:48-139 restricted to pixel rect [x0,y0,x1,y1):
  * all samples of those pixels, Li by the scene's integrator, FilmTile::add_sample + merge_film_tile.
  * film_xyzw: full-frame W*H*4 buffer (handle precision, host or device per film_mem); only pixels the

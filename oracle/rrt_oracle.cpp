@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -2599,6 +2600,33 @@ int oracle_camera_samples(const rrt_scene_desc* d, const int32_t rect[4], uint64
           else for (int q = 0; q < 6; q++) ro[q] = 0.0;
         }
       }
+  });
+}
+
+// rrt_sampler_values over the oracle's own Sampler: get_1d / get_2d of stream (pixel, sample_num) with its counter at first + k. HaltonSampler:
+// `dimension` is set to first + k before each draw; StratifiedSampler: the 1D / 2D counter (8 bits here, so first + count <= 256).
+int oracle_sampler_values(const rrt_scene_desc* d, const uint32_t* pixel, const uint32_t* sample_num, size_t n, uint32_t first, uint32_t count, uint64_t* index,
+                          double* v1, double* v2) {
+  return guarded([&]() {
+    check_supported(d);
+    const bool st = d->sampler.type == RRT_SAMPLER_STRATIFIED;
+    if (st && (uint64_t)first + count > 256u) throw std::invalid_argument("oracle_sampler_values: the oracle's Stratified counters are 8 bits");
+    for (size_t i = 0; i < n; i++) {
+      const int64_t px = pixel[i] & 0xffffu, py = pixel[i] >> 16;
+      if (px >= d->film.xres || py >= d->film.yres || sample_num[i] >= d->sampler.samples_per_pixel) throw std::invalid_argument("oracle_sampler_values: stream outside the film or the samples");
+      Sampler s; s.h = &d->sampler; s.xres = d->film.xres;
+      s.start_pixel(px, py);
+      s.current_pixel_sample_index = sample_num[i];
+      uint64_t idx = ((uint64_t)(py * (int64_t)d->film.xres + px) << 10) | sample_num[i];
+      if (!st) idx = s.interval_sample_index = s.get_index_for_sample(sample_num[i]);
+      if (index) index[i] = idx;
+      for (uint32_t k = 0; k < count; k++) {
+        s.dimension = first + k; s.cur1d = first + k;
+        v1[i * count + k] = s.get_1d();
+        s.dimension = first + k; s.cur2d = first + k;
+        s.get_2d(&v2[2 * (i * count + k)], &v2[2 * (i * count + k) + 1]);
+      }
+    }
   });
 }
 

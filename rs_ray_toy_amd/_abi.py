@@ -251,6 +251,7 @@ PROTOTYPES = {
     "rrt_trace_any": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.c_void_p]),
     "rrt_camera_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "rrt_sampler_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rrt_render_rect": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_radiance": (C.c_int, [C.c_void_p, C.POINTER(RaySamples), C.c_size_t, C.c_void_p]),
     "rrt_render_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, C.POINTER(RaySamples), C.c_void_p, C.c_void_p, C.c_int,

@@ -203,6 +203,20 @@ class Renderer:
         _check(A.lib().rrt_camera_samples(self._h, r, s0, s1, dims.ctypes.data, rays.ctypes.data, w.ctypes.data))
         return dims, rays, w
 
+    def sampler_values(self, pixel, sample_num, first, count):
+        """rrt_sampler_values: what the kernels' sampler draws for the streams (pixel, sample_num) with the counter at first .. first + count - 1.
+        pixel (n, 2) of (x, y) or (n,) packed y << 16 | x; sample_num (n,) in 0 .. nsamp-1. Returns index (n,) uint64, v1 (n, count) and
+        v2 (n, count, 2) float64."""
+        pixel = np.asarray(pixel)
+        if pixel.ndim == 2:
+            pixel = (pixel[:, 1].astype(np.uint32) << 16) | pixel[:, 0].astype(np.uint32)
+        pixel = np.ascontiguousarray(pixel, np.uint32); sample_num = np.ascontiguousarray(sample_num, np.uint32)
+        n = len(sample_num)
+        assert pixel.shape == (n,)
+        index = np.zeros(n, np.uint64); v1 = np.zeros((n, max(count, 0))); v2 = np.zeros((n, max(count, 0), 2))
+        _check(A.lib().rrt_sampler_values(self._h, pixel.ctypes.data, sample_num.ctypes.data, n, first, count, index.ctypes.data, v1.ctypes.data, v2.ctypes.data))
+        return index, v1, v2
+
     # SamplerIntegrator::si_render (integrator/mod.rs:48) over a pixel rect; returns (H, W, 4) XYZ+weight film
     def render(self, rect=None, film=None, stats=False):
         W, H = self.scene.resolution

@@ -619,6 +619,27 @@ __global__ void __launch_bounds__(kBlock) k_raygen(SceneDev<R> s, Pools<R> p, Pa
   if (alive) p.q_next[q] = QEnt{slot, 0u, 0u, 0u};
 }
 
+// unit-test surface of rrt_sampler_values: one thread per (stream, k). The index word is formed as k_raygen forms it, and the values are what
+// draw_1d / draw_2d return with the stream's counter at first + k - the very device functions the frame calls (dmath.hpp), no copies. The host has
+// checked the pixels, the sample numbers and the counter range (no draw reaches ERR_HALTON_DIMS / ERR_ST_DIMS) and n * count < 2^31.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) k_sampler_values(SceneDev<R> s, const uint32_t* pixel, const uint32_t* sample_num, uint32_t n, uint32_t first, uint32_t count,
+                                                           unsigned long long* index_out, double* v1, double* v2) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n * count) return;
+  const uint32_t i = t / count, k = t - i * count;
+  const uint32_t pw = pixel[i], px = pw & 0xffffu, py = pw >> 16, sn = sample_num[i];
+  const bool st = s.sampler_type == 1u;
+  const uint32_t index = st ? (((py * (uint32_t)s.xres + px) << 10) | sn) : halton_pixel_offset(s, px, py) + sn * s.stride;
+  if (k == 0 && index_out) index_out[i] = index;
+  uint32_t d = first + k;                                 // the 1D counter (StratifiedSampler: the low kStBits; HaltonSampler: the dimension)
+  v1[t] = draw_1d(s, index, &d);
+  d = st ? (first + k) << kStBits : first + k;            // the 2D counter
+  double a, b;
+  draw_2d(s, index, &d, &a, &b);
+  v2[2 * (size_t)t] = a; v2[2 * (size_t)t + 1] = b;
+}
+
 // k_raygen over a listed pass (list_pixel): the same statements per slot, HaltonSampler only (rrt_render_adaptive refuses the StratifiedSampler)
 // and without the debug dimensions. A kernel of its own, so that the kernel every other pass launches stays the code it is.
 template <typename R>

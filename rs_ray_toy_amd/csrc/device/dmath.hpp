@@ -316,12 +316,15 @@ RRT_DEV void halton_cam4(const SceneDev<R>& s, uint32_t index, double* d0, doubl
   if (s.sample_at_center) { *d0 = 0.5; *d1 = 0.5; }
   else {
     *d0 = (double)__brev(index >> s.base_exp0) * 2.3283064365386963e-10;
-    uint32_t a = (uint32_t)((double)index * s.inv_base_scale1), rev = 0, k = 0;   // index / 3^base_exponents[1], exact after the fix-up (cf. div_base())
+    uint32_t a = (uint32_t)((double)index * s.inv_base_scale1), k = 0;   // index / 3^base_exponents[1], exact after the fix-up (cf. div_base())
     { const uint32_t r = index - a * s.base_scale1; if ((int32_t)r < 0) a -= 1u; else if (r >= s.base_scale1) a += 1u; }
+    // 64 bits, as radical_inverse_dev keeps them: on a film one row high base_scale1 is 1, a is the whole index, and from 3^20 on it has 21
+    // base-3 digits, whose reversal reaches 3^21 - 1 > 2^32 (tests/test_sampler_shapes.py, the 128x1 film at the largest nsamp)
+    uint64_t rev = 0;
     if (tab && a >= kCamB3) {
       const uint32_t hi = a / kCamB3, lo = a - hi * kCamB3;
       const uint4 e = s.cam_hi[0][hi];
-      rev = s.cam_lo[0][lo] * e.y + e.x;
+      rev = (uint64_t)s.cam_lo[0][lo] * e.y + e.x;
       *d1 = fmin((double)rev * __hiloint2double((int)e.w, (int)e.z), 0.99999999999999989);
     } else {
       while (a != 0) { const uint32_t q = div3(a); rev = rev * 3u + (a - q * 3u); a = q; k++; }

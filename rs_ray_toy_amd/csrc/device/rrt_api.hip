@@ -80,6 +80,16 @@ int rrt_camera_samples(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64
   return guarded([&]() { h->impl->camera_samples(rect, s0, s1, dims5, ray_od6, weight); });
 }
 
+int rrt_sampler_values(rrt_handle* h, const uint32_t* pixel, const uint32_t* sample_num, size_t n, uint32_t first, uint32_t count, uint64_t* index, double* v1, double* v2) {
+  auto bad = [&](const char* what) { rrt::set_last_error(std::string("rrt_sampler_values: ") + what); return (int)RRT_EINVAL; };
+  if (!pixel || !sample_num || !v1 || !v2) return bad("null argument");
+  if (n == 0) return bad("n must be > 0");
+  if (n > 0x7fffffffu) return bad("batch too large");
+  if (count == 0) return bad("count must be > 0");
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->sampler_values(pixel, sample_num, n, first, count, index, v1, v2); });
+}
+
 int rrt_render_rect(rrt_handle* h, const int32_t rect[4], void* film_xyzw, int film_mem, rrt_render_stats* stats) {
   if (!h || !rect || !film_xyzw) { rrt::set_last_error("rrt_render_rect: null argument"); return RRT_EINVAL; }
   if (film_mem != RRT_MEM_HOST && film_mem != RRT_MEM_DEVICE) { rrt::set_last_error("rrt_render_rect: bad film_mem"); return RRT_EINVAL; }

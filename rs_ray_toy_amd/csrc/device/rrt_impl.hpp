@@ -43,6 +43,7 @@ struct HandleBase {
   virtual void trace_closest(const rrt_rays* rays, size_t n, rrt_hits* out) = 0;
   virtual void trace_any(const rrt_rays* rays, size_t n, uint8_t* occluded) = 0;
   virtual void camera_samples(const int32_t rect[4], uint64_t s0, uint64_t s1, double* dims5, double* ray_od6, double* weight) = 0;
+  virtual void sampler_values(const uint32_t* pixel, const uint32_t* sample_num, size_t n, uint32_t first, uint32_t count, uint64_t* index /* may be NULL */, double* v1, double* v2) = 0;
   virtual void render_rect(const int32_t rect[4], void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void radiance(const rrt_ray_samples* rays, size_t n, void* rgb4) = 0;
   // rrt_irradiance (od6 NULL; sh27 may be NULL) and rrt_irradiance_rays (od6 set, sums4 and sh27 NULL) under the name `who`
@@ -369,6 +370,38 @@ class Handle : public HandleBase {
     HIP_CHECK(hipMemcpyAsync(dims5, dd.p, 5 * n * sizeof(double), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipMemcpyAsync(ray_od6, dr.p, 6 * n * sizeof(double), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipMemcpyAsync(weight, dw.p, n * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+  }
+
+  // rrt_sampler_values: the sampler's unit-test surface (k_sampler_values). Everything is checked on the host first, so the kernel sets no error
+  // bit; it touches neither the pools nor the counters, so the handle is left as it was.
+  void sampler_values(const uint32_t* pixel, const uint32_t* sample_num, size_t n, uint32_t first, uint32_t count, uint64_t* index, double* v1, double* v2) override {
+    const std::string who = "rrt_sampler_values";
+    check_args(who, kWhenIdle);
+    const rrt_film& f = desc_.film;
+    const uint64_t nsamp = desc_.sampler.samples_per_pixel, total = (uint64_t)n * count;
+    if (total > 0x7fffffffu) throw std::invalid_argument(who + ": batch too large (n * count)");
+    const bool st = desc_.sampler.type == RRT_SAMPLER_STRATIFIED;
+    if (!st && (uint64_t)first + count >= 1000u) throw std::invalid_argument(who + ": the range reaches Halton dimension 1000 (v2 reads dimension first + count)");
+    if (st && (uint64_t)first + count > (uint64_t)kStMask) throw std::invalid_argument(who + ": the range reaches Stratified counter 4095");
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t pw = pixel[i];
+      if ((int32_t)(pw & 0xffffu) >= f.xres || (int32_t)(pw >> 16) >= f.yres) throw std::invalid_argument(who + ": pixel outside the film (stream " + std::to_string(i) + ")");
+      if (sample_num[i] >= nsamp) throw std::invalid_argument(who + ": sample_num outside 0 .. nsamp-1 (stream " + std::to_string(i) + ")");
+    }
+    device_prologue(/*film=*/false);
+    DevBuf<uint32_t> du;
+    DevBuf<unsigned long long> di;
+    DevBuf<double> dv;
+    du.alloc(2 * n); di.alloc(n); dv.alloc(3 * total);
+    HIP_CHECK(hipMemcpyAsync(du.p, pixel, n * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+    HIP_CHECK(hipMemcpyAsync(du.p + n, sample_num, n * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+    hipLaunchKernelGGL((k_sampler_values<R>), dim3((uint32_t)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st_, scene_, du.p, du.p + n, (uint32_t)n, first, count, di.p, dv.p,
+                       dv.p + total);
+    HIP_CHECK(hipGetLastError());
+    if (index) HIP_CHECK(hipMemcpyAsync(index, di.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(v1, dv.p, total * sizeof(double), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(v2, dv.p + total, 2 * total * sizeof(double), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
   }
 

@@ -32,6 +32,7 @@ def lib():
         L.oracle_trace_closest_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4
         L.oracle_trace_any_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
         L.oracle_camera_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_sampler_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_render_rect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.oracle_mip_census.restype = None
         L.oracle_mip_census.argtypes = [C.c_void_p, C.c_int]
@@ -129,6 +130,17 @@ def camera_samples(scene, rect, s0, s1):
     r = (C.c_int32 * 4)(*rect)
     _check(lib().oracle_camera_samples(_d(scene), r, s0, s1, dims.ctypes.data, rays.ctypes.data, w.ctypes.data))
     return dims, rays, w
+
+
+def sampler_values(scene, pixel, sample_num, first, count):
+    """Renderer.sampler_values over the oracle's Sampler: pixel (n, 2) of (x, y), sample_num (n,); returns index (n,) uint64, v1 (n, count), v2 (n, count, 2)."""
+    pixel = np.asarray(pixel)
+    word = np.ascontiguousarray((pixel[:, 1].astype(np.uint32) << 16) | pixel[:, 0].astype(np.uint32), np.uint32)
+    sample_num = np.ascontiguousarray(sample_num, np.uint32)
+    n = len(sample_num)
+    index = np.zeros(n, np.uint64); v1 = np.zeros((n, count)); v2 = np.zeros((n, count, 2))
+    _check(lib().oracle_sampler_values(_d(scene), word.ctypes.data, sample_num.ctypes.data, n, first, count, index.ctypes.data, v1.ctypes.data, v2.ctypes.data))
+    return index, v1, v2
 
 
 def render(scene, rect=None, n_threads=0, faithful_sampler_rebuild=False, stats=False, flat=False):

@@ -48,6 +48,7 @@ CALLS = {
     "render_bands": ("render_bands", lambda r, rect=FULL, rank=0, world=1: r.render_bands(rank, world)),
     "render_bands_begin": ("render_bands", lambda r, rect=FULL, rank=0, world=1: r.render_bands_begin(rank, world, r._frame.data_ptr())),
     "camera_samples": ("camera_samples", lambda r, rect=FULL, rank=0, world=1: r.camera_samples(rect, 1, 2)),
+    "sampler_values": ("rrt_sampler_values", lambda r, rect=FULL, rank=0, world=1: r.sampler_values(np.zeros((1, 2), np.int64), np.ones(1, np.int64), 0, 4)),
     "radiance": ("rrt_radiance", lambda r, rect=FULL, rank=0, world=1: r.radiance(*_rays(1), np.zeros((1, 2), np.int64), np.ones(1, np.int64))),
     "render_rays": ("rrt_render_rays", lambda r, rect=FULL, rank=0, world=1: r.render_rays(rect, 1, 2, np.concatenate(_rays(_n(rect)), 1), None,
                                                                                           np.full((_n(rect), 2), 0.5, r.dtype))),
@@ -70,7 +71,7 @@ CALLS = {
 RANKED = ("render_bands", "render_bands_begin", "render_moments", "render_frame_aov", "render_passes", "render_aov", "render_aov_follow", "render_ao", "render_mattes")
 RECTS = ("render_rays", "render_moments", "render_frame_aov", "render_passes", "render_aov", "render_aov_follow", "render_ao", "render_mattes")
 TILED = ("render_adaptive", "tile_error")      # whole 8 x 8 tiles: only a rect beyond the film reaches the handle
-IDLE = ("radiance", "render_rays", "render_moments", "render_frame_aov", "render_passes", "render_adaptive", "tile_error", "render_aov", "render_aov_follow",
+IDLE = ("sampler_values", "radiance", "render_rays", "render_moments", "render_frame_aov", "render_passes", "render_adaptive", "tile_error", "render_aov", "render_aov_follow",
         "render_ao", "render_mattes", "matte_extract", "denoise", "denoise_moments")
 PRECISION = {"radiance": "ray", "render_rays": "ray", "render_frame_aov": "plane", "render_aov": "plane", "render_aov_follow": "plane", "render_ao": "plane",
              "render_mattes": "table", "matte_extract": "table", "denoise": "plane", "denoise_moments": "plane"}
