@@ -649,6 +649,66 @@ typedef struct rrt_multi_hits {
 } rrt_multi_hits;
 int rrt_trace_all(rrt_handle*, const rrt_rays* rays, size_t n, rrt_multi_hits* out);
 
+/* Mutual visibility of two point sets as a packed bit matrix (no counterpart in the reference; defined geometrically by rrt_trace_all's acceptance
+ * rules): can point a_i see point b_j, for n_a x n_b pairs - what form factors, light-visibility and PVS precomputation, sun-hour and sky-view
+ * studies (points x directions), soft shadows from a sampled emitter and line-of-sight analysis reduce to. rrt_trace_any is the reference's shadow
+ * ray with its quirks (Q9 - Q11) and no geometric occlusion test; rrt_trace_all with k = 0 gives the clean answer (count == 0) but walks the whole
+ * ray and makes the caller build and ship n_a x n_b rays of 7 values and reduce as many counts. Here the segments are made on the device from the
+ * two sets, a walk stops at the first accepted candidate, and one bit per pair comes back. rrt_points is reused, so a record set, an atlas site
+ * set or an irradiance point set passes as it is; `pixel` is ignored. All arrays in a->mem; element type = the handle's precision R.
+ *   Everything below is computed in R, no operation contracted to an fma, divisions and square roots IEEE, dot and cross as for rrt_trace_all.
+ *   Normals: where a set's nx, ny, nz are given (all three or none), nn = n / sqrt(dot(n, n)) per component. A point whose normal is zero or not
+ *     finite (or whose nn is not finite) is dead; so is a point with a non-finite coordinate or a non-finite origin / target below.
+ *   Origin: o_i = a_i + nn_a * (R)offset_a where A has normals, otherwise a_i.
+ *   RRT_VIS_POINTS: q_j = b_j + nn_b * (R)offset_b where B has normals, otherwise b_j; w = q - o, len = sqrt(dot(w, w)), d = w / len per component,
+ *     tmax = len. len == 0: nothing lies between the points, the pair is visible iff no FACING flag is set. len not finite: not visible.
+ *   RRT_VIS_DIRECTIONS: B holds directions (sun positions, sky samples): w = b_j, len = sqrt(dot(w, w)), d = w / len, tmax = +inf. A zero or
+ *     non-finite direction (or len) is a dead column.
+ *   Facing: RRT_VIS_FACING_A requires dot(nn_a, w) > 0, RRT_VIS_FACING_B requires dot(nn_b, w) < 0. A pair that fails is not visible and not traced.
+ *   Blocked: a pair is blocked iff some triangle entry of prim_order other than skip_a[i] and skip_b[j] (indices into prim_order as
+ *     rrt_rays.skip_prim; -1 or a NULL array = none) is accepted for the ray (o, d, tmax) by rrt_trace_all's rules (i) - (iii) above - the same
+ *     functions of csrc/host/multihit.hpp on the same operands. Whether an accepted candidate exists does not depend on the order the candidates
+ *     are looked at, so the answer is that of a scan over all entries and independent of the tree; rule (iii) and the grown node boxes of scenes
+ *     with kept instances make the walk find what the scan finds, as for rrt_trace_all. No prune margin is involved: the walk opens every node whose
+ *     box passes and leaves at the first accepted candidate. Bit for bit, pair (i, j) is visible iff rrt_trace_all reports count == 0 for that ray.
+ *   Bit (i, j) = both points live, facing passed, not blocked.
+ *   RRT_VIS_MATRIX: pair (i, j) is bit j & 63 of bits[i * words + j / 64], words = (n_b + 63) / 64; the unused high bits of a row's last word are 0.
+ *     count[i] (may be NULL) = the number of set bits of row i.
+ *   RRT_VIS_PAIRS: requires n_b == n_a; pair (i, i) is bit i & 63 of bits[i / 64], unused bits 0; count must be NULL.
+ *   The outputs are overwritten. The result depends neither on how the call is cut into launches (option "max_paths") nor on `mem`.
+ * Errors, before any device work, the structs checked before the handle: RRT_EINVAL for NULL a, b, out, bits or coordinate arrays; normals of which
+ * only some are given; a bad mem, or a->mem, b->mem, out->mem not all equal; a precision that is not the handle's; n_a == 0, n_b == 0, either above
+ * 2^31 - 1, or n_a * n_b > 2^40; a bad mode, b_kind or flag bit; a NaN or infinite offset; a non-zero offset or a FACING flag for a set without
+ * normals; in RRT_VIS_DIRECTIONS B normals, offset_b != 0, RRT_VIS_FACING_B or skip_b; in RRT_VIS_PAIRS n_b != n_a or a non-NULL count; a frame in
+ * flight. RRT_EUNSUP for a scene with no triangle entry, as rrt_trace_all gives. The call leaves the handle as it was (a frame rendered before and
+ * after is the same frame).
+ * Not provided: sphere candidates, per-column counts, distances or the blocking primitive (that is rrt_trace_all), a per-pair weight or form-factor
+ * kernel, a _begin / _end form.
+ * Measured (tools/visibility_time.py, profiles/visibility_time.json; config 4, fp32, everything in device memory, one MI355X):
+ * 4 096 x 4 096 atlas sites lifted 1e-3 of the extent (16.8 M pairs, 8.8 % visible), bits and count: 15.1 ms (0.90 ns per pair) against 45.0 ms for
+ * the only route the parent commit offers - torch builds the same segments, rrt_trace_all with k = 0 in chunks of 2^22 rays, torch packs
+ * count == 0 - (0.34 x); 65 536 sites x 256 directions of the upper hemisphere with RRT_VIS_FACING_A (68.6 % visible): 10.4 ms against 17.5 ms
+ * (0.59 x; the route gives pairs that fail the facing test a zero direction, which costs it no walk). Both routes leave the same words and counts,
+ * bit for bit. The time is the kernel's: the device time of a call is 99.9 % of its wall time. One rrt_trace_any pass over the same segments,
+ * without building or packing anything, takes 7.2 / 5.0 ms - it is the reference's shadow ray on the pair-node tree with the fast reciprocal, and it
+ * answers otherwise on 7.3 % / 1.9 % of the pairs (Q9 - Q11). count comes from one atomicAdd per word; a per-row reduction was not measured, nor was
+ * refilling idle lanes. bench.py (23.10 / 23.01 / 23.10 ms per frame) is the parent build's (22.85 / 23.31 / 22.98), run alternately. */
+enum { RRT_VIS_MATRIX = 0, RRT_VIS_PAIRS = 1 };           /* mode */
+enum { RRT_VIS_POINTS = 0, RRT_VIS_DIRECTIONS = 1 };      /* b_kind */
+enum { RRT_VIS_FACING_A = 1, RRT_VIS_FACING_B = 2 };      /* flags */
+typedef struct rrt_vis_params {
+  int32_t mode, b_kind; uint32_t flags; int32_t pad;
+  double offset_a, offset_b;          /* rounded to the handle's type R */
+  const int32_t *skip_a, *skip_b;     /* may be NULL; n_a / n_b entries of prim_order (as rrt_rays.skip_prim), -1 = none; in a->mem */
+} rrt_vis_params;                     /* NULL = {MATRIX, POINTS, 0, 0, 0, NULL, NULL} */
+typedef struct rrt_vis_out {
+  int32_t mem, pad;
+  uint64_t* bits;                     /* MATRIX: n_a * words, words = (n_b + 63) / 64; PAIRS: (n_a + 63) / 64 */
+  uint32_t* count;                    /* MATRIX: n_a, visible columns of row i; may be NULL. PAIRS: must be NULL */
+} rrt_vis_out;
+int rrt_visibility(rrt_handle*, const rrt_points* a, size_t n_a, const rrt_points* b, size_t n_b,
+                   const rrt_vis_params* params, rrt_vis_out* out);
+
 /* Multi-GPU film partition: the same, for the rows of the interleaved 16-row tile bands b with
  * b % world == rank (tile height of integrator/mod.rs:55), rendered as one pixel set. Box filter: the ranks' films are
  * disjoint; wider filters: a sample's splat may land in a neighbour's rows of this rank's film. Either way summing

@@ -183,6 +183,20 @@ class MultiHits(C.Structure):
                 ("b2", C.c_void_p), ("count", C.c_void_p)]
 
 
+RRT_VIS_MATRIX, RRT_VIS_PAIRS = 0, 1
+RRT_VIS_POINTS, RRT_VIS_DIRECTIONS = 0, 1
+RRT_VIS_FACING_A, RRT_VIS_FACING_B = 1, 2
+
+
+class VisParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("b_kind", C.c_int32), ("flags", C.c_uint32), ("pad", C.c_int32), ("offset_a", C.c_double), ("offset_b", C.c_double),
+                ("skip_a", C.c_void_p), ("skip_b", C.c_void_p)]
+
+
+class VisOut(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("pad", C.c_int32), ("bits", C.c_void_p), ("count", C.c_void_p)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("camera_samples", C.c_uint64), ("camera_rays", C.c_uint64), ("closest_queries", C.c_uint64),
                 ("any_queries", C.c_uint64), ("nodes_visited", C.c_uint64), ("prims_tested", C.c_uint64),
@@ -263,6 +277,7 @@ PROTOTYPES = {
     "rrt_atlas_sites": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rrt_nearest": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.c_double, C.POINTER(NearestOut)]),
     "rrt_trace_all": (C.c_int, [C.c_void_p, C.POINTER(Rays), C.c_size_t, C.POINTER(MultiHits)]),
+    "rrt_visibility": (C.c_int, [C.c_void_p, C.POINTER(Points), C.c_size_t, C.POINTER(Points), C.c_size_t, C.POINTER(VisParams), C.POINTER(VisOut)]),
     "rrt_render_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(RenderStats)]),
     "rrt_render_bands_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "rrt_render_end": (C.c_int, [C.c_void_p]),

@@ -532,6 +532,48 @@ class Renderer:
         out = A.MultiHits(A.RRT_MEM_DEVICE, self.precision, int(k), 0, out_ptrs.get("t"), out_ptrs.get("prim"), out_ptrs.get("b1"), out_ptrs.get("b2"), out_ptrs.get("count"))
         _check(A.lib().rrt_trace_all(self._h, C.byref(rays), n, C.byref(out)))
 
+    # mutual visibility of two point sets as a packed bit matrix (rrt_visibility)
+    @staticmethod
+    def _vis_params(offset_a, offset_b, facing_a, facing_b, directions, pairs, skip_a_ptr, skip_b_ptr):
+        flags = (A.RRT_VIS_FACING_A if facing_a else 0) | (A.RRT_VIS_FACING_B if facing_b else 0)
+        return A.VisParams(A.RRT_VIS_PAIRS if pairs else A.RRT_VIS_MATRIX, A.RRT_VIS_DIRECTIONS if directions else A.RRT_VIS_POINTS, flags, 0, float(offset_a), float(offset_b),
+                           skip_a_ptr, skip_b_ptr)
+
+    def visibility(self, a, b, na=None, nb=None, offset_a=0, offset_b=0, facing_a=False, facing_b=False, directions=False, pairs=False, skip_a=None, skip_b=None, count=True):
+        """rrt_visibility over host arrays: points a (n_a, 3) and b (n_b, 3; with directions=True the directions themselves), optional normals na, nb
+        of the same shapes - the ends are moved offset_a / offset_b along the unit normals, facing_a / facing_b require the segment to leave a's side
+        and arrive on b's -, skip_a / skip_b one entry of prim_order per point to leave out (-1 = none). Returns dict(bits (n_a, words) uint64,
+        words = (n_b + 63) // 64, bit j & 63 of word j // 64 of row i = a_i sees b_j; count (n_a,) uint32 = the set bits of each row, with
+        count=True); pairs=True (n_b == n_a): bits (words,) for the pairs (i, i) and no count. unpack_visibility() turns bits into a bool array.
+        Blocked = a triangle accepted by trace_all's rules lies on the segment; spheres are not candidates."""
+        n_a, n_b = len(np.asarray(a)), len(np.asarray(b))
+        pa, keep_a = self._points(a, na, None)
+        pb, keep_b = self._points(b, nb, None)
+        sa = None if skip_a is None else np.ascontiguousarray(skip_a, np.int32)
+        sb = None if skip_b is None else np.ascontiguousarray(skip_b, np.int32)
+        prm = self._vis_params(offset_a, offset_b, facing_a, facing_b, directions, pairs, None if sa is None else sa.ctypes.data, None if sb is None else sb.ctypes.data)
+        bits = np.zeros((n_a + 63) // 64 if pairs else (n_a, (n_b + 63) // 64), np.uint64)
+        cnt = np.zeros(n_a, np.uint32) if count and not pairs else None
+        out = A.VisOut(A.RRT_MEM_HOST, 0, bits.ctypes.data, None if cnt is None else cnt.ctypes.data)
+        _check(A.lib().rrt_visibility(self._h, C.byref(pa), n_a, C.byref(pb), n_b, C.byref(prm), C.byref(out)))
+        return dict(bits=bits, count=cnt)
+
+    def visibility_device(self, ptrs, n_a, n_b, offset_a=0, offset_b=0, facing_a=False, facing_b=False, directions=False, pairs=False):
+        """rrt_visibility on device-resident arrays (raw pointers): ptrs = {"a": (px, py, pz), "b": (px, py, pz), "bits": pointer to the uint64 words,
+        and optionally "na", "nb": (nx, ny, nz), "skip_a", "skip_b": int32 arrays, "count": n_a uint32}."""
+        none3 = (None, None, None)
+        pa = A.Points(A.RRT_MEM_DEVICE, self.precision, *ptrs["a"], *(ptrs.get("na") or none3), None)
+        pb = A.Points(A.RRT_MEM_DEVICE, self.precision, *ptrs["b"], *(ptrs.get("nb") or none3), None)
+        prm = self._vis_params(offset_a, offset_b, facing_a, facing_b, directions, pairs, ptrs.get("skip_a"), ptrs.get("skip_b"))
+        out = A.VisOut(A.RRT_MEM_DEVICE, 0, ptrs["bits"], ptrs.get("count"))
+        _check(A.lib().rrt_visibility(self._h, C.byref(pa), n_a, C.byref(pb), n_b, C.byref(prm), C.byref(out)))
+
+    def sky_view(self, p, n, directions, offset=0.0):
+        """The share of `directions` (m, 3) each point p (k, 3) with normal n sees unblocked and in front of its surface: visibility(directions=True,
+        facing_a=True) count / m, as (k,) float64 - a sky-view factor for directions spread evenly over the sky, sun hours for sun positions."""
+        directions = np.asarray(directions)
+        return self.visibility(p, directions, na=n, offset_a=offset, facing_a=True, directions=True)["count"].astype(np.float64) / len(directions)
+
     # three fixed, mutually skew directions (no two parallel, none along an axis or a face diagonal of an axis-aligned mesh)
     INSIDE_DIRECTIONS = ((0.8164, 0.4082, 0.4083), (-0.3015, 0.9045, 0.3016), (0.2673, -0.5345, 0.8018))
 
@@ -1020,6 +1062,14 @@ def resolve_sh(sh, n_draws):
     radiance around each point, bands 0 .. 2 in rrt.h's order, in the point's local frame."""
     s = np.asarray(sh, np.float64)
     return (4.0 * np.pi / float(n_draws)) * s.reshape(s.shape[:-1] + (9, 3))
+
+
+def unpack_visibility(bits, n_b):
+    """The packed words of Renderer.visibility -> bool: bits (n_a, words) -> (n_a, n_b), bit j & 63 of word j // 64 of a row; a pairs=True result
+    (words,) -> (n_b,)."""
+    b = np.ascontiguousarray(bits, np.uint64)
+    j = np.arange(int(n_b))
+    return ((b[..., j // 64] >> (j % 64).astype(np.uint64)) & np.uint64(1)).astype(bool)
 
 
 def resolve_moments(m):

@@ -6,6 +6,7 @@
 #include "dtexture.hpp"
 #include "nearest.hpp"   // rrt_nearest: the per-triangle function and the walk, shared with the host (tools/nearest_check.cpp)
 #include "multihit.hpp"  // rrt_trace_all: the triangle test, the slab test, the sorted insert and the walk, shared with the host (tools/trace_all_check.cpp)
+#include "visibility.hpp"  // rrt_visibility: the segment, the first-accept walk and the scan, shared with the host (tools/visibility_check.cpp)
 
 namespace rrtd {
 
@@ -34,7 +35,8 @@ enum { ERR_SHADING_NORMAL = 1, ERR_BETA = 4, ERR_NULL_BSDF = 8, ERR_MIPMAP = 16,
        ERR_INGEST = 512 /* k_ingest_rays: a pixel or sample_num of rrt_ray_samples outside the film / outside 1 .. nsamp-1 */,
        ERR_SITE = 1024 /* k_sites_check: a site of rrt_sites that rrt_surface_at refuses */,
        ERR_NEAREST = 2048 /* k_nearest / k_nearest_pairs_f32: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */,
-       ERR_TRACE_ALL = 4096 /* k_trace_all: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */ };
+       ERR_TRACE_ALL = 4096 /* k_trace_all: a walk passed its step or stack bound, or met a word outside its arrays (a tree that is none) */,
+       ERR_VISIBILITY = 8192 /* k_visibility: the same, for a rrt_visibility walk */ };
 static_assert(ERR_ST_DIMS == kErrStDims, "error bit shared with dmath.hpp");
 static_assert(ERR_HALTON_DIMS == kErrHaltonDims, "error bit shared with dmath.hpp");
 
@@ -3003,6 +3005,69 @@ __global__ void __launch_bounds__(kBlock) k_trace_all(const Node<R>* nodes, uint
       io.t[at] = io.tmax[g]; io.prim[at] = -1;
       if (io.b1) { io.b1[at] = R(0); io.b2[at] = R(0); }
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Mutual visibility of two point sets as a packed bit matrix (rrt_visibility, include/rrt.h): one lane per pair over the linear tree
+// (host/visibility.hpp vis_segment, vis_walk). A wavefront is one output word: task w of the call is word w % words of row w / words in MATRIX mode -
+// 64 consecutive columns of ONE row, so the row's point, normal and skip entry are wave-uniform loads (readfirstlane puts the row index into an SGPR)
+// and the column loads are coalesced - and rows 64 w .. 64 w + 63 in PAIRS mode. The 64 verdicts are collected with one __ballot and lane 0 stores
+// the word with an ordinary 64-bit store; lanes past the last column (row) vote 0, which is the zero padding. count[row] += popcount(word) by one
+// integer atomicAdd per word into a plane the driver zeroed: integer sums are order-free. The stack is k_trace_all's: private up to 64 deep,
+// [entry][thread of the launch] in global memory beyond (DEEP). A launch holds whole waves only (n_tasks x 64 threads), so the early return below
+// retires whole waves and every lane of a live wave reaches the ballot.
+// ------------------------------------------------------------------------------------------------------------
+template <typename R>
+struct VisIO {
+  const R *ax, *ay, *az, *anx, *any, *anz;   // normals: all null or all set
+  const R *bx, *by, *bz, *bnx, *bny, *bnz;
+  const int32_t *skip_a, *skip_b;            // may be null
+  uint64_t* bits;
+  uint32_t* count;                           // may be null (MATRIX); null in PAIRS
+  uint32_t n_a, n_b, words;                  // words per row (MATRIX)
+  int32_t mode, b_kind;
+  uint32_t flags;
+  R off_a, off_b, delta;
+};
+template <typename R, bool DEEP>
+__global__ void __launch_bounds__(kBlock) k_visibility(const Node<R>* nodes, uint32_t n_nodes, const Tri<R>* tris, uint32_t n_tris, const InstDev<R>* insts, uint32_t* err, VisIO<R> io,
+                                                        unsigned long long task0, uint32_t n_tasks, uint32_t* stack, uint32_t stride, uint32_t stack_cap) {
+  const uint32_t th = blockIdx.x * blockDim.x + threadIdx.x;   // thread of the launch
+  if ((th >> 6) >= n_tasks) return;                             // (whole waves)
+  const unsigned long long w = task0 + (th >> 6);
+  const uint32_t lane = th & 63u;
+  uint32_t i, j;
+  bool in_range;
+  if (io.mode == kVisMatrix) {
+    i = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w / io.words));
+    j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w % io.words)) * 64u + lane;
+    in_range = j < io.n_b;
+  } else {
+    i = j = (uint32_t)w * 64u + lane;
+    in_range = i < io.n_a;
+  }
+  bool visible = false;
+  if (in_range) {
+    const bool an = io.anx != nullptr, bn = io.bnx != nullptr;
+    const VisEnd<R> a = vis_end<R>(io.ax[i], io.ay[i], io.az[i], an, an ? io.anx[i] : R(0), an ? io.any[i] : R(0), an ? io.anz[i] : R(0), io.off_a);
+    const VisEnd<R> b = vis_end<R>(io.bx[j], io.by[j], io.bz[j], bn, bn ? io.bnx[j] : R(0), bn ? io.bny[j] : R(0), bn ? io.bnz[j] : R(0), io.off_b);
+    MhRay<R> r;
+    const VisVerdict v = vis_segment<R>(a, b, io.b_kind, io.flags, &r);
+    visible = v == kVisYes;
+    if (v == kVisTrace) {
+      const int32_t sa = io.skip_a ? io.skip_a[i] : -1, sb = io.skip_b ? io.skip_b[j] : -1;
+      bool ok, blocked = true;
+      if (DEEP) { GlobStack st{stack + th, stride}; ok = vis_walk<R>(nodes, n_nodes, tris, n_tris, insts, r, sa, sb, io.delta, st, stack_cap, &blocked); }
+      else { PrivStack st; ok = vis_walk<R>(nodes, n_nodes, tris, n_tris, insts, r, sa, sb, io.delta, st, stack_cap < 64u ? stack_cap : 64u, &blocked); }
+      if (!ok) { atomicOr(err, (uint32_t)ERR_VISIBILITY); blocked = true; }
+      visible = !blocked;
+    }
+  }
+  const unsigned long long word = __ballot(visible);
+  if (lane == 0u) {
+    io.bits[w] = word;
+    if (io.count) atomicAdd(io.count + i, (uint32_t)__popcll(word));
   }
 }
 

@@ -241,6 +241,48 @@ int rrt_trace_all(rrt_handle* h, const rrt_rays* rays, size_t n, rrt_multi_hits*
   return guarded([&]() { h->impl->trace_all(rays, n, out); });
 }
 
+int rrt_visibility(rrt_handle* h, const rrt_points* a, size_t n_a, const rrt_points* b, size_t n_b, const rrt_vis_params* params, rrt_vis_out* out) {
+  auto bad = [&](const char* what) { rrt::set_last_error(std::string("rrt_visibility: ") + what); return (int)RRT_EINVAL; };
+  const rrt_vis_params defaults = {RRT_VIS_MATRIX, RRT_VIS_POINTS, 0u, 0, 0.0, 0.0, nullptr, nullptr};
+  const rrt_vis_params* p = params ? params : &defaults;
+  if (!a) return bad("null point description a (rrt_points)");
+  if (!b) return bad("null point description b (rrt_points)");
+  if (!out) return bad("null output description (rrt_vis_out)");
+  if (!a->px || !a->py || !a->pz) return bad("null coordinate array of a");
+  if (!b->px || !b->py || !b->pz) return bad("null coordinate array of b");
+  if (!out->bits) return bad("null bits");
+  const bool an = a->nx && a->ny && a->nz, bn = b->nx && b->ny && b->nz;
+  if (!an && (a->nx || a->ny || a->nz)) return bad("the normals of a must all be NULL or all be set");
+  if (!bn && (b->nx || b->ny || b->nz)) return bad("the normals of b must all be NULL or all be set");
+  if (a->mem != RRT_MEM_HOST && a->mem != RRT_MEM_DEVICE) return bad("bad mem");
+  if (b->mem != a->mem || out->mem != a->mem) return bad("a, b and the outputs must live in the same memory kind (mem)");
+  if (a->precision != b->precision) return bad("a and b must have the same precision");
+  if (n_a == 0 || n_b == 0) return bad("n_a and n_b must be > 0");
+  if (n_a > 0x7fffffffu || n_b > 0x7fffffffu) return bad("n_a or n_b too large (above 2^31 - 1)");
+  if ((uint64_t)n_a * (uint64_t)n_b > ((uint64_t)1 << 40)) return bad("n_a * n_b too large (above 2^40)");
+  if (p->mode != RRT_VIS_MATRIX && p->mode != RRT_VIS_PAIRS) return bad("bad mode");
+  if (p->b_kind != RRT_VIS_POINTS && p->b_kind != RRT_VIS_DIRECTIONS) return bad("bad b_kind");
+  if ((p->flags & ~(uint32_t)(RRT_VIS_FACING_A | RRT_VIS_FACING_B)) != 0u) return bad("bad flags");
+  if (!(p->offset_a - p->offset_a == 0.0)) return bad("offset_a must be finite");
+  if (!(p->offset_b - p->offset_b == 0.0)) return bad("offset_b must be finite");
+  if (!an && p->offset_a != 0.0) return bad("offset_a needs the normals of a");
+  if (!an && (p->flags & RRT_VIS_FACING_A)) return bad("RRT_VIS_FACING_A needs the normals of a");
+  if (p->b_kind == RRT_VIS_DIRECTIONS) {
+    if (bn) return bad("RRT_VIS_DIRECTIONS: b is a set of directions and takes no normals");
+    if (p->offset_b != 0.0) return bad("RRT_VIS_DIRECTIONS: offset_b must be 0");
+    if (p->flags & RRT_VIS_FACING_B) return bad("RRT_VIS_DIRECTIONS: RRT_VIS_FACING_B has no meaning");
+    if (p->skip_b) return bad("RRT_VIS_DIRECTIONS: skip_b must be NULL");
+  }
+  if (!bn && p->offset_b != 0.0) return bad("offset_b needs the normals of b");
+  if (!bn && (p->flags & RRT_VIS_FACING_B)) return bad("RRT_VIS_FACING_B needs the normals of b");
+  if (p->mode == RRT_VIS_PAIRS) {
+    if (n_b != n_a) return bad("RRT_VIS_PAIRS: n_b must equal n_a");
+    if (out->count) return bad("RRT_VIS_PAIRS: count must be NULL");
+  }
+  if (!h) return bad("null handle");
+  return guarded([&]() { h->impl->visibility(a, n_a, b, n_b, p, out); });
+}
+
 int rrt_render_rays(rrt_handle* h, const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_xyzw, int film_mem,
                     rrt_render_stats* stats) {
   if (const int rc = ray_samples_check("rrt_render_rays", rays, false); rc != RRT_OK) return rc;

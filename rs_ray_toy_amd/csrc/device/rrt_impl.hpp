@@ -53,6 +53,7 @@ struct HandleBase {
   virtual void atlas_sites(int32_t aw, int32_t ah, const int32_t* prims, size_t n_list, int mem, int32_t* site_prim, void* b1, void* b2, uint64_t* n_covered) = 0;
   virtual void nearest(const rrt_points* pts, size_t n, double max_dist, const rrt_nearest_out* out) = 0;
   virtual void trace_all(const rrt_rays* rays, size_t n, const rrt_multi_hits* out) = 0;
+  virtual void visibility(const rrt_points* a, size_t n_a, const rrt_points* b, size_t n_b, const rrt_vis_params* prm, const rrt_vis_out* out) = 0;
   virtual void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film, int film_mem, rrt_render_stats* stats) = 0;   // p_film in rays->mem
   virtual void render_bands(int rank, int world, void* film, int film_mem, rrt_render_stats* stats) = 0;
   virtual void render_bands_begin(int rank, int world, void* film_device) = 0;
@@ -856,6 +857,71 @@ class Handle : public HandleBase {
     HIP_CHECK(hipStreamSynchronize(st_));
     check_device_errors();
   }
+  // ---- mutual visibility of two point sets as a packed bit matrix: rrt_visibility ------------------------------------------------------------------
+  // One lane per pair, one wave per output word (k_visibility), no pool and no queue. The words are cut into launches of at most max_paths (and 2^20)
+  // threads, whole waves each, only to bound the deep stack array (trace_all's mh_stack_); a pair's bit depends on the pair alone, so the cut changes
+  // no bit. The count plane is zeroed here and summed by integer atomics. Host arrays are staged and copied back per array, as trace_all's.
+  void visibility(const rrt_points* a, size_t n_a, const rrt_points* b, size_t n_b, const rrt_vis_params* prm, const rrt_vis_out* out) override {
+    const std::string who("rrt_visibility");
+    check_args(who, kWhenIdle, Prec{"a", a->precision});
+    if (b->precision != precision()) throw std::invalid_argument(who + ": b precision must match the handle");
+    if (!nn_has_tri_) throw UnsupportedError(who + ": the scene has no triangle entry (spheres are not candidates)");
+    HIP_CHECK(hipSetDevice(dev_));
+    HIP_CHECK(hipMemsetAsync(counters_.p + C_ERROR, 0, sizeof(uint32_t), st_));
+    const bool host = a->mem != RRT_MEM_DEVICE;
+    const bool pairs = prm->mode == RRT_VIS_PAIRS;
+    const bool an = a->nx != nullptr, bn = b->nx != nullptr;
+    const size_t words = (n_b + 63) / 64;
+    const size_t n_tasks = pairs ? (n_a + 63) / 64 : n_a * words;   // one wave, one output word each
+    VisIO<R> io{};
+    io.ax = (const R*)a->px; io.ay = (const R*)a->py; io.az = (const R*)a->pz; io.anx = (const R*)a->nx; io.any = (const R*)a->ny; io.anz = (const R*)a->nz;
+    io.bx = (const R*)b->px; io.by = (const R*)b->py; io.bz = (const R*)b->pz; io.bnx = (const R*)b->nx; io.bny = (const R*)b->ny; io.bnz = (const R*)b->nz;
+    io.skip_a = prm->skip_a; io.skip_b = prm->skip_b; io.bits = out->bits; io.count = out->count;
+    io.n_a = (uint32_t)n_a; io.n_b = (uint32_t)n_b; io.words = (uint32_t)words; io.mode = prm->mode; io.b_kind = prm->b_kind; io.flags = prm->flags;
+    io.off_a = (R)prm->offset_a; io.off_b = (R)prm->offset_b; io.delta = mh_delta_;
+    DevBuf<R> stage_a, stage_b;
+    DevBuf<int32_t> stage_skip_a, stage_skip_b;
+    DevBuf<uint64_t> stage_bits;
+    DevBuf<uint32_t> stage_count;
+    if (host) {
+      auto stage = [&](DevBuf<R>& buf, const rrt_points* s, size_t n, bool normals, const R** dst) {
+        buf.alloc((normals ? 6 : 3) * n);
+        const void* src[6] = {s->px, s->py, s->pz, s->nx, s->ny, s->nz};
+        for (int k = 0; k < (normals ? 6 : 3); k++) {
+          HIP_CHECK(hipMemcpyAsync(buf.p + (size_t)k * n, src[k], n * sizeof(R), hipMemcpyHostToDevice, st_));
+          dst[k] = buf.p + (size_t)k * n;
+        }
+      };
+      const R* pa[6] = {}; const R* pb[6] = {};
+      stage(stage_a, a, n_a, an, pa); stage(stage_b, b, n_b, bn, pb);
+      io.ax = pa[0]; io.ay = pa[1]; io.az = pa[2]; io.anx = pa[3]; io.any = pa[4]; io.anz = pa[5];
+      io.bx = pb[0]; io.by = pb[1]; io.bz = pb[2]; io.bnx = pb[3]; io.bny = pb[4]; io.bnz = pb[5];
+      if (prm->skip_a) { stage_skip_a.alloc(n_a); HIP_CHECK(hipMemcpyAsync(stage_skip_a.p, prm->skip_a, n_a * sizeof(int32_t), hipMemcpyHostToDevice, st_)); io.skip_a = stage_skip_a.p; }
+      if (prm->skip_b) { stage_skip_b.alloc(n_b); HIP_CHECK(hipMemcpyAsync(stage_skip_b.p, prm->skip_b, n_b * sizeof(int32_t), hipMemcpyHostToDevice, st_)); io.skip_b = stage_skip_b.p; }
+      stage_bits.alloc(n_tasks); io.bits = stage_bits.p;
+      if (out->count) { stage_count.alloc(n_a); io.count = stage_count.p; }
+    }
+    if (io.count) HIP_CHECK(hipMemsetAsync(io.count, 0, n_a * sizeof(uint32_t), st_));
+    const size_t per_pass = std::min<size_t>({n_tasks, std::max<size_t>(1, max_paths_ / 64), (size_t)1 << 14});   // waves of a launch: at most 2^20 threads
+    const uint32_t depth = scene_.stack_depth;
+    const size_t stride = (per_pass * 64 + kBlock - 1) / kBlock * kBlock;   // threads of a launch
+    if (deep_ && mh_stack_.n < (size_t)depth * stride) mh_stack_.alloc((size_t)depth * stride);
+    for (size_t t0 = 0; t0 < n_tasks; t0 += per_pass) {
+      const uint32_t m = (uint32_t)std::min(per_pass, n_tasks - t0);
+      const dim3 grid((uint32_t)(((size_t)m * 64 + kBlock - 1) / kBlock));
+      with_flag(deep_, [&](auto DEEP) {
+        hipLaunchKernelGGL((k_visibility<R, DEEP()>), grid, dim3(kBlock), 0, st_, scene_.nodes, scene_.n_nodes, scene_.tris, scene_.n_tris, scene_.insts, counters_.p + C_ERROR, io,
+                           (unsigned long long)t0, m, deep_ ? mh_stack_.p : nullptr, (uint32_t)stride, depth);
+      });
+    }
+    HIP_CHECK(hipGetLastError());
+    if (host) {
+      HIP_CHECK(hipMemcpyAsync(out->bits, io.bits, n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost, st_));
+      if (out->count) HIP_CHECK(hipMemcpyAsync(out->count, io.count, n_a * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+    }
+    HIP_CHECK(hipStreamSynchronize(st_));
+    check_device_errors();
+  }
   void render_rays(const int32_t rect[4], uint64_t s0, uint64_t s1, const rrt_ray_samples* rays, const void* p_film, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("rrt_render_rays", kWhenIdle, Prec{"ray", rays->precision}, {}, rect);
     if (s0 < 1 || s1 > desc_.sampler.samples_per_pixel || s0 >= s1) throw std::invalid_argument("rrt_render_rays: sample range outside [1, nsamp) or empty");
@@ -932,6 +998,7 @@ class Handle : public HandleBase {
     if (err & ERR_KIND_SET) throw DeviceError("internal: a material produced a BxDF outside the kind set its shading kernel was selected for (shade_spec())");
     if (err & ERR_NEAREST) throw DeviceError("internal: a rrt_nearest walk passed its step or stack bound (the tree is not the tree its depth and node count describe)");
     if (err & ERR_TRACE_ALL) throw DeviceError("internal: a rrt_trace_all walk passed its step or stack bound (the tree is not the tree its depth and node count describe)");
+    if (err & ERR_VISIBILITY) throw DeviceError("internal: a rrt_visibility walk passed its step or stack bound (the tree is not the tree its depth and node count describe)");
   }
   void render_bands(int rank, int world, void* film_user, int film_mem, rrt_render_stats* stats) override {
     check_args("render_bands", kAnyTime, {}, Ranks{rank, world});
